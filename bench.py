@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Bench: batched Accord dependency calculation on MI355X through the C ABI.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, runs W warmup steps, times K steps and prints the result line (metric, value, ms_per_step and the
+workload's sizes). --dump-outputs DIR then writes what the last timed step computed (the arrays of the result view a
+caller copies out) as DIR/<name>.npy. --full adds everything that takes runs of its own: the per-kernel breakdown and
+the roofline (untimed diagnostic steps with every launch bracketed by HIP events), the CPU baselines, the
+CommandsForKey legs of config 2 and the mixed-batch legs of config 4.
 
 --config 2 (default; BASELINE.json configs[1], the metric's workload): KeyDeps of 1M txns x 8 keys, zipf(0.99) over
 1M keys, read/write mix, status model of SURVEY.md §8(d). A step = one acc_keydeps_batch over the whole batch
@@ -71,6 +77,17 @@ def keydeps_bytes(n_txn, n_pairs, sum_kd, sum_e, sum_u):
     b_in = 8 * n_pairs + 4 * (n_txn + 1) + 41 * n_txn
     b_out = 4 * (sum_kd + sum_e) + 4 * sum_kd + 4 * sum_u + 8 * (n_txn + 1)
     return b_in, b_out
+
+
+def keydeps_outputs(kd):
+    """The arrays of a BatchKeyDeps (acc_keydeps_copy_out of the step's view), by name."""
+    return {f: getattr(kd, f) for f in ("arena_off", "arena", "kd_off", "key_idx", "u_off", "dep_txn")}
+
+
+def rangedeps_outputs(rd):
+    """The arrays of a BatchRangeDeps (acc_rangedeps_copy_out of the step's view), by name."""
+    return {f: getattr(rd, f) for f in ("rng_start", "rng_end", "arena_off", "arena", "rd_off", "range_id", "u_off",
+                                        "dep_txn")}
 
 
 def rangedeps_bytes(n_txn, n_pairs, n_ranges, sum_rd, sum_e, sum_u, n_dict):
@@ -267,6 +284,9 @@ def dist_setup(args):
 
 
 DIAG_STEPS = 2
+# environment knobs of the legs that only run with --full
+FULL_ONLY_ENV = ("ACC_BENCH_KERNELS", "ACC_BENCH_NOTIME", "ACC_BENCH_CFK", "ACC_BENCH_MIXED", "ACC_CPU_THREADS",
+                 "ACC_CPU_STRIDE", "ACC_CPU_STRIDE3", "ACC_CPU_STRIDE_RD")
 
 
 def timed_steps(args, world, dev, step):
@@ -305,12 +325,45 @@ def timed_steps(args, world, dev, step):
         e = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == "nccl" else "cpu")
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, step.outputs())
     return elapsed
 
 
+DUMP_BYTES = 60 << 20   # all of a dump's arrays together (float64 elements), under the 64 MB a dump may take
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy (float64) for each array of the last timed step's result, every value exact: a 64-bit integer
+    array that holds a value of 2^53 or more (key codes, range bounds) is written as its two 32-bit halves,
+    <name>_hi and <name>_lo. An array longer than its share of DUMP_BYTES is written as a fixed sample: the elements
+    at sorted positions drawn once from a seeded generator (the same positions whenever the length is the same).
+    DIR/sizes.npy holds every written array's full length, in the order of the sorted names."""
+    os.makedirs(path, exist_ok=True)
+    exact = {}
+    for k, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if (a.dtype.kind in "iu" and a.dtype.itemsize == 8 and a.size
+                and (int(a.max()) >= 1 << 53 or int(a.min()) <= -(1 << 53))):
+            bits = a.view(np.uint64)
+            exact[k + "_hi"], exact[k + "_lo"] = bits >> np.uint64(32), bits & np.uint64(0xFFFFFFFF)
+        else:
+            exact[k] = a
+    arrays = exact
+    names = sorted(arrays)
+    cap = DUMP_BYTES // 8 // max(len(names), 1)
+    for k in names:
+        a = np.asarray(arrays[k]).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0xACC0D).integers(0, a.size, cap))]
+        np.save(os.path.join(path, k + ".npy"), a.astype(np.float64))
+    np.save(os.path.join(path, "sizes.npy"), np.array([np.asarray(arrays[k]).size for k in names], np.float64))
+
+
 class Step:
-    def __init__(self, ctx, fn):
-        self.ctx, self.fn, self.view = ctx, fn, None
+    def __init__(self, ctx, fn, outputs=None):
+        """outputs(): the host arrays of the last step's result, by name (what --dump-outputs writes)."""
+        self.ctx, self.fn, self.view, self.outputs = ctx, fn, None, outputs
         self.diag = self.live = None
 
     def __call__(self):
@@ -335,8 +388,9 @@ def run_config2(args, world, rank, local, dev):
                    L.TsCols(t["txn_msb"].data_ptr(), t["txn_lsb"].data_ptr(), t["txn_node"].data_ptr()),
                    L.TsCols(t["exe_msb"].data_ptr(), t["exe_lsb"].data_ptr(), t["exe_node"].data_ptr()),
                    t["status"].data_ptr(), t["key_off"].data_ptr(), t["key_code"].data_ptr())
-    ctx = Context(local, timing=os.environ.get("ACC_BENCH_NOTIME") != "1")   # NOTIME: overhead probe only
-    step = Step(ctx, lambda: ctx.keydeps_batch_raw(bi))
+    # timing context (--full): the breakdown and the roofline; ACC_BENCH_NOTIME: overhead probe only
+    ctx = Context(local, timing=args.full and os.environ.get("ACC_BENCH_NOTIME") != "1")
+    step = Step(ctx, lambda: ctx.keydeps_batch_raw(bi), lambda: keydeps_outputs(ctx.copy_out(step.view)))
     elapsed = timed_steps(args, world, dev, step)
     view = step.view
     timing = step.diag
@@ -362,9 +416,11 @@ def run_config2(args, world, rank, local, dev):
             "parallelism": f"keyspace shards x{world} (independent CommandStores)",
         },
         "dep_edges_per_s": round(int(view.total_edges) * world * args.steps / elapsed, 1),
-        "roofline": roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config, variant,
-                             profiled=args.scale == 1.0),
     }
+    if not args.full:
+        return ctx, timing, elapsed, result
+    result["roofline"] = roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config, variant,
+                                  profiled=args.scale == 1.0)
     if rank == 0 and world == 1 and not args.no_cpu:
         # config 3: the O(prefix) scans of the 5M-txn hot key make each sampled query cost ~10 ms: sparser sample
         result["cpu_baseline"] = (keydeps_cpu_baseline(batch, "config 3", "ACC_CPU_STRIDE3", 20_000) if c3 else
@@ -581,7 +637,7 @@ def run_config2_sharded(args, world, rank, local, dev):
     t_gen = time.perf_counter() - t_gen
     bi, keep = S.batch_in_device(sub, dev)
     gidx = torch.from_numpy(g.astype(np.int32)).to(dev)
-    ctx = Context(local, timing=True)
+    ctx = Context(local, timing=args.full)
     info = {}
     # the exchange behind the C ABI (what a JVM host calls): an acc_comm over RCCL (its 128-byte id broadcast once at
     # setup) and acc_shard_reduce = pack + one size exchange + one grouped all-to-all(v) + KeyDeps.with fold
@@ -644,8 +700,10 @@ def run_config2_sharded(args, world, rank, local, dev):
         "exchange": {"bytes_sent_total": int(tot[1].item()), "bytes_sent_max_rank": int(mx[1].item()),
                      "path": exchange,
                      "setup_backend": dist.get_backend() + (" (RCCL over xGMI)" if dist.get_backend() == "nccl" else "")},
-        "roofline": roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config, profiled=False),
     }
+    if args.full:
+        result["roofline"] = roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config,
+                                      profiled=False)
     return ctx, timing, elapsed, result
 
 
@@ -665,8 +723,8 @@ def run_config4(args, world, rank, local, dev):
                         t["status"].data_ptr(), t["key_off"].data_ptr(), t["key_code"].data_ptr(),
                         t["rng_off"].data_ptr(), t["rng_start"].data_ptr(), t["rng_end"].data_ptr(),
                         int(rb.end_inclusive), 0)
-    ctx = Context(local, timing=True)
-    step = Step(ctx, lambda: ctx.rangedeps_batch_raw(bi))
+    ctx = Context(local, timing=args.full)
+    step = Step(ctx, lambda: ctx.rangedeps_batch_raw(bi), lambda: rangedeps_outputs(ctx.copy_out_range(step.view)))
     elapsed = timed_steps(args, world, dev, step)
     view = step.view
     timing = step.diag
@@ -688,9 +746,11 @@ def run_config4(args, world, rank, local, dev):
             "parallelism": f"keyspace shards x{world} (independent CommandStores)",
         },
         "dep_entries_per_s": round(int(view.total_edges) * world * args.steps / elapsed, 1),
-        "roofline": roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config,
-                             profiled=args.scale == 1.0),
     }
+    if not args.full:
+        return ctx, timing, elapsed, result
+    result["roofline"] = roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config,
+                                  profiled=args.scale == 1.0)
     if os.environ.get("ACC_BENCH_MIXED", "1") != "0":
         result["keydeps_mixed"] = mixed_keydeps_leg(bi, local)
         result["partial_deps"] = partial_deps_leg(bi, local)
@@ -732,7 +792,7 @@ def run_config4_sharded(args, world, rank, local, dev):
                         t["status"].data_ptr(), t["key_off"].data_ptr(), t["key_code"].data_ptr(),
                         t["rng_off"].data_ptr(), t["rng_start"].data_ptr(), t["rng_end"].data_ptr(),
                         int(sub.end_inclusive), 0)
-    ctx = Context(local, timing=True)
+    ctx = Context(local, timing=args.full)
     if dist.get_backend() == "gloo":   # the one-GPU rehearsal: every rank on GPU 0, the host transport over gloo
         comm, exchange = S.Comm.host(ctx, world, rank), "acc_comm (host transport over gloo) + acc_partial_deps_reduce"
     else:
@@ -779,8 +839,10 @@ def run_config4_sharded(args, world, rank, local, dev):
         },
         "exchange": {"bytes_sent_total": int(tot[1].item()), "bytes_sent_max_rank": int(mx[1].item()), "path": exchange,
                      "setup_backend": dist.get_backend() + (" (RCCL over xGMI)" if dist.get_backend() == "nccl" else "")},
-        "roofline": roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config, profiled=False),
     }
+    if args.full:
+        result["roofline"] = roofline(b_in + b_out, step, args.steps, elapsed * 1000.0 / args.steps, args.config,
+                                      profiled=False)
     return ctx, step.diag, elapsed, result
 
 
@@ -901,7 +963,7 @@ def run_config5(args, world, rank, local, dev):
     import torch
     from accord_amd import _lib as L
     from accord_amd import workload as W
-    from accord_amd.deps import Context, merge_levelise_device
+    from accord_amd.deps import Context, merge_copy_out, merge_levelise_device
 
     seed = W.CONFIG_SEEDS["5"] + 0x1000 * rank
     n_txn = int(16_384 * args.scale)
@@ -916,13 +978,16 @@ def run_config5(args, world, rank, local, dev):
     mi = L.MergeIn(L.ACC_MEM_DEVICE, n_txn, len(m["key_off"]) - 1,
                    *(t[k].data_ptr() for k in ("grp_off", "key_off", "key_code", "val_off", "txn_rank", "k2v_off",
                                                "k2v")))
-    ctx = Context(local, timing=True)
+    ctx = Context(local, timing=args.full)
 
     def fn():
         view, nl[0] = merge_levelise_device(ctx, mi, er.data_ptr(), level.data_ptr(), order.data_ptr())
         return view
 
-    step = Step(ctx, fn)
+    def outputs():
+        return dict(merge_copy_out(ctx, step.view), level=level.cpu().numpy(), order=order.cpu().numpy(), n_levels=nl)
+
+    step = Step(ctx, fn, outputs)
     elapsed = timed_steps(args, world, dev, step)
     view = step.view
     timing = step.diag
@@ -944,9 +1009,11 @@ def run_config5(args, world, rank, local, dev):
             "levels": int(nl[0]),
             "parallelism": f"independent coordinators x{world}",
         },
-        "roofline": roofline(merge_bytes(m, view, n_txn, int(view.total_vals)), step, args.steps,
-                             elapsed * 1000.0 / args.steps, args.config, profiled=args.scale == 1.0),
     }
+    if not args.full:
+        return ctx, timing, elapsed, result
+    result["roofline"] = roofline(merge_bytes(m, view, n_txn, int(view.total_vals)), step, args.steps,
+                                  elapsed * 1000.0 / args.steps, args.config, profiled=args.scale == 1.0)
     if rank == 0 and world == 1 and not args.no_cpu:
         result["cpu_baseline"] = merge_cpu_baseline(m, exec_rank, n_in)
     return ctx, timing, elapsed, result
@@ -961,8 +1028,18 @@ def main():
     ap.add_argument("--scale", type=float, default=1.0, help="fraction of the config (testing only)")
     ap.add_argument("--dist", default="zipf", choices=["zipf", "uniform"], help="key distribution (configs 2, 3)")
     ap.add_argument("--unpermuted", action="store_true", help="zipf hot keys at the low end of the key space")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's result arrays as DIR/<name>.npy "
+                                                          "(float64, exact; a fixed seeded sample of the long ones)")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel breakdown and roofline, the CPU baseline "
+                                                        "and the config's further legs")
     args = ap.parse_args()
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs writes one store's result: run it with --gpus 1")
+    if not args.full:
+        ignored = (["--no-cpu"] if args.no_cpu else []) + [k for k in FULL_ONLY_ENV if k in os.environ]
+        if ignored and os.environ.get("RANK", "0") == "0":
+            print(f"bench.py: {', '.join(ignored)} only matter with --full; this plain run ignores them", file=sys.stderr)
 
     world, rank, local, dev = dist_setup(args)
     keyed = run_config2 if world == 1 else run_config2_sharded

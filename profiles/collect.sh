@@ -15,7 +15,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 export ACC_BENCH_MIXED=0   # profile the config-4 RangeDeps step alone (the mixed-batch KeyDeps leg runs after it)
 export ACC_BENCH_CFK=0     # likewise the config-2 CommandsForKey-update leg
-bench="$root/bench.py --config $cfg --steps 5 --warmup 2 --no-cpu $*"
+bench="$root/bench.py --config $cfg --steps 5 --warmup 2 --full --no-cpu $*"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o run -- \
     python3 $bench > "$out/trace.log" 2>&1 || { echo "trace pass failed: $?"; tail -5 "$out/trace.log"; exit 1; }
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/fetch" -o run -- \

@@ -11,7 +11,7 @@ for cfg in ${CFGS:-2}; do
         for v in "$@"; do
             lib=""; envs=""
             case "$v" in new) ;; new+*) envs="${v#new+}"; envs="${envs//,/ }" ;; *) lib=tools/ab/$v.so ;; esac
-            env $envs ACC_BENCH_CFK=0 ACC_BENCH_KERNELS=1 ACC_LIB_PATH=$lib timeout -k 10 300 python -u bench.py --config $cfg --steps $steps --warmup 3 --no-cpu \
+            env $envs ACC_BENCH_CFK=0 ACC_BENCH_KERNELS=1 ACC_LIB_PATH=$lib timeout -k 10 300 python -u bench.py --config $cfg --steps $steps --warmup 3 --full --no-cpu \
                 > gpurun_out/abn_c${cfg}_${v}_$i.log 2>&1 || { echo "bench $v c$cfg failed"; tail -20 gpurun_out/abn_c${cfg}_${v}_$i.log; exit 1; }
             python -c "
 import json; d=json.loads(open('gpurun_out/abn_c${cfg}_${v}_$i.log').read().strip().splitlines()[-1])

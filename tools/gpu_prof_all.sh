@@ -6,11 +6,15 @@ cd "$GRAFT_REPO_ROOT"
 tag=$1; shift
 mkdir -p gpurun_out
 for cfg in "$@"; do
-    bash profiles/collect.sh "$tag" "$cfg" || exit 1
+    # collect.sh ends with "profiles collected under <directory>": the bench lines go beside that directory
+    prof=$(bash profiles/collect.sh "$tag" "$cfg" | tee /dev/stderr | sed -n 's/^profiles collected under //p') || exit 1
+    [ -d "$prof" ] || { echo "collect.sh named no profile directory for c$cfg"; exit 1; }
     echo "profiled c$cfg"
 done
+logs=$(dirname "$prof")
 for cfg in "$@"; do
-    ACC_BENCH_KERNELS=1 timeout -k 10 400 python -u bench.py --config $cfg > gpurun_out/bench_c$cfg.log 2>&1 \
-        || { echo "bench c$cfg failed"; tail -30 gpurun_out/bench_c$cfg.log; exit 1; }
-    tail -1 gpurun_out/bench_c$cfg.log | cut -c1-300
+    log=$logs/bench_c$cfg.log
+    ACC_BENCH_KERNELS=1 timeout -k 10 600 python -u bench.py --config $cfg --full > "$log" 2>&1 \
+        || { echo "bench c$cfg failed"; tail -30 "$log"; exit 1; }
+    tail -1 "$log" | cut -c1-300
 done

@@ -1,7 +1,7 @@
 """Config-2 KeyDeps phase breakdown -> profiles/<round>_config2_phases.json.
 
 Inputs (both from one GPU box): a bench log of the product library with per-kernel timings
-(ACC_BENCH_KERNELS=1 python bench.py --config 2 ...) and a log of the tuning build (tools/build_prof.sh ->
+(ACC_BENCH_KERNELS=1 python bench.py --config 2 --full ...) and a log of the tuning build (tools/build_prof.sh ->
 tools/ab/prof.so, -DACC_PHASE_PROF) whose stderr carries the count pass's [ct_phase] and the stream pass's [st_phase]
 per-wave cycle counters. Usage: python tools/phases_json.py KERNELS_LOG PROF_LOG OUT_JSON"""
 import json
