@@ -54,17 +54,7 @@ namespace acc {
 
 namespace cf {
 
-constexpr uint64_t IDENTITY_LSB = 0xFFFFFFFFFFFF001EULL;
 enum : uint64_t { E_STATUS = 1, E_KIND = 2, E_KEYS = 4, E_STALE = 8, E_OFF = 16, E_DUP = 32 };
-
-__device__ __forceinline__ int ts_cmp(uint64_t am, uint64_t al, int32_t an, uint64_t bm, uint64_t bl, int32_t bn)
-{
-    if (am != bm) return am < bm ? -1 : 1;
-    const uint64_t a1 = al & IDENTITY_LSB, b1 = bl & IDENTITY_LSB;
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (an != bn) return an < bn ? -1 : 1;
-    return 0;
-}
 
 __host__ __device__ inline bool has_info(uint32_t s) { return s >= ACC_ST_ACCEPTED && s <= ACC_ST_APPLIED; }
 

@@ -27,7 +27,6 @@
 namespace acc {
 namespace cd {
 
-constexpr uint64_t IDENTITY_LSB = 0xFFFFFFFFFFFF001EULL;
 constexpr uint32_t NONE_K = 0xFFFFFFFFu;
 enum : uint32_t { TK = 0, PRE = 2, ACC = 3, COMMITTED = 4, APPLIED = 6, INVALID = 7 };
 enum : uint64_t { E_ARG_STATUS = 1, E_ARG_SORT = 2, E_ARG_OFF = 4, E_STALE = 8, E_STATE = 16, E_CAP = 32, E_MCAP = 64 };
@@ -37,26 +36,10 @@ struct Ts {
     int32_t n;
 };
 
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b)
-{
-    if (a.m != b.m) return a.m < b.m ? -1 : 1;
-    const uint64_t a1 = a.l & IDENTITY_LSB, b1 = b.l & IDENTITY_LSB;
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (a.n != b.n) return a.n < b.n ? -1 : 1;
-    return 0;
-}
+__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
 __device__ __forceinline__ uint32_t kind(const Ts &t) { return (uint32_t)(t.l >> 1) & 7u; }
-// Kind.witnesses() (primitives/Txn.java:221-236)
-__device__ __forceinline__ uint32_t witnesses_mask(uint32_t k)
-{
-    switch (k) {
-    case 0: case 2: return 1u << 1;
-    case 1: case 3: return (1u << 0) | (1u << 1);
-    case 4: return (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4);
-    default: return 0;
-    }
-}
-__device__ __forceinline__ bool witnesses(const Ts &owner, const Ts &t) { return (witnesses_mask(kind(owner)) >> kind(t)) & 1u; }
+// owner.kind().witnesses(t.kind()) (ts.hpp)
+__device__ __forceinline__ bool witnesses(const Ts &owner, const Ts &t) { return (acc::witnesses(kind(owner)) >> kind(t)) & 1u; }
 __device__ __forceinline__ bool has_info(uint32_t s) { return s >= ACC && s <= APPLIED; }
 
 struct Info {
@@ -204,7 +187,7 @@ struct Ctx {
     // mergeAndFilterMissing (:988-1025) of additions[0, count) into x's missing[], written to dst
     __device__ __forceinline__ void put_merged(Buf &dst, const Info &x, SP<Ts> src_m, SP<Ts> add, uint32_t count)
     {
-        const uint32_t kinds = witnesses_mask(kind(x.id));
+        const uint32_t kinds = acc::witnesses(kind(x.id));
         uint32_t keep = 0;
         for (uint32_t i = 0; i < count; ++i) keep += (kinds >> kind(add[i])) & 1u;
         if (!keep) { put(dst, x, src_m, nullptr); return; }
@@ -1363,7 +1346,7 @@ __device__ __forceinline__ uint32_t ch_missing(uint32_t e, const uint32_t *__res
     const HG X = G[eg[e]];
     if (!has_info(X.st)) return 0;
     const Ts id = hg_id(X), bound = hg_bound(X);
-    const uint32_t wm = witnesses_mask(kind(id));
+    const uint32_t wm = acc::witnesses(kind(id));
     const uint32_t h = X.h;
     uint32_t n = 0;
     auto put = [&](const UR &t) {
@@ -1451,7 +1434,7 @@ __global__ __launch_bounds__(BLOCK) void k_ch_miss(uint32_t ne, const uint32_t *
             lng = ub - u0 >= CH_LONG;
             const UpdRec r = urec[X.info_q];
             da = r.da; db = r.db;
-            wm = witnesses_mask(kind(id));
+            wm = acc::witnesses(kind(id));
             if (EMIT) out = moff[e];
         } else if (has_info(X.st) && X.snap_x != NONE) {
             // a snapshot entry with a long missing[] and no new uncommitted TxnId below its bound (an old entry of a hot
@@ -1943,7 +1926,7 @@ void cfk_snap_to_batch(acc_ctx *ctx, const acc_cfk_snap *in, acc_cfk_batch_view 
         // sort of the compacted (msb, lsb & IDENTITY_LSB, node) bits: a few radix passes over the bits that vary
         launch(ctx, "cb_node", k_cb_node, g, dim3(BLOCK), 0, NE, s.en, k);
         const uint64_t *words[3] = { s.em, s.el, k };
-        const uint64_t wand[3] = { ~0ull, 0xFFFFFFFFFFFF001EULL, ~0ull };
+        const uint64_t wand[3] = { ~0ull, IDENTITY_LSB, ~0ull };
         DenseRank dr = dense_rank(ctx, "cb_dr", NE, 3, words, wand, nullptr, true);
         const uint32_t *perm = dr.perm;
         if (!perm) {   // every entry carries one TxnId: identity order

@@ -38,7 +38,6 @@ struct acc_maxconflicts {
 namespace acc {
 namespace mc {
 
-constexpr uint64_t IDENTITY_LSB = 0xFFFFFFFFFFFF001EULL;
 constexpr uint32_t MC_BLK = 256;
 constexpr uint64_t MAXC = ~0ull;
 enum : uint64_t { E_OFF = 1, E_SORT = 2, E_RANGE = 4 };
@@ -47,14 +46,7 @@ struct Ts {
     uint64_t m, l;
     int32_t n;
 };
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b)
-{
-    if (a.m != b.m) return a.m < b.m ? -1 : 1;
-    const uint64_t a1 = a.l & IDENTITY_LSB, b1 = b.l & IDENTITY_LSB;
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (a.n != b.n) return a.n < b.n ? -1 : 1;
-    return 0;
-}
+__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
 __device__ __forceinline__ Ts tmax(const Ts &a, const Ts &b) { return cmp(a, b) >= 0 ? a : b; }   // Timestamp.max
 
 struct Upd {

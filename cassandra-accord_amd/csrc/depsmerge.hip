@@ -382,7 +382,7 @@ void merge_half(acc_ctx *ctx, const char *ns, uint32_t mem, uint32_t ng, uint64_
     uint64_t *nodew = ctx->get<uint64_t>("dm_nodew", NV);
     launch(ctx, "dm_node_word", k_dm_node_word, dim3(grid_for(NV, BLOCK)), dim3(BLOCK), 0, (size_t)NV, node, nodew);
     const uint64_t *vw[3] = { msb, lsb, nodew };
-    const uint64_t vand[3] = { ~0ull, 0xFFFFFFFFFFFF001EULL, ~0ull };   // Timestamp.IDENTITY_LSB (Timestamp.java:41)
+    const uint64_t vand[3] = { ~0ull, IDENTITY_LSB, ~0ull };   // Timestamp.IDENTITY_LSB (Timestamp.java:41)
     DenseRank vd = dense_rank(ctx, "dm_vdict", NV, 3, vw, vand, nullptr, false);
     uint64_t *krank64 = ctx->get<uint64_t>("dm_krank64", NK);
     launch(ctx, "dm_widen", k_dm_widen, dim3(grid_for(NK, BLOCK)), dim3(BLOCK), 0, (size_t)NK, (const uint32_t *)kd.rank, krank64);

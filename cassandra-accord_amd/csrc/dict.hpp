@@ -1,8 +1,9 @@
-// dict.hpp — shared front end of the deps paths (keydeps.hip): input validation and the dense order-rank
+// dict.hpp — shared front end of the deps paths (dictionary.hip): input validation and the dense order-rank
 // dictionary of every TxnId and executeAt of a batch (Timestamp.compareTo, primitives/Timestamp.java:208-217).
 #pragma once
 
 #include "prims.hpp"
+#include "ts.hpp"
 #include <functional>
 
 namespace acc {
@@ -40,26 +41,17 @@ void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, con
 void redo_general_dictionary(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
                              const uint64_t *em, const uint64_t *el, const int32_t *en, uint64_t *g, Dictionary &d);
 
-// The CommandsForKey snapshot of a key batch (keydeps.hip stages 1-3) for the scans other than mapReduceActive: pairs
-// sorted by (key, TxnId rank) = one segment per key, entries in CommandsForKey.txns order. cfk = false when the batch has
-// no pairs. Device pointers owned by the context, valid until its next compute call.
-struct CfkSnapshot {
-    bool cfk = false;
-    uint32_t n = 0, nseg = 0;
-    size_t P = 0;
-    int rbits = 0;
-    const uint32_t *rank = nullptr;         // [2n] dictionary ranks (TxnIds, then executeAts)
-    const uint32_t *txn_of_rank = nullptr;  // TxnId rank -> batch index
-    const uint32_t *seg_start = nullptr;    // [nseg] first entry of each segment
-    const uint64_t *seg_key = nullptr;      // [nseg] key code of each segment, ascending
-    const uint32_t *s_rank = nullptr, *s_exec = nullptr;   // [P] TxnId / executeAt rank per entry
-    const uint8_t *s_info = nullptr;        // [P] status | kind << 3
-    const uint32_t *perm = nullptr;         // [P] entry -> input pair index
-    const uint64_t *tm = nullptr, *tl = nullptr, *em = nullptr, *el = nullptr;   // staged inputs
-    const int32_t *tn = nullptr, *en = nullptr;
-    const uint32_t *key_off = nullptr;
+// The validation error bits of the prep pass and the dictionary (g[4] / hg[4]); check_errors throws the first one set.
+enum : uint32_t {
+    ERR_BAD_STATUS = 1u << 0,
+    ERR_BAD_KIND = 1u << 1,
+    ERR_LOCAL_ONLY = 1u << 2,
+    ERR_KEYS_UNSORTED = 1u << 3,
+    ERR_DUP_TXNID = 1u << 4,
+    ERR_KEY_OFF = 1u << 5,
+    ERR_KEY_TOTAL = 1u << 6,   // key_off[n] != n_pairs
 };
-void cfk_snapshot(acc_ctx *ctx, const acc_batch_in *in, CfkSnapshot &out);
+void check_errors(uint64_t errs);
 
 // The dictionary of a batch computed by one half of PartialDeps, handed to the other (acc_partial_deps_batch): valid
 // when the KeyDeps half ran prep_dictionary (the batch has key pairs).

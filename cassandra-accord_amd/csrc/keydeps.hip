@@ -5,320 +5,40 @@
 //               (local/CommandsForKey.java:614-650) minus p1 (messages/PreAccept.java:253-259),
 // then the KeyDeps.Builder result (utils/RelationMultiMap.java:88-260) in Java layout.
 //
-// Pipeline (all on one HIP stream, three host syncs for sizes):
-//   1. prep        validate, OR-reduce varying bits of TxnId/executeAt/key words, sortedness.
-//   2. dictionary  compact the 148-bit Timestamp order key (Timestamp.compareTo :208-217) to its varying
-//                  bits, radix-sort the 2N timestamps, dense order ranks (equal <=> Timestamp.equals).
-//   3. CFK build   radix-sort (key, txnRank) pairs -> one segment per key = CommandsForKey.txns;
-//                  committed[] per segment sorted by (executeAt rank, txn order) (ctor :459-469);
-//                  lastWrite index, per-segment prefix-max of committed executeAt, uncommitted list.
-//   4. scan        count -> exclusive scan -> emit. Each (T,k) query finds maxCommittedBefore with the
-//                  reference's FAST bisection (SortedArrays.java:992-1027, replayed on ranks, so ties
-//                  resolve identically), then only touches [scanStart, insertPos) plus the
-//                  uncommitted entries before scanStart instead of the whole O(prefix).
-//   5. build       per-T union of the per-key lists, indices into it, Java keysToTxnIds layout.
-#include "dict.hpp"
+// This file holds the CFK build and the run-based path with its tiers. The stages, each a host function over one
+// record (CfkBuild, keydeps.hpp):
+//   build_cfk      argument checks; staged inputs; prep and the order-rank dictionary of the 2N timestamps
+//                  (dictionary.hip); the pairs sorted by (key, TxnId rank) by one of five sorts (sort_pairs); the
+//                  columns: one segment per key = CommandsForKey.txns, tile counts, the run-based scan's class lists,
+//                  rank directory and bumped committed list (build_columns).
+//   keydeps_runs   no executeAt ties: a query is a union of sorted runs over its segment (see "v2" below). Count pass
+//                  (a record per pair), mark pass and scans (result sizes, stream txns / big txns), then the stream
+//                  passes on the context stream while the big txns' tiers (window, sorting, wave) run on a side
+//                  stream, and the TxnId compaction; the sorting tiers and the global fallback follow only for txns
+//                  the first round passed on.
+//   keydeps_replay (keydeps_replay.hip) executeAt ties, where the reference's FAST bisection is order-dependent, or
+//                  ACC_OPT_FORCE_REPLAY: the exact replay of every (T, k) query.
+// keydeps_batch = build_cfk, then keydeps_of (replay or runs). keydeps_mixed (keydeps_mixed.hip) = the same with segment
+// keys and the sparse compaction, then its range part. cfk_snapshot = build_cfk alone.
+//
+// Host syncs of a tie-free batch, and what each one reads:
+//   1. prep (prep_dictionary): the varying-bit masks of the timestamp and key words, validation errors, sortedness,
+//      the number of executeAts that differ from their TxnId: they pick the dictionary and the pair sort.
+//   2. columns (build_columns): the tile totals (bumped committed count: the size of the next sort), the error and
+//      tie words of the dictionary kernels. A sorted-batch dictionary that met a tie is redone by the general sort
+//      here and the columns built again (one more sync).
+//   3. sizes (keydeps_runs): E, the number of big txns and of stream txns with a run record, the 9-16-key flag: they
+//      size the result arrays and pick the launches.
+//   4. compaction (finish): the result totals, gather-count checks, the tiers' counts. Again after the sorting tiers
+//      or the global fallback (which has one sync of its own), when the first round left txns to them.
+// The replay path has syncs 1 and 2, then one for E and one for the result totals.
+#include "keydeps.hpp"
 
 #include <vector>
 
 namespace acc {
 
-// Timestamp words: w0 = msb (unsigned), w1 = lsb & IDENTITY_LSB (lowHlc then identity flags, unsigned
-// compare is exact because lowHlc < 2^48), w2 = node ^ 0x80000000 (signed -> unsigned order).
-constexpr uint64_t IDENTITY_LSB = 0xFFFFFFFFFFFF001EULL;
-
-__device__ __forceinline__ uint64_t ts_w1(uint64_t lsb) { return lsb & IDENTITY_LSB; }
-__device__ __forceinline__ uint64_t ts_w2(int32_t node) { return (uint64_t)((uint32_t)node ^ 0x80000000u); }
-
-__device__ __forceinline__ int ts_cmp(uint64_t am, uint64_t al, int32_t an, uint64_t bm, uint64_t bl, int32_t bn)
-{
-    if (am != bm) return am < bm ? -1 : 1;
-    uint64_t a1 = ts_w1(al), b1 = ts_w1(bl);
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (an != bn) return an < bn ? -1 : 1;
-    return 0;
-}
-
-// Kind.witnesses() as a bitmask over Kind ordinals (primitives/Txn.java:221-236); 0 = throws.
-__device__ __forceinline__ uint32_t witnesses(uint32_t kind)
-{
-    switch (kind) {
-    case 0: case 2: return 1u << 1;                                   // Read, EphemeralRead -> Ws
-    case 1: case 3: return (1u << 0) | (1u << 1);                     // Write, SyncPoint -> RsOrWs
-    case 4:         return (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4);  // ESP -> AnyGloballyVisible
-    default:        return 0;
-    }
-}
-
-struct TsPlan {
-    Runs r0, r1, r2;
-    int b0, b1, b2;
-};
-
-enum : uint32_t {
-    ERR_BAD_STATUS = 1u << 0,
-    ERR_BAD_KIND = 1u << 1,
-    ERR_LOCAL_ONLY = 1u << 2,
-    ERR_KEYS_UNSORTED = 1u << 3,
-    ERR_DUP_TXNID = 1u << 4,
-    ERR_KEY_OFF = 1u << 5,
-    ERR_KEY_TOTAL = 1u << 6,   // key_off[n] != n_pairs
-};
-
-// g[0..2] ts word masks, g[3] key mask, g[4] error bits, g[5] batch-not-in-TxnId-order flag.
-// Block-level OR (wave shuffles, then LDS across waves) and ONE atomic per block and word: same-address
-// atomics from every wave serialise at the L2 (1.4 ms for 8M pairs in the first build).
-template <int NW>
-__device__ __forceinline__ void block_or_n(uint64_t (&v)[NW], uint64_t *dst)
-{
-    __shared__ uint64_t part[WAVES][NW];
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        uint64_t x = v[w];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) x |= shfl_idx(x, (int)(lane_id() ^ d));
-        if (lane_id() == 0) part[threadIdx.x >> 6][w] = x;
-    }
-    __syncthreads();
-    if (threadIdx.x < NW) {
-        uint64_t x = 0;
-#pragma unroll
-        for (int q = 0; q < WAVES; ++q) x |= part[q][threadIdx.x];
-        if (x) atomicOr((unsigned long long *)&dst[threadIdx.x], (unsigned long long)x);
-    }
-}
-
-// Per txn: executeAt != TxnId flags, varying-bit masks, status / kind checks, TxnId order; per pair (a chunk's txns'
-// pairs are one contiguous range, walked coalesced with each pair's txn found in the chunk's key offsets in LDS):
-// owner[], key order within a txn (Keys.ofSortedUnique), the key-code varying-bit mask. Pair indices are bounded by P
-// (a malformed key_off is reported, never followed out of bounds). One chunk of BLOCK txns per block (full occupancy:
-// a few resident blocks per CU left every chunk's HBM round trips exposed, 0.11 ms for config 2); each block folds its
-// words into one of PREP_SLOTS slot rows of g (same-address atomics serialise at the L2) and the host ORs the rows.
-constexpr uint32_t PREP_SLOTS = 64;   // 64 x 8 words = ctx->pinned's slot area
-
-__global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const uint64_t *__restrict__ tm, const uint64_t *__restrict__ tl,
-                                                    const int32_t *__restrict__ tn, const uint64_t *__restrict__ em,
-                                                    const uint64_t *__restrict__ el, const int32_t *__restrict__ en,
-                                                    const uint8_t *__restrict__ status, const uint32_t *__restrict__ key_off,
-                                                    const uint64_t *__restrict__ key_code, uint32_t *__restrict__ owner,
-                                                    uint32_t *__restrict__ bflag, uint64_t *__restrict__ g)
-{
-    __shared__ uint32_t ko[BLOCK + 1];
-    const uint32_t tid = threadIdx.x;
-    uint64_t m0 = 0, m1 = 0, m2 = 0, km = 0, errs = 0, unsorted = 0, ornk = 0;
-    uint32_t differs = 0;
-    const uint64_t r0 = tm[0], r1 = ts_w1(tl[0]), r2 = ts_w2(tn[0]);
-    const uint64_t kref = P ? key_code[0] : 0;
-    if (blockIdx.x == 0 && tid == 0 && key_off[n] != P) errs |= ERR_KEY_TOTAL;
-    for (uint32_t t0 = blockIdx.x * BLOCK; t0 < n; t0 += gridDim.x * BLOCK) {
-        const uint32_t t = t0 + tid;
-        const uint32_t tcnt = min((uint32_t)BLOCK, n - t0);
-        __syncthreads();   // the previous chunk's ko[] readers are done
-        if (tid < tcnt) ko[tid] = key_off[t];
-        if (tid == 0) ko[tcnt] = key_off[t0 + tcnt];
-        if (t < n) {
-            // executeAt != txnId (Timestamp.equals): these are the only executeAts the sorted-batch
-            // dictionary has to sort
-            const bool d = tm[t] != em[t] || ts_w1(tl[t]) != ts_w1(el[t]) || tn[t] != en[t];
-            differs += d;
-            bflag[t] = (uint32_t)d;
-            m0 |= (tm[t] ^ r0) | (em[t] ^ r0);
-            m1 |= (ts_w1(tl[t]) ^ r1) | (ts_w1(el[t]) ^ r1);
-            m2 |= (ts_w2(tn[t]) ^ r2) | (ts_w2(en[t]) ^ r2);
-            if (status[t] > 7) errs |= ERR_BAD_STATUS;
-            uint32_t kind = (uint32_t)(tl[t] >> 1) & 7u;
-            if (kind >= 6) errs |= ERR_BAD_KIND;
-            else if (kind == 5) errs |= ERR_LOCAL_ONLY;
-            if (t + 1 < n && ts_cmp(tm[t], tl[t], tn[t], tm[t + 1], tl[t + 1], tn[t + 1]) >= 0) unsorted = 1;
-        }
-        __syncthreads();
-        const bool bad = tid < tcnt && ko[tid + 1] < ko[tid];
-        if (bad) errs |= ERR_KEY_OFF;
-        else if (tid < tcnt) ornk |= ko[tid + 1] - ko[tid];   // bounds the keys per txn (pair packing)
-        if (!__syncthreads_or(bad ? 1 : 0) && P) {
-            const uint32_t a = (uint32_t)min((size_t)ko[0], P), b = (uint32_t)min((size_t)ko[tcnt], P);
-            for (uint32_t j = a + tid; j < b; j += BLOCK) {
-                uint32_t lo = 0, hi = tcnt;   // last txn i with ko[i] <= j (empty txns share their offset with the next)
-                while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (ko[m] <= j) lo = m; else hi = m; }
-                owner[j] = t0 + lo;
-                const uint64_t kc = key_code[j];
-                km |= kc ^ kref;
-                if (j > ko[lo] && key_code[j - 1] >= kc) errs |= ERR_KEYS_UNSORTED;
-            }
-        }
-    }
-    uint64_t *gs = g + 8 * (blockIdx.x % PREP_SLOTS);
-    uint64_t v[7] = { m0, m1, m2, km, errs, unsorted, ornk };
-    block_or_n<7>(v, gs);
-    __shared__ uint32_t s_nd;
-    if (tid == 0) s_nd = 0;
-    __syncthreads();
-    if (differs) atomicAdd(&s_nd, differs);
-    __syncthreads();
-    if (tid == 0 && s_nd) atomicAdd((unsigned long long *)&gs[7], (unsigned long long)s_nd);
-}
-
-// ---- sorted-batch dictionary: TxnIds are already in order; only the differing executeAts (B) are sorted.
-// rank(txnId_t) = t + |{b in B : b < txnId_t}|, rank(b_k) = k + |{txnIds < b_k}|; exact dense ranks when no
-// executeAt equals another timestamp (checked here; otherwise the general sort recomputes them).
-__global__ __launch_bounds__(BLOCK) void k_b_compact(uint32_t n, const uint32_t *__restrict__ bflag, const uint32_t *__restrict__ bidx,
-                                                     const uint64_t *__restrict__ em, const uint64_t *__restrict__ el,
-                                                     const int32_t *__restrict__ en, const uint64_t *__restrict__ tm,
-                                                     const uint64_t *__restrict__ tl, const int32_t *__restrict__ tn,
-                                                     TsPlan plan, uint64_t *__restrict__ bkey, uint32_t *__restrict__ bsrc,
-                                                     uint64_t *__restrict__ tkey)
-{
-    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= n) return;
-    uint64_t c0 = pext_runs(tm[t], plan.r0), c1 = pext_runs(ts_w1(tl[t]), plan.r1), c2 = pext_runs(ts_w2(tn[t]), plan.r2);
-    tkey[t] = (plan.b0 ? (c0 << (plan.b1 + plan.b2)) : 0) | (plan.b1 ? (c1 << plan.b2) : 0) | c2;
-    if (bflag[t]) {
-        c0 = pext_runs(em[t], plan.r0); c1 = pext_runs(ts_w1(el[t]), plan.r1); c2 = pext_runs(ts_w2(en[t]), plan.r2);
-        uint32_t b = bidx[t];
-        bkey[b] = (plan.b0 ? (c0 << (plan.b1 + plan.b2)) : 0) | (plan.b1 ? (c1 << plan.b2) : 0) | c2;
-        bsrc[b] = t;
-    }
-}
-
-__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v)
-{
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rank_txn_sorted(uint32_t n, uint32_t nb, const uint64_t *__restrict__ tkey,
-                                                           const uint64_t *__restrict__ sb, const uint32_t *__restrict__ bflag,
-                                                           uint32_t *__restrict__ rank, uint32_t *__restrict__ txn_of_rank,
-                                                           uint64_t *__restrict__ g)
-{
-    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    uint64_t tie = 0;
-    if (t < n) {
-        uint32_t lb = lower_bound_u64(sb, 0, nb, tkey[t]);
-        if (lb < nb && sb[lb] == tkey[t]) tie = 1;
-        uint32_t r = t + lb;
-        rank[t] = r;
-        txn_of_rank[r] = t;
-        if (!bflag[t]) rank[n + t] = r;
-    }
-    uint64_t v[1] = { tie };
-    block_or_n<1>(v, g + 6);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rank_b_sorted(uint32_t n, uint32_t nb, const uint64_t *__restrict__ tkey,
-                                                         const uint64_t *__restrict__ sb, const uint32_t *__restrict__ sperm,
-                                                         const uint32_t *__restrict__ bsrc, uint32_t *__restrict__ rank,
-                                                         uint64_t *__restrict__ g)
-{
-    uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
-    uint64_t tie = 0;
-    if (k < nb) {
-        if (k > 0 && sb[k] == sb[k - 1]) tie = 1;
-        uint32_t t = bsrc[sperm[k]];
-        rank[n + t] = k + lower_bound_u64(tkey, 0, n, sb[k]);
-    }
-    uint64_t v[1] = { tie };
-    block_or_n<1>(v, g + 6);
-}
-
-// ---------------------------------------------------------------- dictionary (order ranks)
-
-// i < N: TxnId of txn i; i >= N: executeAt of txn i-N. word_sel < 0: whole compacted key (fits 64 bits);
-// else the compaction of that single word.
-__global__ __launch_bounds__(BLOCK) void k_ts_compact(uint32_t n, const uint64_t *__restrict__ tm, const uint64_t *__restrict__ tl,
-                                                      const int32_t *__restrict__ tn, const uint64_t *__restrict__ em,
-                                                      const uint64_t *__restrict__ el, const int32_t *__restrict__ en,
-                                                      TsPlan plan, int word_sel, const uint32_t *__restrict__ perm,
-                                                      uint64_t *__restrict__ out)
-{
-    size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= 2 * (size_t)n) return;
-    size_t src = perm ? perm[i] : i;
-    uint32_t t = (uint32_t)(src < n ? src : src - n);
-    bool is_exec = src >= n;
-    uint64_t w0 = is_exec ? em[t] : tm[t];
-    uint64_t w1 = ts_w1(is_exec ? el[t] : tl[t]);
-    uint64_t w2 = ts_w2(is_exec ? en[t] : tn[t]);
-    uint64_t c0 = pext_runs(w0, plan.r0), c1 = pext_runs(w1, plan.r1), c2 = pext_runs(w2, plan.r2);
-    uint64_t k;
-    if (word_sel < 0) k = (plan.b0 ? (c0 << (plan.b1 + plan.b2)) : 0) | (plan.b1 ? (c1 << plan.b2) : 0) | c2;
-    else k = word_sel == 0 ? c0 : word_sel == 1 ? c1 : c2;
-    out[i] = k;
-}
-
-// flag[i] = sorted key i differs from key i-1 (all compacted words compared).
-__global__ __launch_bounds__(BLOCK) void k_rank_flags(size_t m, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ c0,
-                                                      const uint64_t *__restrict__ c1, const uint64_t *__restrict__ c2,
-                                                      const uint64_t *__restrict__ sorted_single, uint32_t *__restrict__ flag)
-{
-    size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= m) return;
-    uint32_t f = 1;
-    if (i > 0) {
-        if (sorted_single) f = sorted_single[i] != sorted_single[i - 1];
-        else {
-            uint32_t a = perm[i], b = perm[i - 1];
-            f = (c0[a] != c0[b]) || (c1[a] != c1[b]) || (c2[a] != c2[b]);
-        }
-    }
-    flag[i] = f;
-}
-
-// rank[src] = inclusive(flag) - 1 (equal Timestamps share a rank); txn_of_rank for TxnId entries.
-__global__ __launch_bounds__(BLOCK) void k_rank_scatter(size_t m, uint32_t n, const uint32_t *__restrict__ perm,
-                                                        const uint32_t *__restrict__ incl, uint32_t *__restrict__ rank,
-                                                        uint32_t *__restrict__ txn_of_rank)
-{
-    size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= m) return;
-    uint32_t src = perm[i];
-    uint32_t r = incl[i] - 1;
-    rank[src] = r;
-    if (src < n) txn_of_rank[r] = src;
-}
-
-// Count TxnId entries per rank to detect duplicate TxnIds (CommandsForKey txns are sorted unique).
-__global__ __launch_bounds__(BLOCK) void k_dup_txn(uint32_t n, const uint32_t *__restrict__ rank, uint32_t *__restrict__ seen,
-                                                   uint64_t *__restrict__ g)
-{
-    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    uint64_t err = 0;
-    if (t < n) {
-        if (atomicAdd(&seen[rank[t]], 1u) != 0) err = ERR_DUP_TXNID;
-    }
-    uint64_t v[1] = { err };
-    block_or_n<1>(v, g + 4);
-}
-
-// g[6] != 0: some executeAt compares equal to another txn's TxnId or executeAt. Only then can two
-// committed entries of one key tie on executeAt, where the FAST bisection's pick (CommandsForKey.java:619)
-// is order-dependent; such batches take the exact replay path (v1).
-__global__ __launch_bounds__(BLOCK) void k_exec_ties(uint32_t n, const uint32_t *__restrict__ rank, uint32_t *__restrict__ seen,
-                                                     uint64_t *__restrict__ g)
-{
-    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    uint64_t tie = 0;
-    if (t < n && rank[n + t] != rank[t]) {
-        if (atomicAdd(&seen[rank[n + t]], 1u) != 0) tie = 1;
-    }
-    uint64_t v[1] = { tie };
-    block_or_n<1>(v, g + 6);
-}
-
 // ---------------------------------------------------------------- CFK build
-
-struct PairPlan {
-    Runs rk;       // key code compaction
-    int rbits;     // txn-rank bits in the composite (0 when the batch is already in TxnId order)
-    int mode;      // 0: key only (sorted batch), 1: (key << rbits) | rank, 2: key only after a rank pre-sort,
-                   // 3: (key << 32) | pair index, keys-only sort (sorted batch, key within 32 bits);
-                   // 4: (key << 32) | owner << sb | slot (mode 3 with the pair's txn packed: the CFK columns gather the
-                   //    16-MB txn records directly instead of a 16-B per-pair copy)
-    int sb;        // mode 4: bits of the key slot within its txn
-};
 
 // the per-txn record k_txn_info writes, done by k_pair_keys' first n threads when tinfo is set (one launch fewer)
 struct TxnInfoArgs {
@@ -408,330 +128,6 @@ __global__ __launch_bounds__(BLOCK) void k_pair_pos(size_t P, const uint32_t *__
 {
     size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p < P) pair_pos[perm[p]] = (uint32_t)p;
-}
-
-// v1 only: committed / uncommitted flags and the segmented prefix-max input
-// multi_seg (non-null): committed[] lists only for segments of two or more entries (the mixed path answers
-// single-entry segments without them, k_mx_pcount)
-__global__ __launch_bounds__(BLOCK) void k_v1_flags(size_t P, const uint8_t *__restrict__ s_info, const uint32_t *__restrict__ s_exec,
-                                                    const uint32_t *__restrict__ seg_incl, const uint32_t *__restrict__ multi_seg,
-                                                    uint32_t *__restrict__ cflag, uint32_t *__restrict__ uflag,
-                                                    uint64_t *__restrict__ pmax_in)
-{
-    size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= P) return;
-    uint32_t st = s_info[p] & 7u;
-    bool c = st >= 4 && st <= 6;
-    if (multi_seg) {
-        const uint32_t sg = seg_incl[p] - 1;
-        cflag[p] = c && multi_seg[sg + 1] - multi_seg[sg] >= 2;
-    } else {
-        cflag[p] = c;
-    }
-    uflag[p] = st >= 1 && st <= 3;
-    // segmented prefix-max via a segment-id prefix: max over (seg << 32 | exec+1) never crosses segments
-    pmax_in[p] = ((uint64_t)(seg_incl[p] - 1) << 32) | (c ? (uint64_t)s_exec[p] + 1 : 0);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_low32(size_t P, const uint64_t *__restrict__ in, uint32_t *__restrict__ out)
-{
-    size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p < P) out[p] = (uint32_t)in[p];
-}
-__global__ __launch_bounds__(BLOCK) void k_low32x2(size_t P, const uint64_t *__restrict__ a, uint32_t *__restrict__ a32,
-                                                   const uint64_t *__restrict__ b, uint32_t *__restrict__ b32)
-{
-    size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p < P) { a32[p] = (uint32_t)a[p]; b32[p] = (uint32_t)b[p]; }
-}
-
-// Committed entries -> (seg << ebits | execRank) composite for the stable (seg, executeAt) sort; pads
-// (all ones in `bits`) fill [NC, P) so the sort runs on the host-known size P.
-__global__ __launch_bounds__(BLOCK) void k_committed_keys(size_t P, const uint32_t *__restrict__ cflag, const uint32_t *__restrict__ cum_c,
-                                                          const uint32_t *__restrict__ seg_incl, const uint32_t *__restrict__ s_exec,
-                                                          const uint32_t *__restrict__ uflag, const uint32_t *__restrict__ cum_u,
-                                                          int ebits, int bits, uint64_t *__restrict__ ckey,
-                                                          uint32_t *__restrict__ cpos, uint32_t *__restrict__ u_pos, int pads)
-{
-    size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (p >= P) return;
-    uint32_t nc = cum_c[P];
-    if (cflag[p]) {
-        uint32_t c = cum_c[p];
-        ckey[c] = ((uint64_t)(seg_incl[p] - 1) << ebits) | s_exec[p];
-        cpos[c] = (uint32_t)p;
-    }
-    if (pads && p >= nc) {
-        ckey[p] = bits >= 64 ? ~0ull : ((1ull << bits) - 1);
-        cpos[p] = 0xFFFFFFFFu;
-    }
-    if (uflag[p]) u_pos[cum_u[p]] = (uint32_t)p;
-}
-
-// cl_exec / lastWrite input / cl_start per segment.
-__global__ __launch_bounds__(BLOCK) void k_committed_cols(size_t P, const uint32_t *__restrict__ cpos_sorted,
-                                                          const uint32_t *__restrict__ s_exec, const uint8_t *__restrict__ s_info,
-                                                          const uint32_t *__restrict__ cum_c, uint32_t *__restrict__ cl_exec,
-                                                          uint32_t *__restrict__ lastw_in)
-{
-    size_t c = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (c >= P) return;
-    uint32_t nc = cum_c[P];
-    if (c >= nc) { lastw_in[c] = 0; return; }
-    uint32_t p = cpos_sorted[c];
-    cl_exec[c] = s_exec[p];
-    // committed[i].kind().isWrite(): kind of the TxnId (CommandsForKey.java:623)
-    lastw_in[c] = ((s_info[p] >> 3) == 1) ? (uint32_t)c + 1 : 0;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_seg_committed_start(size_t P, const uint32_t *__restrict__ seg_incl,
-                                                               const uint32_t *__restrict__ seg_start, const uint32_t *__restrict__ cum_c,
-                                                               uint32_t *__restrict__ cl_start)
-{
-    size_t s = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    uint32_t nseg = seg_incl[P - 1];
-    if (s > nseg) return;
-    cl_start[s] = s == nseg ? cum_c[P] : cum_c[seg_start[s]];
-}
-
-// ---------------------------------------------------------------- the conflict scan
-
-struct CfkView {
-    const uint32_t *seg_start, *s_rank, *s_exec, *seg_incl, *pair_pos, *owner, *rank;
-    const uint8_t *s_info;
-    const uint32_t *cl_start, *cl_exec, *lastw;   // lastw = inclusive max-scan of (isWrite ? c+1 : 0)
-    const uint32_t *pmax;                          // low 32 bits of the segmented prefix max (exec+1)
-    const uint32_t *cum_u, *u_pos;
-    const uint64_t *tl;
-    uint32_t n;
-    const uint32_t *vseg;   // non-null: query j is (owner[j], segment vseg[j]) (range-domain txns, no CFK member)
-};
-
-struct Query {
-    uint32_t s0, pos, scan_start, ub, ue, trank, wk;
-    bool p1, has_m;
-    uint32_t m;
-};
-
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ Query make_query_ts(const CfkView &v, uint32_t t, uint32_t seg);
-
-// first i in [lo, hi) with (uint32_t)a[i] >= v, the low words ascending over the range (one segment's prefix maxima)
-__device__ __forceinline__ uint32_t lower_bound_lo32(const uint64_t *a, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if ((uint32_t)a[m] < v) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ Query make_query(const CfkView &v, uint32_t j)
-{
-    return make_query_ts(v, v.owner[j], v.vseg ? v.vseg[j] : v.seg_incl[v.pair_pos[j]] - 1);
-}
-
-// the query of txn t against CFK segment seg
-__device__ __forceinline__ Query make_query_ts(const CfkView &v, uint32_t t, uint32_t seg)
-{
-    Query q;
-    uint32_t s0 = v.seg_start[seg], s1 = v.seg_start[seg + 1];
-    uint32_t S = v.rank[v.n + t];          // startedBefore = T.executeAt
-    q.trank = v.rank[t];
-    q.p1 = S != q.trank;                   // p1 = executeAt.equals(txnId) ? null : txnId
-    q.wk = witnesses((uint32_t)(v.tl[t] >> 1) & 7u);
-    q.s0 = s0;
-    // insertPos(0, startedBefore): first txn with TxnId >= S (CommandsForKey.java:1698-1703)
-    q.pos = lower_bound_u32(v.s_rank, s0, s1, S);
-    // maxCommittedBefore (CommandsForKey.java:618-625): FAST bisection of S over committed[] by executeAt
-    uint32_t c0 = v.cl_start[seg], c1 = v.cl_start[seg + 1];
-    uint32_t from = c0, to = c1;
-    long i = -1;
-    bool found = false;
-    while (from < to) {
-        uint32_t mid = (from + to) >> 1;
-        uint32_t e = v.cl_exec[mid];
-        if (S < e) to = mid;
-        else if (S > e) from = mid + 1;
-        else { i = (long)mid - 1; found = true; break; }
-    }
-    if (!found) i = (long)to - 1;
-    q.has_m = false;
-    q.m = 0;
-    if (i >= (long)c0) {
-        uint32_t w = v.lastw[i];           // greatest Write index <= i, +1 (0: none anywhere before)
-        if (w != 0 && w - 1 >= c0) { q.has_m = true; q.m = v.cl_exec[w - 1]; }
-    }
-    // Committed entries below scanStart all have executeAt < M (prefix max < M): pruned
-    q.scan_start = q.has_m ? lower_bound_u32(v.pmax, s0, q.pos, q.m + 1) : s0;
-    q.ub = v.cum_u[s0];
-    q.ue = v.cum_u[q.scan_start];
-    return q;
-}
-
-// EMIT: every entry to out[0..c); FIRST (count pass): only the first entry, to out[0]
-template <bool EMIT, bool FIRST = false>
-__device__ __forceinline__ uint32_t run_query(const CfkView &v, const Query &q, uint32_t *__restrict__ out)
-{
-    uint32_t c = 0;
-    // uncommitted (HISTORICAL / PREACCEPTED / ACCEPTED) entries below scanStart: always witnessed
-    for (uint32_t u = q.ub; u < q.ue; ++u) {
-        uint32_t p = v.u_pos[u];
-        uint32_t kind = v.s_info[p] >> 3;
-        if (!((q.wk >> kind) & 1u)) continue;
-        uint32_t r = v.s_rank[p];
-        if (q.p1 && r == q.trank) continue;
-        if (EMIT) out[c] = r;
-        else if (FIRST && c == 0) out[0] = r;
-        ++c;
-    }
-    // [scanStart, insertPos): the reference's per-entry switch (CommandsForKey.java:628-647)
-    for (uint32_t p = q.scan_start; p < q.pos; ++p) {
-        uint32_t info = v.s_info[p];
-        uint32_t st = info & 7u, kind = info >> 3;
-        if (!((q.wk >> kind) & 1u)) continue;
-        if (st == 0 || st == 7) continue;                                    // TRANSITIVELY_KNOWN, INVALID
-        if (st >= 4 && st <= 6 && q.has_m && v.s_exec[p] < q.m) continue;   // pruned committed
-        uint32_t r = v.s_rank[p];
-        if (q.p1 && r == q.trank) continue;
-        if (EMIT) out[c] = r;
-        else if (FIRST && c == 0) out[0] = r;
-        ++c;
-    }
-    return c;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_query_count(size_t P, CfkView v, uint64_t *__restrict__ cnt)
-{
-    size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (j >= P) return;
-    Query q = make_query(v, (uint32_t)j);
-    cnt[j] = run_query<false>(v, q, nullptr);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_query_emit(size_t P, CfkView v, const uint64_t *__restrict__ dep_off,
-                                                      uint32_t *__restrict__ deps, uint32_t *__restrict__ list_of)
-{
-    size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (j >= P) return;
-    Query q = make_query(v, (uint32_t)j);
-    uint64_t o = dep_off[j];
-    uint32_t c = run_query<true>(v, q, deps + o);
-    for (uint32_t k = 0; k < c; ++k) list_of[o + k] = (uint32_t)j;
-}
-
-// ---------------------------------------------------------------- KeyDeps assembly
-
-__device__ __forceinline__ bool contains_u32(const uint32_t *a, uint64_t lo, uint64_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) >> 1;
-        uint32_t x = a[mid];
-        if (x < v) lo = mid + 1;
-        else if (x > v) hi = mid;
-        else return true;
-    }
-    return false;
-}
-
-__device__ __forceinline__ uint64_t lower_bound_u32_64(const uint32_t *a, uint64_t lo, uint64_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// first[e] = dep is not in an earlier key's list of the same txn (the union keeps one copy).
-__global__ __launch_bounds__(BLOCK) void k_first(uint64_t E, const uint32_t *__restrict__ deps, const uint32_t *__restrict__ list_of,
-                                                 const uint32_t *__restrict__ owner, const uint32_t *__restrict__ key_off,
-                                                 const uint64_t *__restrict__ dep_off, uint32_t *__restrict__ first)
-{
-    uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (e >= E) return;
-    uint32_t j = list_of[e];
-    uint32_t t = owner[j];
-    uint32_t d = deps[e];
-    uint32_t f = 1;
-    for (uint32_t jj = key_off[t]; jj < j; ++jj)
-        if (contains_u32(deps, dep_off[jj], dep_off[jj + 1], d)) { f = 0; break; }
-    first[e] = f;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_nonempty(size_t P, const uint64_t *__restrict__ cnt, uint32_t *__restrict__ nz)
-{
-    size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (j < P) nz[j] = cnt[j] != 0;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_txn_sizes(uint32_t n, const uint32_t *__restrict__ key_off, const uint64_t *__restrict__ dep_off,
-                                                     const uint32_t *__restrict__ cnz, const uint32_t *__restrict__ cumf,
-                                                     uint64_t *__restrict__ kd_cnt, uint64_t *__restrict__ u_cnt,
-                                                     uint64_t *__restrict__ a_cnt)
-{
-    uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= n) return;
-    uint32_t j0 = key_off[t], j1 = key_off[t + 1];
-    uint64_t e0 = dep_off[j0], e1 = dep_off[j1];
-    uint64_t kd = cnz[j1] - cnz[j0];
-    kd_cnt[t] = kd;
-    u_cnt[t] = cumf[e1] - cumf[e0];
-    a_cnt[t] = kd + (e1 - e0);
-}
-
-// arena indices (KeyDeps.keysToTxnIds value part) and KeyDeps.txnIds (as batch indices)
-__global__ __launch_bounds__(BLOCK) void k_write_entries(uint64_t E, const uint32_t *__restrict__ deps, const uint32_t *__restrict__ list_of,
-                                                         const uint32_t *__restrict__ owner, const uint32_t *__restrict__ key_off,
-                                                         const uint64_t *__restrict__ dep_off, const uint32_t *__restrict__ cumf,
-                                                         const uint32_t *__restrict__ first, const uint32_t *__restrict__ cnz,
-                                                         const uint64_t *__restrict__ arena_off, const uint64_t *__restrict__ u_off,
-                                                         const uint32_t *__restrict__ txn_of_rank, int32_t *__restrict__ arena,
-                                                         uint32_t *__restrict__ dep_txn)
-{
-    uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (e >= E) return;
-    uint32_t j = list_of[e];
-    uint32_t t = owner[j];
-    uint32_t d = deps[e];
-    uint32_t j0 = key_off[t], j1 = key_off[t + 1];
-    // index of d in the sorted union = number of distinct deps of T smaller than d
-    uint32_t idx = 0;
-    for (uint32_t jj = j0; jj < j1; ++jj) {
-        uint64_t a = dep_off[jj], b = dep_off[jj + 1];
-        if (a == b) continue;
-        uint64_t lb = jj == j ? e : lower_bound_u32_64(deps, a, b, d);
-        idx += cumf[lb] - cumf[a];
-    }
-    uint32_t kd = cnz[j1] - cnz[j0];
-    uint64_t base = dep_off[j0];
-    arena[arena_off[t] + kd + (e - base)] = (int32_t)idx;
-    if (first[e]) dep_txn[u_off[t] + idx] = txn_of_rank[d];
-}
-
-// per non-empty (T,k): KeyDeps.keys entry and the end-offset header int (KeyDeps.java:150-172)
-__global__ __launch_bounds__(BLOCK) void k_write_keys(size_t P, const uint64_t *__restrict__ cnt, const uint32_t *__restrict__ owner,
-                                                      const uint32_t *__restrict__ key_off, const uint64_t *__restrict__ dep_off,
-                                                      const uint32_t *__restrict__ cnz, const uint64_t *__restrict__ kd_off,
-                                                      const uint64_t *__restrict__ arena_off, uint32_t *__restrict__ key_idx,
-                                                      int32_t *__restrict__ arena)
-{
-    size_t j = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (j >= P || cnt[j] == 0) return;
-    uint32_t t = owner[j];
-    uint32_t j0 = key_off[t], j1 = key_off[t + 1];
-    uint32_t slot = cnz[j] - cnz[j0];
-    uint32_t kd = cnz[j1] - cnz[j0];
-    key_idx[kd_off[t] + slot] = (uint32_t)j - j0;
-    arena[arena_off[t] + slot] = (int32_t)(kd + (dep_off[j + 1] - dep_off[j0]));
 }
 
 // ---------------------------------------------------------------- v2: run-based conflict scan
@@ -887,15 +283,6 @@ __global__ __launch_bounds__(BLOCK) void k_cfk_gather4(size_t P, uint32_t *__res
 // popcounts of the planes below p (the last set bit for the Write column): one line read and a few ALU ops.
 constexpr int RW_CBC = 6, RW_LUCW = 7;
 constexpr uint32_t RD_W = 32;
-
-struct V2Cols {
-    uint4 *rdir;          // [P / RD_W + 1] chunks of 16 u32, as 4 x uint4
-    uint32_t *list_rank;  // class lists (TxnId ranks), list l at bases[l]
-    uint32_t *bc_rank, *bc_exec;  // bumped committed, position order
-    uint8_t *bc_kind;
-    uint64_t *bc_pm_in;   // (seg << 32) | exec+1, for the segmented prefix max
-    uint64_t *bc_key;     // (seg << rbits) | exec, for the (seg, executeAt) sort
-};
 
 __global__ __launch_bounds__(BLOCK) void k_v2_apply(size_t P, const uint32_t *__restrict__ s_rank, const uint32_t *__restrict__ s_exec,
                                                     const uint8_t *__restrict__ s_info, const uint32_t *__restrict__ seg_flag,
@@ -1615,32 +1002,6 @@ __device__ uint32_t gather_to(uint64_t *buf, uint32_t cap, const RunsT<MAXK> &R,
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     return cursor;
-}
-
-__device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m)
-{
-    uint32_t lo = __shfl_xor((uint32_t)v, m, 64), hi = __shfl_xor((uint32_t)(v >> 32), m, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
-// in-LDS bitonic sort of n2 (power of two, >= 128) u64 entries by one wave
-__device__ __forceinline__ void wave_bitonic_lds(uint64_t *buf, uint32_t n2)
-{
-    const uint32_t lane = lane_id();
-    for (uint32_t k = 2; k <= n2; k <<= 1) {
-        for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
-            for (uint32_t i = lane; i < n2; i += 64) {
-                uint32_t l = i ^ jj;
-                if (l > i) {
-                    uint64_t a = buf[i], b = buf[l];
-                    bool up = (i & k) == 0;
-                    if ((a > b) == up) { buf[i] = b; buf[l] = a; }
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        }
-    }
 }
 
 // register bitonic across the 64 lanes (ascending by lane)
@@ -3065,331 +2426,140 @@ __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_
 
 // ---------------------------------------------------------------- host orchestration
 
-static void check_errors(uint64_t errs)
-{
-    if (errs & ERR_KEY_TOTAL) fail(ACC_E_ARG, "key_off[n_txn] must equal n_pairs");
-    if (errs & ERR_BAD_STATUS) fail(ACC_E_ARG, "invalid InternalStatus ordinal (> INVALID_OR_TRUNCATED)");
-    if (errs & ERR_BAD_KIND) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in TxnId flags");
-    if (errs & ERR_KEY_OFF) fail(ACC_E_ARG, "key_off must be non-decreasing");
-    if (errs & ERR_KEYS_UNSORTED) fail(ACC_E_ARG, "keys of a txn must be sorted and unique (Keys.ofSortedUnique)");
-    if (errs & ERR_DUP_TXNID) fail(ACC_E_ARG, "TxnIds of a batch must be distinct (CommandsForKey txns are sorted unique)");
-    if (errs & ERR_LOCAL_ONLY) fail(ACC_E_STATE, "Kind.witnesses(): unhandled kind LocalOnly (AssertionError)");
-}
-
-// Exact replay path (v1): committed[] per segment sorted by (executeAt, txn order) and the reference's
-// FAST bisection per query; per-(T,k) lists emitted in order, then the per-T union by binary search.
-// Used when executeAt ties exist (or ACC_OPT_FORCE_REPLAY).
-// CommandsForKey state of a built batch, kept for the range-domain queries of acc_keydeps_mixed
-struct KdState {
-    bool cfk = false;                 // a CFK exists (P > 0)
-    uint32_t n = 0;
-    size_t P = 0;
-    int rbits = 0;
-    const uint32_t *rank = nullptr, *txn_of_rank = nullptr, *key_off = nullptr, *owner = nullptr;
-    const uint32_t *seg_incl = nullptr, *seg_start = nullptr, *s_rank = nullptr, *s_exec = nullptr;
-    const uint32_t *pair_pos = nullptr, *perm = nullptr;
-    const uint8_t *s_info = nullptr;
-    const uint64_t *tl = nullptr, *key_code = nullptr;
-    const uint64_t *tm = nullptr, *em = nullptr, *el = nullptr;
-    const int32_t *tn = nullptr, *en = nullptr;
-    uint64_t *g = nullptr;
-    bool have_dict = false;
-    Dictionary dict;
-    bool sparse = false;              // the batch has many txns without keys (a mixed batch's range txns)
-    const uint64_t *seg_key = nullptr;   // per segment its key code (written by k_v2_apply)
-    bool v1 = false;                  // the exact-replay columns below are built
-    CfkView v1view{};
+// The sorted pairs of a batch: the permutation (entry -> input pair index) and what the column kernels have to know
+// about the sort that made it. The mode itself is in the record's PairPlan.
+struct PairSort {
+    Sorted ps{ nullptr, nullptr };     // vals: the permutation [P + V2_ITEMS] (mode 4: written by the CFK gather, which
+                                       // unpacks sp_m4); keys: the sorted composites (modes 0-2)
+    const uint64_t *sp_m4 = nullptr;   // mode 4: the sorted packed keys, unpacked by the CFK gather
+    int key_shift = 0;                 // modes 0-2: the composite's bits below the key
+    uint32_t *seg_flag = nullptr;      // [P] segment-start flags
+    bool flags_done = false;           // seg_flag is written (mode 3) or will be by the CFK gather (mode 4)
+    bool tinfo_done = false;           // modes 3, 4: the txn records were written by the pair-key launch
 };
 
-// Exact-replay CFK columns: uncommitted/committed flags and counts, segmented executeAt prefix max, committed[] per
-// segment sorted by executeAt (CommandsForKey.java:462-469) with the nearest-Write scan
-// multi_only: committed[] lists of the segments with two or more entries only, sorted at their exact size (one host
-// sync): the mixed path's single-entry segments never read them
-static CfkView build_v1_cfk(acc_ctx *ctx, uint32_t n, size_t P, int rbits, const uint64_t *tl, const uint32_t *owner,
-                            const uint32_t *rank, const uint32_t *seg_incl, const uint32_t *seg_start,
-                            const uint32_t *s_rank, const uint32_t *s_exec, const uint8_t *s_info, const uint32_t *pair_pos,
-                            bool multi_only = false)
+// Pairs sorted by (key, TxnId rank) by the cheapest of five sorts (PairPlan::mode, stat keydeps.pair_sort_mode):
+// a batch given in TxnId order needs no rank in the sort key, and a key code of few varying bits leaves room to pack
+// the pair index (or the pair's txn and slot) into a keys-only sort.
+static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb)
 {
+    const uint32_t n = cb.n;
+    const size_t P = cb.P;
+    const uint32_t *key_off = cb.key_off;
+    const uint64_t *key_code = cb.key_code;
+    const uint32_t *owner = cb.owner, *rank = cb.dict.rank;
+    const int rbits = cb.dict.rbits;
+    PairPlan &pp = cb.pp;
+    pp.rk = make_runs(cb.dict.hg[3]);
+    pp.rbits = rbits;
+    pp.sb = std::max(1, bits_for(cb.dict.hg[6]));   // bounds the key slot within a txn (hg[6] = OR of the key counts)
+    uint64_t *pkey = ctx->get<uint64_t>("pair_key", P);
     const unsigned gP = grid_for(P, BLOCK);
-    uint32_t *cflag = ctx->get<uint32_t>("cflag", P);
-    uint32_t *uflag = ctx->get<uint32_t>("uflag", P);
-    uint64_t *pmax_in = ctx->get<uint64_t>("pmax_in", P);
-    launch(ctx, "v1_flags", k_v1_flags, dim3(gP), dim3(BLOCK), 0, P, s_info, s_exec, seg_incl,
-           multi_only ? seg_start : (const uint32_t *)nullptr, cflag, uflag, pmax_in);
-    uint32_t *cum_c = ctx->get<uint32_t>("cum_c", P + 1);
-    uint32_t *cum_u = ctx->get<uint32_t>("cum_u", P + 1);
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, cflag, cum_c, P, true, cum_c + P);
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, uflag, cum_u, P, true, cum_u + P);
-    uint64_t *pmax64 = ctx->get<uint64_t>("pmax64", P);
-    scan<uint64_t, OpMax<uint64_t>>(ctx, pmax_in, pmax64, P, false);
-    uint32_t *pmax = ctx->get<uint32_t>("pmax", P);
-    launch(ctx, "low32", k_low32, dim3(gP), dim3(BLOCK), 0, P, (const uint64_t *)pmax64, pmax);
-
-    // committed[] per segment: stable sort of (segment, executeAt rank)
-    const int segbits = bits_for(P);
-    const int cbits = segbits + rbits;
-    if (cbits > 64) fail(ACC_E_ARG, "batch too large for the committed-list composite key");
-    uint64_t *ckey = ctx->get<uint64_t>("ckey", P);
-    uint32_t *cpos = ctx->get<uint32_t>("cpos", P);
-    uint32_t *u_pos = ctx->get<uint32_t>("u_pos", P);
-    launch(ctx, "committed_keys", k_committed_keys, dim3(gP), dim3(BLOCK), 0, P, (const uint32_t *)cflag,
-           (const uint32_t *)cum_c, (const uint32_t *)seg_incl, (const uint32_t *)s_exec, (const uint32_t *)uflag,
-           (const uint32_t *)cum_u, rbits, cbits, ckey, cpos, u_pos, multi_only ? 0 : 1);
-    size_t NC = P;
-    if (multi_only) {
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, cum_c + P, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-        ctx->sync();
-        NC = (size_t)(ctx->pinned[0] & 0xFFFFFFFFu);
-        ctx->stat("keydeps.v1_committed_sorted", NC);
-    }
-    Sorted cs = radix_sort(ctx, "rs_cl", ckey, cpos, NC, cbits);
-    uint32_t *cl_exec = ctx->get<uint32_t>("cl_exec", P);
-    uint32_t *lastw_in = ctx->get<uint32_t>("lastw_in", P);
-    uint32_t *lastw = ctx->get<uint32_t>("lastw", P);
-    launch(ctx, "committed_cols", k_committed_cols, dim3(gP), dim3(BLOCK), 0, P, (const uint32_t *)cs.vals,
-           (const uint32_t *)s_exec, (const uint8_t *)s_info, (const uint32_t *)cum_c, cl_exec, lastw_in);
-    scan<uint32_t, OpMax<uint32_t>>(ctx, lastw_in, lastw, P, false);
-    uint32_t *cl_start = ctx->get<uint32_t>("cl_start", P + 1);
-    launch(ctx, "seg_committed_start", k_seg_committed_start, dim3(grid_for(P + 1, BLOCK)), dim3(BLOCK), 0, P,
-           (const uint32_t *)seg_incl, (const uint32_t *)seg_start, (const uint32_t *)cum_c, cl_start);
-    CfkView v;
-    v.seg_start = seg_start; v.s_rank = s_rank; v.s_exec = s_exec; v.seg_incl = seg_incl; v.pair_pos = pair_pos;
-    v.owner = owner; v.rank = rank; v.s_info = s_info; v.cl_start = cl_start; v.cl_exec = cl_exec; v.lastw = lastw;
-    v.pmax = pmax; v.cum_u = cum_u; v.u_pos = u_pos; v.tl = tl; v.n = n; v.vseg = nullptr;
-    return v;
-}
-
-static void keydeps_v1_tail(acc_ctx *ctx, acc_keydeps_view *view, uint32_t n, size_t P, int rbits,
-                            const uint64_t *tl, const uint32_t *key_off, const uint32_t *owner,
-                            const uint32_t *rank, const uint32_t *txn_of_rank, uint64_t *g, const uint32_t *seg_incl,
-                            const uint32_t *seg_start, const uint32_t *s_rank, const uint32_t *s_exec, const uint8_t *s_info,
-                            const uint32_t *pair_pos, KdState *ks)
-{
-    hipStream_t st = ctx->stream;
-    const unsigned gP = grid_for(P, BLOCK);
-    // ---- 4. conflict scan: count, scan, emit
-    CfkView v = build_v1_cfk(ctx, n, P, rbits, tl, owner, rank, seg_incl, seg_start, s_rank, s_exec, s_info, pair_pos);
-    if (ks) { ks->v1 = true; ks->v1view = v; }
-    uint64_t *cnt = ctx->get<uint64_t>("cnt", P);
-    uint64_t *dep_off = ctx->get<uint64_t>("dep_off", P + 1);
-    launch(ctx, "query_count", k_query_count, dim3(gP), dim3(BLOCK), 0, P, v, cnt);
-    scan<uint64_t, OpAdd<uint64_t>>(ctx, cnt, dep_off, P, true, dep_off + P);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, dep_off + P, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, g + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t E = ctx->pinned[0];
-    check_errors(ctx->pinned[1]);
-    if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 dependency entries in one batch");
-
-    uint32_t *deps = ctx->get<uint32_t>("deps", E);
-    uint32_t *list_of = ctx->get<uint32_t>("list_of", E);
-    launch(ctx, "query_emit", k_query_emit, dim3(gP), dim3(BLOCK), 0, P, v, (const uint64_t *)dep_off, deps, list_of);
-
-    // ---- 5. KeyDeps assembly
-    const unsigned gE = grid_for(E, BLOCK);
-    uint32_t *first = ctx->get<uint32_t>("first", E);
-    uint32_t *cumf = ctx->get<uint32_t>("cumf", E + 1);
-    launch(ctx, "first", k_first, dim3(gE), dim3(BLOCK), 0, E, (const uint32_t *)deps, (const uint32_t *)list_of,
-           (const uint32_t *)owner, key_off, (const uint64_t *)dep_off, first);
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, first, cumf, E, true, cumf + E);
-    uint32_t *nz = ctx->get<uint32_t>("nz", P);
-    uint32_t *cnz = ctx->get<uint32_t>("cnz", P + 1);
-    launch(ctx, "nonempty", k_nonempty, dim3(gP), dim3(BLOCK), 0, P, (const uint64_t *)cnt, nz);
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, nz, cnz, P, true, cnz + P);
-    uint64_t *kd_cnt = ctx->get<uint64_t>("kd_cnt", n);
-    uint64_t *u_cnt = ctx->get<uint64_t>("u_cnt", n);
-    uint64_t *a_cnt = ctx->get<uint64_t>("a_cnt", n);
-    launch(ctx, "txn_sizes", k_txn_sizes, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, key_off, (const uint64_t *)dep_off,
-           (const uint32_t *)cnz, (const uint32_t *)cumf, kd_cnt, u_cnt, a_cnt);
-    uint64_t *kd_off = ctx->get<uint64_t>("kd_off", (size_t)n + 1);
-    uint64_t *u_off = ctx->get<uint64_t>("u_off", (size_t)n + 1);
-    uint64_t *arena_off = ctx->get<uint64_t>("arena_off", (size_t)n + 1);
-    scan<uint64_t, OpAdd<uint64_t>>(ctx, kd_cnt, kd_off, n, true, kd_off + n);
-    scan<uint64_t, OpAdd<uint64_t>>(ctx, u_cnt, u_off, n, true, u_off + n);
-    scan<uint64_t, OpAdd<uint64_t>>(ctx, a_cnt, arena_off, n, true, arena_off + n);
-    // upper bounds: ΣKd <= P, ΣU <= E, Σ(Kd+E) <= P + E
-    int32_t *arena = ctx->get<int32_t>("arena", P + E);
-    uint32_t *key_idx = ctx->get<uint32_t>("key_idx", P);
-    uint32_t *dep_txn = ctx->get<uint32_t>("dep_txn", E);
-    launch(ctx, "write_entries", k_write_entries, dim3(gE), dim3(BLOCK), 0, E, (const uint32_t *)deps,
-           (const uint32_t *)list_of, (const uint32_t *)owner, key_off, (const uint64_t *)dep_off, (const uint32_t *)cumf,
-           (const uint32_t *)first, (const uint32_t *)cnz, (const uint64_t *)arena_off, (const uint64_t *)u_off,
-           (const uint32_t *)txn_of_rank, arena, dep_txn);
-    launch(ctx, "write_keys", k_write_keys, dim3(gP), dim3(BLOCK), 0, P, (const uint64_t *)cnt, (const uint32_t *)owner,
-           key_off, (const uint64_t *)dep_off, (const uint32_t *)cnz, (const uint64_t *)kd_off,
-           (const uint64_t *)arena_off, key_idx, arena);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, arena_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, kd_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 2, u_off + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    *view = acc_keydeps_view{ n, ctx->pinned[0], ctx->pinned[1], ctx->pinned[2], E, arena_off, arena, kd_off,
-                              key_idx, u_off, dep_txn };
-    ctx->kd_view = *view;
-    ctx->kd_valid = true;
-}
-
-// The general dictionary: a compacted LSD radix sort of all 2N timestamps (multi-word beyond 64 varying bits), dense
-// ranks by a flag scan, duplicate-TxnId and executeAt-tie checks (g[4], g[6]).
-static void general_ranks(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
-                          const uint64_t *em, const uint64_t *el, const int32_t *en, const TsPlan &plan, uint64_t *g,
-                          uint32_t *rank, uint32_t *txn_of_rank)
-{
-    hipStream_t st = ctx->stream;
-    const size_t m = 2 * (size_t)n;
-    uint32_t *flag = ctx->get<uint32_t>("rank_flag", m);
-    uint32_t *incl = ctx->get<uint32_t>("rank_incl", m);
-    const unsigned gm = grid_for(m, BLOCK);
-    Sorted ts_sorted;
-    if (plan.b0 + plan.b1 + plan.b2 <= 64) {
-        uint64_t *ck = ctx->get<uint64_t>("ts_ckey", m);
-        launch(ctx, "ts_compact", k_ts_compact, dim3(gm), dim3(BLOCK), 0, n, tm, tl, tn, em, el, en, plan, -1,
-               (const uint32_t *)nullptr, ck);
-        ts_sorted = radix_sort(ctx, "rs_ts", ck, nullptr, m, plan.b0 + plan.b1 + plan.b2);
-        launch(ctx, "rank_flags", k_rank_flags, dim3(gm), dim3(BLOCK), 0, m, (const uint32_t *)ts_sorted.vals,
-               (const uint64_t *)nullptr, (const uint64_t *)nullptr, (const uint64_t *)nullptr,
-               (const uint64_t *)ts_sorted.keys, flag);
+    PairSort s;
+    s.seg_flag = ctx->get<uint32_t>("seg_flag", P);
+    if (cb.dict.batch_sorted && pp.rk.bits <= 32) {
+        // pair index order is already TxnId order within every key: a stable keys-only sort of (key << 32 | pair index),
+        // 8 B per element; the segment flags pass unpacks the permutation. Mode 4 packs (owner, slot) instead of the
+        // pair index and the CFK gather unpacks it (one random read of the owner's record per pair, which carries
+        // key_off[owner] for the pair index)
+        const bool m4 = bits_for((uint64_t)n - 1) + pp.sb <= 32;
+        pp.mode = m4 ? 4 : 3;
+        TxnInfoArgs ti;   // the txn records (k_txn_info) by the same launch: the ranks are final unless ties turn up
+        ti.n = n; ti.status = cb.status; ti.tl = cb.tl; ti.tinfo = cb.tinfo; ti.bigflag = cb.bigflag;
+        launch(ctx, "pair_keys", k_pair_keys, dim3(grid_for(std::max<size_t>(P, n), BLOCK)), dim3(BLOCK), 0, P, key_code,
+               owner, key_off, rank, (const uint32_t *)nullptr, pp, 0, pkey, ti);
+        s.tinfo_done = true;
+        const uint64_t *sp = radix_sort_keys(ctx, "rs_pair", pkey, P, 32, pp.rk.bits);
+        uint32_t *perm = ctx->get<uint32_t>("pair_perm", P + V2_ITEMS);
+        if (m4) s.sp_m4 = sp;
+        else launch(ctx, "seg_flags", k_seg_flags_packed, dim3(gP), dim3(BLOCK), 0, P, sp, s.seg_flag, perm, -1, key_off,
+                    (uint32_t *)nullptr);
+        s.ps = { nullptr, perm };
+        s.flags_done = true;
+    } else if (cb.dict.batch_sorted) {
+        pp.mode = 0;   // pair index order is already TxnId order within every key: stable sort by key
+        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, owner, key_off, rank,
+               (const uint32_t *)nullptr, pp, 0, pkey, TxnInfoArgs{});
+        s.ps = radix_sort(ctx, "rs_pair", pkey, nullptr, P, pp.rk.bits);
+    } else if (pp.rk.bits + rbits <= 64) {
+        pp.mode = 1;
+        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, owner, key_off, rank,
+               (const uint32_t *)nullptr, pp, 0, pkey, TxnInfoArgs{});
+        s.ps = radix_sort(ctx, "rs_pair", pkey, nullptr, P, pp.rk.bits + rbits);
+        s.key_shift = rbits;
     } else {
-        // multi-word LSD: node word, then lsb word, then msb word (each only over its varying bits)
-        uint64_t *c[3] = { ctx->get<uint64_t>("ts_c0", m), ctx->get<uint64_t>("ts_c1", m), ctx->get<uint64_t>("ts_c2", m) };
-        for (int w = 0; w < 3; ++w)
-            launch(ctx, "ts_compact", k_ts_compact, dim3(gm), dim3(BLOCK), 0, n, tm, tl, tn, em, el, en, plan, w,
-                   (const uint32_t *)nullptr, c[w]);
-        uint64_t *tmpk = ctx->get<uint64_t>("ts_tmpk", m);
-        uint32_t *permb = ctx->get<uint32_t>("ts_perm", m);
-        const uint32_t *perm = nullptr;
-        const int wbits[3] = { plan.b0, plan.b1, plan.b2 };
-        for (int w = 2; w >= 0; --w) {
-            const uint64_t *keys = c[w];
-            if (perm) {
-                launch(ctx, "ts_compact", k_ts_compact, dim3(gm), dim3(BLOCK), 0, n, tm, tl, tn, em, el, en, plan, w,
-                       perm, tmpk);
-                keys = tmpk;
-            }
-            Sorted s = radix_sort(ctx, "rs_ts", keys, perm, m, wbits[w]);
-            ACC_HIP(hipMemcpyAsync(permb, s.vals, m * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-            perm = permb;
-        }
-        ts_sorted = { nullptr, permb };
-        launch(ctx, "rank_flags", k_rank_flags, dim3(gm), dim3(BLOCK), 0, m, (const uint32_t *)permb,
-               (const uint64_t *)c[0], (const uint64_t *)c[1], (const uint64_t *)c[2], (const uint64_t *)nullptr, flag);
+        pp.mode = 2;
+        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, owner, key_off, rank,
+               (const uint32_t *)nullptr, pp, 1, pkey, TxnInfoArgs{});
+        Sorted byrank = radix_sort(ctx, "rs_pair_r", pkey, nullptr, P, rbits);
+        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, owner, key_off, rank,
+               (const uint32_t *)byrank.vals, pp, 0, pkey, TxnInfoArgs{});
+        s.ps = radix_sort(ctx, "rs_pair", pkey, byrank.vals, P, pp.rk.bits);
     }
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, flag, incl, m, false);
-    launch(ctx, "rank_scatter", k_rank_scatter, dim3(gm), dim3(BLOCK), 0, m, n, (const uint32_t *)ts_sorted.vals,
-           (const uint32_t *)incl, rank, txn_of_rank);
-    uint32_t *seen = ctx->get<uint32_t>("dup_seen", m);
-    ACC_HIP(hipMemsetAsync(seen, 0, m * sizeof(uint32_t), st));
-    launch(ctx, "dup_txn", k_dup_txn, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)rank, seen, g);
-    launch(ctx, "exec_ties", k_exec_ties, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)rank, seen, g);
+    return s;
 }
 
-static TsPlan ts_plan(const uint64_t *hg)
+// The rank-dependent columns of the CFK (txn records, the gather into (key, TxnId) order, tile counts, the run-based
+// scan's column set), then the build's host sync: ctx->pinned receives the tile totals, g[4..6] as staged by
+// k_v2_apply, and the bumped-query count. Run again when the deferred tie check finds the sorted-batch ranks invalid.
+static void build_columns(acc_ctx *ctx, CfkBuild &cb, const PairSort &s, bool tinfo_done)
 {
-    TsPlan plan;
-    plan.r0 = make_runs(hg[0]); plan.r1 = make_runs(hg[1]); plan.r2 = make_runs(hg[2]);
-    plan.b0 = plan.r0.bits; plan.b1 = plan.r1.bits; plan.b2 = plan.r2.bits;
-    return plan;
+    const uint32_t n = cb.n;
+    const size_t P = cb.P;
+    const uint32_t *rank = cb.dict.rank;
+    const PairPlan &pp = cb.pp;
+    const unsigned gP = grid_for(P, BLOCK);
+    const uint32_t nt = (uint32_t)((P + V2_TILE - 1) / V2_TILE);
+    uint4 *ptinfo = s.sp_m4 ? nullptr : ctx->get<uint4>("pair_tinfo", P);
+    uint32_t *tile_sums = ctx->get<uint32_t>("v2_tile_sums", (size_t)NCNT * nt);
+    uint32_t *tile_pref = ctx->get<uint32_t>("v2_tile_pref", (size_t)NCNT * nt);
+    uint32_t *totals = ctx->get<uint32_t>("v2_totals", 16);
+    uint64_t rk_mask = 0;   // the bits the key compaction keeps (k_v2_apply rebuilds segment key codes from them)
+    for (int r = 0; r < pp.rk.n; ++r) rk_mask |= (pp.rk.len[r] >= 64 ? ~0ull : ((1ull << pp.rk.len[r]) - 1)) << pp.rk.lo[r];
+    if (!tinfo_done)
+        launch(ctx, "txn_info", k_txn_info, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, rank, cb.status, cb.tl, cb.key_off,
+               cb.tinfo, cb.bigflag);
+    if (!s.sp_m4)
+        launch(ctx, "pair_tinfo", k_pair_tinfo, dim3(gP), dim3(BLOCK), 0, P, (const uint32_t *)cb.owner, (const uint4 *)cb.tinfo,
+               ptinfo);
+    launch(ctx, "cfk_gather", k_cfk_gather4, dim3(nt), dim3(BLOCK), 0, P, s.ps.vals, (const uint4 *)ptinfo, s.sp_m4, pp.sb,
+           (const uint4 *)cb.tinfo, s.seg_flag, cb.s_rank, cb.s_exec, cb.s_info,
+           cb.opts.seg_keys ? cb.pair_pos : (uint32_t *)nullptr, tile_sums, nt);
+    launch(ctx, "v2_tile_scans", k_v2_tile_scans, dim3(NCNT), dim3(BLOCK), 0, (const uint32_t *)tile_sums, tile_pref, nt, totals);
+    launch(ctx, "v2_apply", k_v2_apply, dim3(nt), dim3(BLOCK), 0, P, (const uint32_t *)cb.s_rank, (const uint32_t *)cb.s_exec,
+           (const uint8_t *)cb.s_info, (const uint32_t *)s.seg_flag, (const uint32_t *)tile_pref, (const uint32_t *)totals, nt,
+           cb.dict.rbits, cb.cols, cb.seg_incl, cb.seg_start, (const uint32_t *)s.ps.vals, cb.key_code, cb.seg_key, s.sp_m4,
+           pp.rk, rk_mask, cb.bases, cb.tot, 4u, cb.gstat, (uint32_t)GSTAT_N, (const uint64_t *)cb.g,
+           reinterpret_cast<uint64_t *>(totals) + 4);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, totals, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->sync();
 }
 
-// A batch whose sorted-batch dictionary met an executeAt tie (g[6], found after the caller's next sync when the check
-// was deferred): the general dictionary instead, in place (same rank buffers). g[6] is then the exact-tie flag.
-void redo_general_dictionary(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
-                             const uint64_t *em, const uint64_t *el, const int32_t *en, uint64_t *g, Dictionary &d)
+// pair_pos on demand, for the consumers that address pairs by index (exact replay, the global write tier) when the
+// build was not asked for it
+static void need_pair_pos(acc_ctx *ctx, CfkBuild &cb)
 {
-    ACC_HIP(hipMemsetAsync(g + 6, 0, sizeof(uint64_t), ctx->stream));
-    general_ranks(ctx, n, tm, tl, tn, em, el, en, ts_plan(d.hg), g, d.rank, d.txn_of_rank);
-    d.fast = false;
-    d.ties_pending = false;
-    ctx->stat("keydeps.fast_dictionary", 0);
+    if (cb.have_pair_pos) return;
+    launch(ctx, "pair_pos", k_pair_pos, dim3(grid_for(cb.P, BLOCK)), dim3(BLOCK), 0, cb.P, (const uint32_t *)cb.perm, cb.pair_pos);
+    cb.have_pair_pos = true;
 }
 
-// Validation (k_prep_txn: statuses, kinds, key order, TxnId order) and the order-rank dictionary of the 2N
-// timestamps (rank[t] = TxnId of t, rank[n + t] = executeAt of t; equal <=> Timestamp.equals). Shared by the
-// KeyDeps and RangeDeps paths. Throws the first validation error. defer_ties: the sorted-batch dictionary's tie check
-// (g[6]) is left to the caller's next sync (out.ties_pending), which then calls redo_general_dictionary on a tie.
-void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
-                     const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status,
-                     const uint32_t *key_off, const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out,
-                     bool defer_ties)
+// Stage 1: the CommandsForKey of a batch. Argument checks, staged inputs, prep and dictionary (dictionary.hip), the pair
+// sort, the columns, and the build's host sync, at which validation errors and executeAt ties are known.
+CfkBuild build_cfk(acc_ctx *ctx, const acc_batch_in *in, CfkOpts opts)
 {
-    hipStream_t st = ctx->stream;
-    // ---- 1. prep
-    static_assert(8 * PREP_SLOTS <= acc_ctx::PINNED_WORDS - acc_ctx::PINNED_SLOTS, "slot rows fit the pinned area");
-    static_assert(PREP_G_WORDS == 8 + 8 * PREP_SLOTS, "g and the prep slots share one buffer");
-    uint64_t *gslots = g + 8;   // g has PREP_G_WORDS words
-    ACC_HIP(hipMemsetAsync(g, 0, PREP_G_WORDS * sizeof(uint64_t), st));
-    uint32_t *bflag = ctx->get<uint32_t>("bflag", n);
-    launch(ctx, "prep_txn", k_prep_txn, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, P, tm, tl, tn, em, el, en, status,
-           key_off, key_code, owner, bflag, gslots);
-    // the last key_off entry must equal P
-    uint64_t hg[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    {
-        // (key_off[n] == P is checked by the kernel: ERR_KEY_TOTAL)
-        uint64_t *hs = ctx->pinned + acc_ctx::PINNED_SLOTS;
-        ACC_HIP(hipMemcpyAsync(hs, gslots, 8 * PREP_SLOTS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        for (uint32_t r = 0; r < PREP_SLOTS; ++r) {
-            for (int w = 0; w < 7; ++w) hg[w] |= hs[8 * r + w];
-            hg[7] += hs[8 * r + 7];
-        }
-    }
-    check_errors(hg[4]);
-    const bool batch_sorted = hg[5] == 0;
-
-    // ---- 2. dictionary: order ranks over 2N timestamps
-    const TsPlan plan = ts_plan(hg);
-    const size_t m = 2 * (size_t)n;
-    uint32_t *rank = ctx->get<uint32_t>("rank", m);
-    uint32_t *txn_of_rank = ctx->get<uint32_t>("txn_of_rank", m);
-    const uint64_t nb = hg[7];
-    bool fast_dict = batch_sorted && plan.b0 + plan.b1 + plan.b2 <= 64 && nb < n;
-    out.ties_pending = false;
-    if (fast_dict) {
-        uint32_t *bidx = ctx->get<uint32_t>("bidx", (size_t)n + 1);
-        scan<uint32_t, OpAdd<uint32_t>>(ctx, bflag, bidx, n, true, bidx + n);
-        uint64_t *bkey = ctx->get<uint64_t>("bkey", nb);
-        uint32_t *bsrc = ctx->get<uint32_t>("bsrc", nb);
-        uint64_t *tkey = ctx->get<uint64_t>("tkey", n);
-        launch(ctx, "b_compact", k_b_compact, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)bflag,
-               (const uint32_t *)bidx, em, el, en, tm, tl, tn, plan, bkey, bsrc, tkey);
-        Sorted sb = radix_sort(ctx, "rs_b", bkey, nullptr, nb, plan.b0 + plan.b1 + plan.b2);
-        launch(ctx, "rank_txn_sorted", k_rank_txn_sorted, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (uint32_t)nb,
-               (const uint64_t *)tkey, (const uint64_t *)sb.keys, (const uint32_t *)bflag, rank, txn_of_rank, g);
-        launch(ctx, "rank_b_sorted", k_rank_b_sorted, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, n, (uint32_t)nb,
-               (const uint64_t *)tkey, (const uint64_t *)sb.keys, (const uint32_t *)sb.vals, (const uint32_t *)bsrc, rank, g);
-        if (defer_ties) {
-            out.ties_pending = true;
-        } else {
-            ACC_HIP(hipMemcpyAsync(ctx->pinned, g + 6, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-            ctx->sync();
-            if (ctx->pinned[0]) {   // an executeAt equals another timestamp: dense ranks need the general dictionary
-                ACC_HIP(hipMemsetAsync(g + 6, 0, sizeof(uint64_t), st));
-                fast_dict = false;
-            }
-        }
-    }
-    if (!fast_dict) general_ranks(ctx, n, tm, tl, tn, em, el, en, plan, g, rank, txn_of_rank);
-    ctx->stat("keydeps.fast_dictionary", fast_dict ? 1 : 0);
-    out.rank = rank;
-    out.txn_of_rank = txn_of_rank;
-    out.rbits = bits_for(m - 1);
-    out.batch_sorted = batch_sorted;
-    out.fast = fast_dict;
-    memcpy(out.hg, hg, sizeof hg);
-}
-
-static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view *view, KdState *ks,
-                         bool cfk_only = false)
-{
-    if (!in || !view) fail(ACC_E_ARG, "null argument");
+    if (!in) fail(ACC_E_ARG, "null argument");
     if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    const uint32_t n = in->n_txn;
-    const size_t P = (size_t)in->n_pairs;
+    CfkBuild cb;
+    cb.opts = opts;
+    const uint32_t n = cb.n = in->n_txn;
+    const size_t P = cb.P = (size_t)in->n_pairs;
     if (P >= 0xFFFFFFFFull) fail(ACC_E_ARG, "n_pairs must be < 2^32");
     hipStream_t st = ctx->stream;
     ctx->kd_valid = false;
 
     // ---- stage inputs
-    const uint32_t *key_off = stage_in(ctx, "in_key_off", in->key_off, (size_t)n + 1, in->mem);
+    cb.key_off = stage_in(ctx, "in_key_off", in->key_off, (size_t)n + 1, in->mem);
     if (n == 0 || P == 0) {
         // no pairs: every txn has KeyDeps.NONE
         uint64_t *arena_off = ctx->get<uint64_t>("arena_off", (size_t)n + 1);
@@ -3398,178 +2568,142 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         ACC_HIP(hipMemsetAsync(arena_off, 0, ((size_t)n + 1) * 8, st));
         ACC_HIP(hipMemsetAsync(kd_off, 0, ((size_t)n + 1) * 8, st));
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)n + 1) * 8, st));
-        *view = acc_keydeps_view{ n, 0, 0, 0, 0, arena_off, ctx->get<int32_t>("arena", 1), kd_off,
-                                  ctx->get<uint32_t>("key_idx", 1), u_off, ctx->get<uint32_t>("dep_txn", 1) };
-        ctx->kd_view = *view;
+        ctx->kd_view = acc_keydeps_view{ n, 0, 0, 0, 0, arena_off, ctx->get<int32_t>("arena", 1), kd_off,
+                                         ctx->get<uint32_t>("key_idx", 1), u_off, ctx->get<uint32_t>("dep_txn", 1) };
         ctx->kd_valid = true;
         ctx->sync();
-        return;
+        return cb;
     }
-    const uint64_t *tm = stage_in(ctx, "in_tm", in->txn_id.msb, n, in->mem);
-    const uint64_t *tl = stage_in(ctx, "in_tl", in->txn_id.lsb, n, in->mem);
-    const int32_t *tn = stage_in(ctx, "in_tn", in->txn_id.node, n, in->mem);
-    const uint64_t *em = stage_in(ctx, "in_em", in->execute_at.msb, n, in->mem);
-    const uint64_t *el = stage_in(ctx, "in_el", in->execute_at.lsb, n, in->mem);
-    const int32_t *en = stage_in(ctx, "in_en", in->execute_at.node, n, in->mem);
-    const uint8_t *status = stage_in(ctx, "in_status", in->status, n, in->mem);
-    const uint64_t *key_code = stage_in(ctx, "in_key_code", in->key_code, P, in->mem);
+    cb.tm = stage_in(ctx, "in_tm", in->txn_id.msb, n, in->mem);
+    cb.tl = stage_in(ctx, "in_tl", in->txn_id.lsb, n, in->mem);
+    cb.tn = stage_in(ctx, "in_tn", in->txn_id.node, n, in->mem);
+    cb.em = stage_in(ctx, "in_em", in->execute_at.msb, n, in->mem);
+    cb.el = stage_in(ctx, "in_el", in->execute_at.lsb, n, in->mem);
+    cb.en = stage_in(ctx, "in_en", in->execute_at.node, n, in->mem);
+    cb.status = stage_in(ctx, "in_status", in->status, n, in->mem);
+    cb.key_code = stage_in(ctx, "in_key_code", in->key_code, P, in->mem);
 
-    // ---- 1-2. prep + dictionary
-    uint64_t *g = ctx->get<uint64_t>("g", PREP_G_WORDS);
-    uint32_t *owner = ctx->get<uint32_t>("owner", P);
-    Dictionary dict;
-    // the sorted-batch dictionary's tie check is read at the CFK sync below (one host sync fewer)
-    prep_dictionary(ctx, n, P, tm, tl, tn, em, el, en, status, key_off, key_code, owner, g, dict, true);
-    uint64_t hg[8];
-    memcpy(hg, dict.hg, sizeof hg);
-    const bool batch_sorted = dict.batch_sorted;
-    uint32_t *const rank = dict.rank, *const txn_of_rank = dict.txn_of_rank;
-    const int rbits = dict.rbits;
+    // ---- prep + dictionary
+    cb.g = ctx->get<uint64_t>("g", PREP_G_WORDS);
+    cb.owner = ctx->get<uint32_t>("owner", P);
+    // the sorted-batch dictionary's tie check is read at the columns' sync below (one host sync fewer)
+    prep_dictionary(ctx, n, P, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.status, cb.key_off, cb.key_code, cb.owner, cb.g,
+                    cb.dict, true);
 
-    // ---- 3. CFK build: pairs sorted by (key, TxnId rank)
-    uint4 *tinfo = ctx->get<uint4>("tinfo", n);
-    uint32_t *bigflag = ctx->get<uint32_t>("v3_bigflag", n);
-    bool tinfo_done = false;   // the txn records written by the pair-key launch
-    PairPlan pp;
-    pp.rk = make_runs(hg[3]);
-    pp.rbits = rbits;
-    uint64_t *pkey = ctx->get<uint64_t>("pair_key", P);
-    const unsigned gP = grid_for(P, BLOCK);
-    Sorted ps;
-    int key_shift = 0;
-    uint32_t *seg_flag = ctx->get<uint32_t>("seg_flag", P);
-    bool flags_done = false;
-    const uint64_t *sp_m4 = nullptr;   // mode 4: the sorted packed keys, unpacked by the CFK gather
-    pp.sb = std::max(1, bits_for(hg[6]));   // bounds the key slot within a txn (hg[6] = OR of the key counts)
-    if (batch_sorted && pp.rk.bits <= 32) {
-        // pair index order is already TxnId order within every key: a stable keys-only sort of (key << 32 | pair index),
-        // 8 B per element; the segment flags pass unpacks the permutation. Mode 4 packs (owner, slot) instead of the
-        // pair index and the CFK gather unpacks it (one random read of the owner's record per pair, which carries
-        // key_off[owner] for the pair index)
-        const bool m4 = bits_for((uint64_t)n - 1) + pp.sb <= 32;
-        pp.mode = m4 ? 4 : 3;
-        TxnInfoArgs ti;   // the txn records (k_txn_info) by the same launch: the ranks are final unless ties turn up
-        ti.n = n; ti.status = status; ti.tl = tl; ti.tinfo = tinfo; ti.bigflag = bigflag;
-        launch(ctx, "pair_keys", k_pair_keys, dim3(grid_for(std::max<size_t>(P, n), BLOCK)), dim3(BLOCK), 0, P, key_code,
-               (const uint32_t *)owner, key_off, (const uint32_t *)rank, (const uint32_t *)nullptr, pp, 0, pkey, ti);
-        tinfo_done = true;
-        const uint64_t *sp = radix_sort_keys(ctx, "rs_pair", pkey, P, 32, pp.rk.bits);
-        uint32_t *perm = ctx->get<uint32_t>("pair_perm", P + V2_ITEMS);
-        if (m4) sp_m4 = sp;
-        else launch(ctx, "seg_flags", k_seg_flags_packed, dim3(gP), dim3(BLOCK), 0, P, sp, seg_flag, perm, -1, key_off,
-                    (uint32_t *)nullptr);
-        ps = { nullptr, perm };
-        flags_done = true;
-    } else if (batch_sorted) {
-        pp.mode = 0;   // pair index order is already TxnId order within every key: stable sort by key
-        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, (const uint32_t *)owner, key_off,
-               (const uint32_t *)rank, (const uint32_t *)nullptr, pp, 0, pkey, TxnInfoArgs{});
-        ps = radix_sort(ctx, "rs_pair", pkey, nullptr, P, pp.rk.bits);
-    } else if (pp.rk.bits + rbits <= 64) {
-        pp.mode = 1;
-        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, (const uint32_t *)owner, key_off,
-               (const uint32_t *)rank, (const uint32_t *)nullptr, pp, 0, pkey, TxnInfoArgs{});
-        ps = radix_sort(ctx, "rs_pair", pkey, nullptr, P, pp.rk.bits + rbits);
-        key_shift = rbits;
-    } else {
-        pp.mode = 2;
-        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, (const uint32_t *)owner, key_off,
-               (const uint32_t *)rank, (const uint32_t *)nullptr, pp, 1, pkey, TxnInfoArgs{});
-        Sorted byrank = radix_sort(ctx, "rs_pair_r", pkey, nullptr, P, rbits);
-        launch(ctx, "pair_keys", k_pair_keys, dim3(gP), dim3(BLOCK), 0, P, key_code, (const uint32_t *)owner, key_off,
-               (const uint32_t *)rank, (const uint32_t *)byrank.vals, pp, 0, pkey, TxnInfoArgs{});
-        ps = radix_sort(ctx, "rs_pair", pkey, byrank.vals, P, pp.rk.bits);
-    }
-    uint32_t *seg_incl = ctx->get<uint32_t>("seg_incl", P + V2_ITEMS);   // written by k_v2_apply (the multi-scan's column 8)
-    if (!flags_done)
-        launch(ctx, "seg_flags", k_seg_flags, dim3(gP), dim3(BLOCK), 0, P, (const uint64_t *)ps.keys, key_shift, seg_flag);
+    // ---- pairs sorted by (key, TxnId rank)
+    cb.tinfo = ctx->get<uint4>("tinfo", n);
+    cb.bigflag = ctx->get<uint32_t>("v3_bigflag", n);
+    const PairSort ps = sort_pairs(ctx, cb);
+    cb.perm = ps.ps.vals;
+    if (!ps.flags_done)
+        launch(ctx, "seg_flags", k_seg_flags, dim3(grid_for(P, BLOCK)), dim3(BLOCK), 0, P, (const uint64_t *)ps.ps.keys,
+               ps.key_shift, ps.seg_flag);
 
-    uint32_t *seg_start = ctx->get<uint32_t>("seg_start", P + 1);
-    uint64_t *seg_key_buf = ks ? ctx->get<uint64_t>("seg_key", P + 1) : nullptr;   // per segment its key code
-    uint32_t *s_rank = ctx->get<uint32_t>("s_rank", P + V2_ITEMS);   // padded for the 16-B column loads
-    uint32_t *s_exec = ctx->get<uint32_t>("s_exec", P + V2_ITEMS);
-    uint8_t *s_info = ctx->get<uint8_t>("s_info", P + V2_ITEMS);
-    uint32_t *pair_pos = ctx->get<uint32_t>("pair_pos", P);
-    uint4 *ptinfo = sp_m4 ? nullptr : ctx->get<uint4>("pair_tinfo", P);
-    bool have_pair_pos = ks != nullptr;
-    uint64_t rk_mask = 0;   // the bits the key compaction keeps (k_v2_apply rebuilds segment key codes from them)
-    for (int r = 0; r < pp.rk.n; ++r) rk_mask |= (pp.rk.len[r] >= 64 ? ~0ull : ((1ull << pp.rk.len[r]) - 1)) << pp.rk.lo[r];
-    auto need_pair_pos = [&]() {
-        if (have_pair_pos) return;
-        launch(ctx, "pair_pos", k_pair_pos, dim3(gP), dim3(BLOCK), 0, P, (const uint32_t *)ps.vals, pair_pos);
-        have_pair_pos = true;
-    };
-    const int segbits = bits_for(P);
-    // ---- v2 structures (class lists, prefix counts, bumped committed list)
-    const uint32_t nt = (uint32_t)((P + V2_TILE - 1) / V2_TILE);
-    uint32_t *tile_sums = ctx->get<uint32_t>("v2_tile_sums", (size_t)NCNT * nt);
-    uint32_t *tile_pref = ctx->get<uint32_t>("v2_tile_pref", (size_t)NCNT * nt);
-    uint32_t *totals = ctx->get<uint32_t>("v2_totals", 16);
-    uint32_t *bases = ctx->get<uint32_t>("v2_bases", 16);
-    V2Cols cols;
-    cols.rdir = ctx->get<uint4>("v2_rdir", 4 * (P / RD_W + 1));
-    cols.list_rank = ctx->get<uint32_t>("v2_list_rank", P);
-    cols.bc_rank = ctx->get<uint32_t>("v2_bc_rank", P);
-    cols.bc_exec = ctx->get<uint32_t>("v2_bc_exec", P);
-    cols.bc_kind = ctx->get<uint8_t>("v2_bc_kind", P);
-    cols.bc_pm_in = ctx->get<uint64_t>("v2_bc_pm_in", P);
-    cols.bc_key = ctx->get<uint64_t>("v2_bc_key", P);
+    // ---- the columns: one segment per key = CommandsForKey.txns, and the run-based scan's structures (class lists,
+    // prefix counts, bumped committed list)
+    cb.seg_incl = ctx->get<uint32_t>("seg_incl", P + V2_ITEMS);   // written by k_v2_apply (the multi-scan's column 8)
+    cb.seg_start = ctx->get<uint32_t>("seg_start", P + 1);
+    cb.seg_key = opts.seg_keys ? ctx->get<uint64_t>("seg_key", P + 1) : nullptr;   // per segment its key code
+    cb.s_rank = ctx->get<uint32_t>("s_rank", P + V2_ITEMS);   // padded for the 16-B column loads
+    cb.s_exec = ctx->get<uint32_t>("s_exec", P + V2_ITEMS);
+    cb.s_info = ctx->get<uint8_t>("s_info", P + V2_ITEMS);
+    cb.pair_pos = ctx->get<uint32_t>("pair_pos", P);
+    cb.have_pair_pos = opts.seg_keys;   // written by the CFK gather when asked for
+    cb.bases = ctx->get<uint32_t>("v2_bases", 16);
+    cb.cols.rdir = ctx->get<uint4>("v2_rdir", 4 * (P / RD_W + 1));
+    cb.cols.list_rank = ctx->get<uint32_t>("v2_list_rank", P);
+    cb.cols.bc_rank = ctx->get<uint32_t>("v2_bc_rank", P);
+    cb.cols.bc_exec = ctx->get<uint32_t>("v2_bc_exec", P);
+    cb.cols.bc_kind = ctx->get<uint8_t>("v2_bc_kind", P);
+    cb.cols.bc_pm_in = ctx->get<uint64_t>("v2_bc_pm_in", P);
+    cb.cols.bc_key = ctx->get<uint64_t>("v2_bc_key", P);
     // the count / mark passes' accumulators, zeroed by the column kernels (txn records, k_v2_apply); bigflag above
-    uint64_t *tot = ctx->get<uint64_t>("v3_tot", 4);   // E, big txns, a 9-16-key big txn, stream txns with a run record
-    uint64_t *gstat = ctx->get<uint64_t>("v2_gstat", GSTAT_N + 6);   // + the batch totals and E / big counts (k_v3_ucompact)
-    // the rank-dependent columns (run again when the deferred tie check finds the sorted-batch ranks invalid)
-    auto build_columns = [&]() {
-        if (!tinfo_done)
-            launch(ctx, "txn_info", k_txn_info, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)rank, status,
-                   tl, key_off, tinfo, bigflag);
-        tinfo_done = false;   // a second build (the ties re-rank) writes them again
-        if (!sp_m4)
-            launch(ctx, "pair_tinfo", k_pair_tinfo, dim3(gP), dim3(BLOCK), 0, P, (const uint32_t *)owner, (const uint4 *)tinfo, ptinfo);
-        launch(ctx, "cfk_gather", k_cfk_gather4, dim3(nt), dim3(BLOCK), 0, P, ps.vals, (const uint4 *)ptinfo, sp_m4, pp.sb,
-               (const uint4 *)tinfo, seg_flag, s_rank, s_exec, s_info, ks ? pair_pos : (uint32_t *)nullptr, tile_sums, nt);
-        launch(ctx, "v2_tile_scans", k_v2_tile_scans, dim3(NCNT), dim3(BLOCK), 0, (const uint32_t *)tile_sums, tile_pref, nt, totals);
-        launch(ctx, "v2_apply", k_v2_apply, dim3(nt), dim3(BLOCK), 0, P, (const uint32_t *)s_rank, (const uint32_t *)s_exec,
-               (const uint8_t *)s_info, (const uint32_t *)seg_flag, (const uint32_t *)tile_pref, (const uint32_t *)totals, nt,
-               rbits, cols, seg_incl, seg_start, (const uint32_t *)ps.vals, key_code, seg_key_buf, sp_m4, pp.rk, rk_mask,
-               bases, tot, 4u, gstat, (uint32_t)GSTAT_N, (const uint64_t *)g, reinterpret_cast<uint64_t *>(totals) + 4);
-    };
-    build_columns();
-    // totals, g[4..6] staged by k_v2_apply, the bumped-query count
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, totals, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    if (dict.ties_pending && ctx->pinned[6]) {
+    cb.tot = ctx->get<uint64_t>("v3_tot", 4);   // E, big txns, a 9-16-key big txn, stream txns with a run record
+    cb.gstat = ctx->get<uint64_t>("v2_gstat", GSTAT_N + 6);   // + the batch totals and E / big counts (k_v3_ucompact)
+    build_columns(ctx, cb, ps, ps.tinfo_done);
+    if (cb.dict.ties_pending && ctx->pinned[6]) {
         // an executeAt equals another timestamp: the sorted-batch ranks are not dense ranks; the general dictionary,
         // then the rank-dependent columns again (the pair order does not depend on ranks in a sorted batch)
         check_errors(ctx->pinned[4]);
-        redo_general_dictionary(ctx, n, tm, tl, tn, em, el, en, g, dict);
-        build_columns();
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, totals, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        ctx->sync();
+        redo_general_dictionary(ctx, n, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.g, cb.dict);
+        build_columns(ctx, cb, ps, false);
     }
-    dict.ties_pending = false;
-    if (ks) { ks->have_dict = true; ks->dict = dict; ks->owner = owner; }
-    uint32_t htot[16];
-    memcpy(htot, ctx->pinned, sizeof htot);
+    cb.dict.ties_pending = false;
+    memcpy(cb.htot, ctx->pinned, sizeof cb.htot);
     check_errors(ctx->pinned[4]);
-    const bool ties = ctx->pinned[6] != 0;
-    ctx->stat("keydeps.path_replay", ties || (ctx->flags & ACC_OPT_FORCE_REPLAY) ? 1 : 0);
-    ctx->stat("keydeps.exec_ties", ties ? 1 : 0);
-    ctx->stat("keydeps.batch_sorted", batch_sorted ? 1 : 0);
-    if (ks) {
-        ks->cfk = true; ks->n = n; ks->P = P; ks->rbits = rbits; ks->rank = rank; ks->txn_of_rank = txn_of_rank;
-        ks->key_off = key_off; ks->owner = owner; ks->seg_incl = seg_incl; ks->seg_start = seg_start;
-        ks->s_rank = s_rank; ks->s_exec = s_exec; ks->pair_pos = pair_pos; ks->perm = ps.vals; ks->s_info = s_info;
-        ks->tl = tl; ks->key_code = key_code; ks->g = g; ks->seg_key = seg_key_buf;
-        ks->tm = tm; ks->tn = tn; ks->em = em; ks->el = el; ks->en = en;
-    }
-    if (cfk_only) return;
-    if (ties || (ctx->flags & ACC_OPT_FORCE_REPLAY)) {
-        need_pair_pos();
-        keydeps_v1_tail(ctx, view, n, P, rbits, tl, key_off, owner, rank, txn_of_rank, g, seg_incl, seg_start,
-                        s_rank, s_exec, s_info, pair_pos, ks);
-        return;
-    }
-    const uint32_t nbc = htot[6];
+    cb.ties = ctx->pinned[6] != 0;
+    ctx->stat("keydeps.path_replay", cb.ties || (ctx->flags & ACC_OPT_FORCE_REPLAY) ? 1 : 0);
+    ctx->stat("keydeps.exec_ties", cb.ties ? 1 : 0);
+    ctx->stat("keydeps.batch_sorted", cb.dict.batch_sorted ? 1 : 0);
+    ctx->stat("keydeps.pair_sort_mode", (uint64_t)cb.pp.mode);
+    cb.cfk = true;
+    return cb;
+}
+
+// The run-based path's global fallback, for the nfb txns (efb raw entries) the tiers listed in wo.fb_list. The caller
+// runs the TxnId compaction again afterwards.
+static void global_fallback(acc_ctx *ctx, CfkBuild &cb, const V2View &vv, const V2Out &wo, uint64_t nfb, uint64_t efb)
+{
+    hipStream_t st = ctx->stream;
+    const int rbits = cb.dict.rbits;
+    const uint32_t *key_off = cb.key_off, *txn_of_rank = cb.dict.txn_of_rank, *fb_list = wo.fb_list, *vcnz = wo.cnz;
+    const uint64_t *vdep_off = wo.dep_off, *arena_off = wo.arena_off;
+    uint32_t *const dep_scr = wo.dep_scratch;
+    uint64_t *const u_cnt = wo.u_cnt;
+    int32_t *const arena = wo.arena;
+    need_pair_pos(ctx, cb);
+    uint64_t *vcnt = ctx->get<uint64_t>("cnt", cb.P);
+    // txns beyond the block tiers (> 64 keys, > HUGE_E raw entries, or ranks beyond 25 bits): gather to global
+    // memory, sort by (txn, value, key) for the TxnId array and by (txn, key, value) for the arena order
+    uint64_t *fb_e = ctx->get<uint64_t>("v2_fb_e", nfb);
+    uint64_t *fb_off = ctx->get<uint64_t>("v2_fb_off", nfb + 1);
+    uint64_t *fb_maxk = ctx->get<uint64_t>("v2_fb_maxk", 1);
+    ACC_HIP(hipMemsetAsync(fb_maxk, 0, sizeof(uint64_t), st));
+    launch(ctx, "v2_fb_sizes", k_fb_sizes, dim3(grid_for(nfb, BLOCK)), dim3(BLOCK), 0, (uint32_t)nfb,
+           (const uint32_t *)fb_list, key_off, (const uint64_t *)vdep_off, fb_e, fb_maxk);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, fb_e, fb_off, nfb, true, fb_off + nfb);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, fb_maxk, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    const int bbits = bits_for(nfb - 1);
+    const int kbits = std::max(1, bits_for(ctx->pinned[0] - 1));   // key index within its txn
+    if (bbits + rbits + kbits > 64) fail(ACC_E_CAP, "too many oversized txns for the global KeyDeps path");
+    uint64_t *gkey = ctx->get<uint64_t>("v2_gkey", efb);
+    launch(ctx, "v2_big_gather", k_v2_big_gather, dim3((unsigned)((nfb + WAVES - 1) / WAVES)), dim3(BLOCK), 0,
+           (uint32_t)nfb, (const uint32_t *)fb_list, (const uint64_t *)fb_off, vv, (const uint64_t *)vcnt, key_off,
+           rbits, kbits, gkey);
+    Sorted s1 = radix_sort(ctx, "rs_big1", gkey, nullptr, efb, bbits + rbits + kbits);
+    uint32_t *nflag = ctx->get<uint32_t>("v2_big_nflag", efb);
+    uint32_t *nincl = ctx->get<uint32_t>("v2_big_nincl", efb);
+    launch(ctx, "v2_big_newflag", k_v2_big_newflag, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb,
+           (const uint64_t *)s1.keys, kbits, nflag);
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, nflag, nincl, efb, false);
+    uint32_t *idx1 = ctx->get<uint32_t>("v2_big_idx1", efb);
+    uint64_t *key2 = ctx->get<uint64_t>("v2_big_key2", efb);
+    launch(ctx, "v2_big_rank", k_v2_big_rank, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb, (const uint64_t *)s1.keys,
+           (const uint32_t *)nincl, (const uint32_t *)fb_list, (const uint64_t *)fb_off, rbits, kbits, key_off,
+           (const uint64_t *)vdep_off, (const uint32_t *)txn_of_rank, dep_scr, u_cnt, idx1, key2);
+    Sorted s2 = radix_sort(ctx, "rs_big2", key2, nullptr, efb, bbits + kbits + rbits);
+    launch(ctx, "v2_big_arena", k_v2_big_arena, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb,
+           (const uint32_t *)s2.vals, (const uint64_t *)s2.keys, (const uint32_t *)idx1, (const uint32_t *)fb_list,
+           (const uint64_t *)fb_off, rbits, kbits, key_off, (const uint32_t *)vcnz, (const uint64_t *)arena_off, arena);
+}
+
+// Stage 2 of a batch without executeAt ties: the run-based path. The bumped committed entries sorted by (segment,
+// executeAt); the count pass (one record per pair, E); the mark pass and the scans that size the result and split the
+// txns into stream txns and big txns; the big txns' tiers on a side stream while the stream passes run; the TxnId
+// compaction (finish), with the sorting tiers and the global fallback behind it for what the first round passed on.
+static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t n = cb.n;
+    const size_t P = cb.P;
+    const unsigned gP = grid_for(P, BLOCK);
+    const int rbits = cb.dict.rbits, segbits = bits_for(P);
+    const uint32_t *key_off = cb.key_off, *owner = cb.owner, *txn_of_rank = cb.dict.txn_of_rank;
+    const V2Cols &cols = cb.cols;
+    uint32_t *const bigflag = cb.bigflag;
+    uint64_t *const tot = cb.tot, *const gstat = cb.gstat;
+    const uint32_t nbc = cb.htot[6];
     if (segbits + rbits > 64) fail(ACC_E_ARG, "batch too large for the (segment, executeAt) composite key");
     Sorted bcs = radix_sort(ctx, "rs_bc", cols.bc_key, nullptr, nbc, segbits + rbits);
     uint32_t *bcs_exec = ctx->get<uint32_t>("v2_bcs_exec", nbc);
@@ -3585,9 +2719,9 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
     }
 
     V2View vv{};
-    vv.perm = ps.vals; vv.pair_pos = pair_pos; vv.seg_incl = seg_incl; vv.seg_start = seg_start;
-    vv.s_rank = s_rank; vv.s_exec = s_exec; vv.s_info = s_info; vv.rdir = cols.rdir; vv.tinfo = tinfo;
-    vv.list_rank = cols.list_rank; vv.bases = bases; vv.bc_rank = cols.bc_rank; vv.bc_exec = cols.bc_exec; vv.bc_pm = bc_pm64;
+    vv.perm = cb.perm; vv.pair_pos = cb.pair_pos; vv.seg_incl = cb.seg_incl; vv.seg_start = cb.seg_start;
+    vv.s_rank = cb.s_rank; vv.s_exec = cb.s_exec; vv.s_info = cb.s_info; vv.rdir = cols.rdir; vv.tinfo = cb.tinfo;
+    vv.list_rank = cols.list_rank; vv.bases = cb.bases; vv.bc_rank = cols.bc_rank; vv.bc_exec = cols.bc_exec; vv.bc_pm = bc_pm64;
     vv.bc_kind = cols.bc_kind; vv.bcs_exec = bcs_exec; vv.bcs_lastw = bcs_lw64;
     // ---- count pass: per-pair records, big-txn flags, E
     if (P >= 0x80000000ull) fail(ACC_E_CAP, "n_pairs must be < 2^31 (count-pass record format)");
@@ -3603,16 +2737,12 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
     uint32_t *psz = ctx->get<uint32_t>("v3_psz", P);   // the big txns' per-pair entry counts (mark pass -> bigfill)
 #ifdef ACC_PHASE_PROF
     const size_t ct_rows = (size_t)gP * WAVES;
-    unsigned long long *ct_buf = ctx->get<unsigned long long>("v2_ct_prof", 8 * ct_rows);
-    ACC_HIP(hipMemsetAsync(ct_buf, 0, 8 * ct_rows * sizeof(unsigned long long), st));
-    ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ct_prof), &ct_buf, sizeof ct_buf, 0, hipMemcpyHostToDevice, st));
+    unsigned long long *ct_buf = prof_arm(ctx, "v2_ct_prof", HIP_SYMBOL(g_ct_prof), 8 * ct_rows, st);
 #endif
     launch(ctx, "v2_count", k_v2_count, dim3(gP), dim3(BLOCK), 0, P, vv, (const uint32_t *)owner, ro, bigflag, blk_e);
 #ifdef ACC_PHASE_PROF
     {
-        std::vector<unsigned long long> h(8 * ct_rows);
-        ACC_HIP(hipMemcpyAsync(h.data(), ct_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-        ACC_HIP(hipStreamSynchronize(st));
+        const std::vector<unsigned long long> h = prof_read(ct_buf, 8 * ct_rows, st);
         double sum[8] = {}, mx[3] = {};
         size_t w = 0;
         for (size_t r = 0; r < ct_rows; ++r) {
@@ -3671,6 +2801,9 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
     ctx->stat("keydeps.huge_txns", 0);
     V2Out wo{};
     bool win_ok = false;
+#ifdef ACC_PHASE_PROF
+    unsigned long long *win_buf = nullptr;
+#endif
     uint64_t *vcnt = nullptr;
     uint32_t *med_list = nullptr, *big_list = nullptr, *fb_list = nullptr;
     // the sorting tiers: medium (<= MED_CAP raw entries), block (<= BIG_E), huge (<= HUGE_E, fed by the block tier)
@@ -3693,7 +2826,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         scan<uint64_t, OpAdd<uint64_t>>(ctx, u_cnt, u_off, n, true, u_off + n);
         const uint32_t *tmap = nullptr, *ne_cnt = nullptr;
         const uint64_t *uo = u_off;
-        if (ks && ks->sparse) {
+        if (cb.opts.sparse) {
             uint32_t *flag = ctx->get<uint32_t>("v3_ne_flag", n), *pos = ctx->get<uint32_t>("v3_ne_pos", n);
             uint32_t *cnt = ctx->get<uint32_t>("v3_ne_cnt", 1), *ne_t = ctx->get<uint32_t>("v3_ne_t", n);
             uint64_t *ne_uoff = ctx->get<uint64_t>("v3_ne_uoff", (size_t)n + 1);
@@ -3739,11 +2872,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         ctx->launch_stream = ctx->aux[0];
         if (win_ok) {
 #ifdef ACC_PHASE_PROF
-            {
-                unsigned long long *wpb = ctx->get<unsigned long long>("v2_win_prof", 10);
-                ACC_HIP(hipMemsetAsync(wpb, 0, 80, ctx->aux[0]));
-                ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_win_prof), &wpb, sizeof wpb, 0, hipMemcpyHostToDevice, ctx->aux[0]));
-            }
+            win_buf = prof_arm(ctx, "v2_win_prof", HIP_SYMBOL(g_win_prof), 10, ctx->aux[0]);
 #endif
             // the window tier takes every big txn of <= 16 keys; the sorting tiers run after the next host sync, only
             // when it passed txns on or some txn has more keys (no launch without work)
@@ -3779,9 +2908,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         sp.dep_scr = dep_st; sp.n = n; sp.ntiles = ntiles;
 #ifdef ACC_PHASE_PROF
         const size_t prof_rows = (size_t)ntiles;
-        unsigned long long *prof_buf = ctx->get<unsigned long long>("v3_prof", 8 * prof_rows);
-        ACC_HIP(hipMemsetAsync(prof_buf, 0, 8 * prof_rows * sizeof(unsigned long long), st));
-        ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_st_prof), &prof_buf, sizeof prof_buf, 0, hipMemcpyHostToDevice, st));
+        unsigned long long *prof_buf = prof_arm(ctx, "v3_prof", HIP_SYMBOL(g_st_prof), 8 * prof_rows, st);
 #endif
         if (nrun) {
             // the stream txns with a run record on side stream 1, concurrently with the lean pass below (their gathers
@@ -3800,9 +2927,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         else launch(ctx, "v3_stream", k_v3_stream<uint64_t, st_nt, ST_G, ST_N2, false, false>, dim3(nblocks), dim3(st_nt), 0, sp);
 #ifdef ACC_PHASE_PROF
         {
-            std::vector<unsigned long long> h(8 * prof_rows);
-            ACC_HIP(hipMemcpyAsync(h.data(), prof_buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-            ACC_HIP(hipStreamSynchronize(st));
+            const std::vector<unsigned long long> h = prof_read(prof_buf, 8 * prof_rows, st);
             double sum[6] = {}, mx[6] = {};
             size_t w = 0;
             for (size_t r = 0; r < prof_rows; ++r) {
@@ -3819,9 +2944,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
     if (nbig || nrun) ctx->join(nrun ? 2 : 1);
 #ifdef ACC_PHASE_PROF
     if (nbig && win_ok) {
-        std::vector<unsigned long long> h(10);
-        ACC_HIP(hipMemcpyAsync(h.data(), ctx->get<unsigned long long>("v2_win_prof", 10), 80, hipMemcpyDeviceToHost, st));
-        ACC_HIP(hipStreamSynchronize(st));
+        const std::vector<unsigned long long> h = prof_read(win_buf, 10, st);
         const double nt = h[6] ? (double)h[6] : 1.0;
         fprintf(stderr, "[win_phase] txns=%llu avg cycles per txn (thread 0 of each block): runs+lowend %.0f gather %.0f "
                 "below-sort %.0f prefix %.0f span-writes %.0f rank-map %.0f list-wait %.0f | avg E %.1f span words %.1f below %.1f\n",
@@ -3846,43 +2969,7 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
         ctx->stat("keydeps.window_txns", ctx->pinned[7] + ctx->pinned[8]);
     }
     if (nfb) {
-        need_pair_pos();
-        uint64_t *vcnt = ctx->get<uint64_t>("cnt", P);
-        uint32_t *vcnz = ctx->get<uint32_t>("cnz", P + 1);
-        uint32_t *fb_list = ctx->get<uint32_t>("v2_fb_list", nbig);
-        // txns beyond the block tiers (> 64 keys, > HUGE_E raw entries, or ranks beyond 25 bits): gather to global
-        // memory, sort by (txn, value, key) for the TxnId array and by (txn, key, value) for the arena order
-        uint64_t *fb_e = ctx->get<uint64_t>("v2_fb_e", nfb);
-        uint64_t *fb_off = ctx->get<uint64_t>("v2_fb_off", nfb + 1);
-        uint64_t *fb_maxk = ctx->get<uint64_t>("v2_fb_maxk", 1);
-        ACC_HIP(hipMemsetAsync(fb_maxk, 0, sizeof(uint64_t), st));
-        launch(ctx, "v2_fb_sizes", k_fb_sizes, dim3(grid_for(nfb, BLOCK)), dim3(BLOCK), 0, (uint32_t)nfb,
-               (const uint32_t *)fb_list, key_off, (const uint64_t *)vdep_off, fb_e, fb_maxk);
-        scan<uint64_t, OpAdd<uint64_t>>(ctx, fb_e, fb_off, nfb, true, fb_off + nfb);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, fb_maxk, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        const int bbits = bits_for(nfb - 1);
-        const int kbits = std::max(1, bits_for(ctx->pinned[0] - 1));   // key index within its txn
-        if (bbits + rbits + kbits > 64) fail(ACC_E_CAP, "too many oversized txns for the global KeyDeps path");
-        uint64_t *gkey = ctx->get<uint64_t>("v2_gkey", efb);
-        launch(ctx, "v2_big_gather", k_v2_big_gather, dim3((unsigned)((nfb + WAVES - 1) / WAVES)), dim3(BLOCK), 0,
-               (uint32_t)nfb, (const uint32_t *)fb_list, (const uint64_t *)fb_off, vv, (const uint64_t *)vcnt, key_off,
-               rbits, kbits, gkey);
-        Sorted s1 = radix_sort(ctx, "rs_big1", gkey, nullptr, efb, bbits + rbits + kbits);
-        uint32_t *nflag = ctx->get<uint32_t>("v2_big_nflag", efb);
-        uint32_t *nincl = ctx->get<uint32_t>("v2_big_nincl", efb);
-        launch(ctx, "v2_big_newflag", k_v2_big_newflag, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb,
-               (const uint64_t *)s1.keys, kbits, nflag);
-        scan<uint32_t, OpAdd<uint32_t>>(ctx, nflag, nincl, efb, false);
-        uint32_t *idx1 = ctx->get<uint32_t>("v2_big_idx1", efb);
-        uint64_t *key2 = ctx->get<uint64_t>("v2_big_key2", efb);
-        launch(ctx, "v2_big_rank", k_v2_big_rank, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb, (const uint64_t *)s1.keys,
-               (const uint32_t *)nincl, (const uint32_t *)fb_list, (const uint64_t *)fb_off, rbits, kbits, key_off,
-               (const uint64_t *)vdep_off, (const uint32_t *)txn_of_rank, dep_scr, u_cnt, idx1, key2);
-        Sorted s2 = radix_sort(ctx, "rs_big2", key2, nullptr, efb, bbits + kbits + rbits);
-        launch(ctx, "v2_big_arena", k_v2_big_arena, dim3(grid_for(efb, BLOCK)), dim3(BLOCK), 0, efb,
-               (const uint32_t *)s2.vals, (const uint64_t *)s2.keys, (const uint32_t *)idx1, (const uint32_t *)fb_list,
-               (const uint64_t *)fb_off, rbits, kbits, key_off, (const uint32_t *)vcnz, (const uint64_t *)arena_off, arena);
+        global_fallback(ctx, cb, vv, wo, nfb, efb);
         finish();
     }
     ctx->stat("keydeps.stream_txns", n - nbig);
@@ -3899,936 +2986,44 @@ static void keydeps_core(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view 
     ctx->kd_valid = true;
 }
 
+// KeyDeps of a built batch: the exact replay (keydeps_replay.hip) when executeAt ties exist, where the FAST
+// bisection's pick is order-dependent, or under ACC_OPT_FORCE_REPLAY; else the run-based path.
+void keydeps_of(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
+{
+    if (!cb.cfk) {
+        *view = ctx->kd_view;   // the empty result build_cfk left
+    } else if (cb.ties || (ctx->flags & ACC_OPT_FORCE_REPLAY)) {
+        need_pair_pos(ctx, cb);
+        keydeps_replay(ctx, cb, view);
+    } else {
+        keydeps_runs(ctx, cb, view);
+    }
+}
 
 void keydeps_batch(acc_ctx *ctx, const acc_batch_in *in, acc_keydeps_view *view)
 {
-    keydeps_core(ctx, in, view, nullptr);
-}
-
-// ---------------------------------------------------------------- KeyDeps of a mixed key/range batch
-//
-// A range-domain txn T is no CommandsForKey member (SafeCommandStore.updateCommandsForKey registers key txns only,
-// local/SafeCommandStore.java:217-240); as a query it visits every CFK whose key lies inside its store-sliced ranges
-// (impl/InMemoryCommandStore.java:274-289: commandsForKey.subMap(start, startInclusive, end, endInclusive)) and runs
-// the same mapReduceActive there. The key txns' results come from keydeps_core; each range txn's covered CFK keys
-// become "virtual" queries (T, segment) answered by the exact-replay scan (make_query / run_query), then one sort of
-// (txn, TxnId rank) gives every range txn's TxnId union and indices.
-
-constexpr uint64_t MX_ERR_DOMAIN = 1, MX_ERR_EMPTY = 2, MX_ERR_UNSORTED = 4, MX_ERR_OFF = 8;
-constexpr uint32_t MX_PIECE = 32;   // covered segments per work piece
-
-// Bucket directory of the sorted CFK keys: bucket(x) = (x - seg_key[0]) >> shift over 2^tbits buckets, the shift
-// making the key span fit; bstart[b] = first segment whose bucket is >= b (b in [0, 2^tbits]). A bound search then
-// bisects one bucket (a few keys) instead of all segments: 2-3 dependent loads instead of ~25.
-__device__ __forceinline__ uint32_t mx_shift(const uint64_t *seg_key, uint32_t nseg, uint32_t tbits)
-{
-    const uint64_t span = seg_key[nseg - 1] - seg_key[0];
-    const uint32_t sb = span ? 64u - (uint32_t)__clzll((long long)span) : 0u;
-    return sb > tbits ? sb - tbits : 0u;
-}
-
-// bend[b] = 1 + the last segment of bucket b (written by that segment; 0 for empty buckets, zeroed before): an
-// exclusive max-scan of bend is bstart (keys are sorted, so the segments of buckets <= b are a prefix)
-__global__ __launch_bounds__(BLOCK) void k_mx_buckets(uint32_t nseg, uint32_t tbits, const uint64_t *__restrict__ seg_key,
-                                                      uint32_t *__restrict__ bend)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nseg) return;
-    const uint32_t sh = mx_shift(seg_key, nseg, tbits);
-    const uint64_t k0 = seg_key[0], b = (seg_key[i] - k0) >> sh;
-    if (i + 1 == nseg || ((seg_key[i + 1] - k0) >> sh) != b) bend[b] = i + 1;
-}
-
-// first segment m in [0, nseg) with seg_key[m] > x (upper) / >= x (!upper)
-__device__ __forceinline__ uint32_t mx_bound(const uint64_t *seg_key, const uint32_t *bstart, uint32_t nseg, uint32_t sh,
-                                             uint32_t tbits, uint64_t x, bool upper)
-{
-    const uint64_t k0 = seg_key[0];
-    if (x < k0) return 0;
-    uint64_t b = (x - k0) >> sh;
-    if (b >= (1ull << tbits)) return nseg;
-    uint32_t lo = bstart[b], hi = bstart[b + 1];
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (upper ? seg_key[m] <= x : seg_key[m] < x) lo = m + 1; else hi = m; }
-    return lo;
-}
-
-// validation (TxnId.domain(), Range start < end, Ranges.ofSortedAndDeoverlapped) and, per range, its run of covered
-// segments [ra, ra + rcnt) over the sorted CFK keys, its owner and its number of work pieces
-__global__ __launch_bounds__(BLOCK) void k_mx_ranges(uint32_t n, const uint64_t *__restrict__ tl,
-                                                     const uint32_t *__restrict__ key_off, const uint32_t *__restrict__ rng_off,
-                                                     const uint64_t *__restrict__ rs, const uint64_t *__restrict__ re,
-                                                     uint32_t end_inclusive, const uint64_t *__restrict__ seg_key, uint32_t nseg,
-                                                     const uint32_t *__restrict__ bstart, uint32_t tbits,
-                                                     uint32_t *__restrict__ ra, uint32_t *__restrict__ rowner,
-                                                     uint64_t *__restrict__ rcnt, uint64_t *__restrict__ rpieces,
-                                                     uint64_t *__restrict__ errs)
-{
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= n) return;
-    const bool isr = (tl[t] & 1u) != 0;
-    const uint32_t r0 = rng_off[t], r1 = rng_off[t + 1];
-    uint64_t e = 0;
-    if (r1 < r0) e |= MX_ERR_OFF;
-    else {
-        if (isr && key_off[t + 1] != key_off[t]) e |= MX_ERR_DOMAIN;
-        if (!isr && r1 != r0) e |= MX_ERR_DOMAIN;
-        for (uint32_t j = r0; j < r1; ++j) {
-            const uint64_t s = rs[j], x = re[j];
-            if (s >= x) e |= MX_ERR_EMPTY;
-            if (j > r0 && re[j - 1] > s) e |= MX_ERR_UNSORTED;
-            // EndInclusive (s, x]: keys > s .. <= x; StartInclusive [s, x): keys >= s .. < x
-            uint32_t a = 0, b = 0;
-            if (nseg) {
-                const uint32_t sh = mx_shift(seg_key, nseg, tbits);
-                a = mx_bound(seg_key, bstart, nseg, sh, tbits, s, end_inclusive != 0);
-                b = mx_bound(seg_key, bstart, nseg, sh, tbits, x, end_inclusive != 0);
-            }
-            const uint32_t c = (e || b < a) ? 0u : b - a;
-            ra[j] = a;
-            rowner[j] = t;
-            rcnt[j] = c;
-            rpieces[j] = (c + MX_PIECE - 1) / MX_PIECE;
-        }
-    }
-    if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
-}
-
-
-// work pieces: piece p = (range, first covered segment), at most MX_PIECE segments each. Its record (one thread per
-// range writes its pieces', so the count / emit passes read one record instead of a chain of dependent loads):
-// prec[2p] = (owner txn, first segment, covered-key index of that segment within the txn's keys, queries),
-// prec[2p + 1] = (T.executeAt rank S, T's TxnId rank, T.kind().witnesses() mask | p1 << 8, 0)
-__global__ __launch_bounds__(BLOCK) void k_mx_pieces(uint32_t R, const uint64_t *__restrict__ poff, const uint32_t *__restrict__ ra,
-                                                     const uint32_t *__restrict__ rowner, const uint64_t *__restrict__ rcnt,
-                                                     const uint64_t *__restrict__ r_off, const uint32_t *__restrict__ rng_off,
-                                                     const uint32_t *__restrict__ rank, uint32_t n, const uint64_t *__restrict__ tl,
-                                                     uint4 *__restrict__ prec)
-{
-    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j >= R) return;
-    const uint64_t p0 = poff[j], p1 = poff[j + 1];
-    if (p0 == p1) return;
-    const uint32_t t = rowner[j], a = ra[j], c = (uint32_t)rcnt[j];
-    const uint32_t kb = (uint32_t)(r_off[j] - r_off[rng_off[t]]);
-    const uint32_t S = rank[n + t], tr = rank[t];
-    const uint32_t wk = witnesses((uint32_t)(tl[t] >> 1) & 7u) | (S != tr ? 1u << 8 : 0u);
-    for (uint64_t p = p0; p < p1; ++p) {
-        const uint32_t k0 = (uint32_t)(p - p0) * MX_PIECE;
-        prec[2 * p] = make_uint4(t, a + k0, kb + k0, min(c - k0, MX_PIECE));
-        prec[2 * p + 1] = make_uint4(S, tr, wk, 0);
-    }
-}
-
-// 32 lanes per piece, one covered segment (one query) per lane
-__device__ __forceinline__ uint32_t mx_scan32(uint32_t x, uint32_t sub)   // inclusive, within the 32-lane half
-{
-#pragma unroll
-    for (uint32_t d = 1; d < 32; d <<= 1) {
-        const uint32_t u = __shfl_up(x, d, 64);
-        if (sub >= d) x += u;
-    }
-    return x;
-}
-
-// count pass: entries and non-empty keys per piece. Each lane keeps its count in qc, or, for a single entry (nearly
-// every non-empty (range txn, key) query: one conflicting key txn), the entry itself with MX_ONE set, so the emit pass
-// replays the scan only for the rare lanes with two or more entries
-constexpr uint32_t MX_ONE = 0x80000000u;
-__device__ __forceinline__ uint32_t mx_qcount(uint32_t q) { return (q & MX_ONE) ? 1u : q; }
-
-// A segment holding one CFK entry (nearly every covered key of a sparse key space) is answered in place: with
-// s1 = s0 + 1, make_query_ts / run_query reduce to one test of that entry. Its committed[] is itself or empty, so any
-// maxCommittedBefore M is its own executeAt, which the prefix-max prune (executeAt < M) never removes; nothing of the
-// segment lies below scanStart = s0; the scan [s0, insertPos) is the entry exactly when its TxnId is below T.executeAt.
-// Queries over longer segments go to deferred lists that k_mx_pdefer answers densely, adding into the piece totals:
-// MX_DSLOTS lists (block b appends to list b % MX_DSLOTS with wave-aggregated atomics on that list's counter, so the
-// appends spread over many addresses), list s holding at most dcap entries (its blocks' lanes); dlist null: every
-// query in place.
-constexpr uint32_t MX_DSLOTS = 1024;
-__global__ __launch_bounds__(BLOCK) void k_mx_pcount(uint64_t NP, const uint4 *__restrict__ prec, CfkView v,
-                                                     uint64_t *__restrict__ pe_cnt, uint32_t *__restrict__ pk_cnt,
-                                                     uint32_t *__restrict__ qc, uint32_t pack, uint32_t *__restrict__ dlist,
-                                                     uint32_t *__restrict__ dcnt, uint32_t dcap)
-{
-    const uint64_t p = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 5;
-    const uint32_t sub = threadIdx.x & 31u, g0 = lane_id() & 32u;
-    uint32_t c = 0;
-    bool dfr = false;
-    if (p < NP) {
-        const uint4 pr = prec[2 * p], pq = prec[2 * p + 1];
-        uint32_t f = 0;
-        if (sub < pr.w) {
-            const uint32_t seg = pr.y + sub;
-            const uint32_t s0 = v.seg_start[seg], s1 = v.seg_start[seg + 1];
-            if (dlist && s1 - s0 == 1) {
-                const uint32_t S = pq.x, trank = pq.y, wk = pq.z & 0xFFu;
-                const uint32_t r = v.s_rank[s0], info = v.s_info[s0], st = info & 7u;
-                c = (r < S && ((wk >> (info >> 3)) & 1u) && st != 0 && st != 7 && !((pq.z >> 8) && r == trank)) ? 1u : 0u;
-                f = r;
-            } else if (dlist) dfr = true;
-            else c = run_query<false, true>(v, make_query_ts(v, pr.x, seg), &f);
-        }
-        qc[p * 32 + sub] = (pack && c == 1) ? (MX_ONE | f) : c;
-    }
-    const uint64_t db = __ballot(dfr);
-    if (db) {
-        const uint32_t slot = blockIdx.x % MX_DSLOTS;
-        uint32_t base = 0;
-        const uint32_t lead = (uint32_t)__ffsll((unsigned long long)db) - 1;
-        if (lane_id() == lead) base = atomicAdd(&dcnt[slot], (uint32_t)__popcll(db));
-        base = __shfl(base, (int)lead, 64);
-        if (dfr) dlist[(size_t)slot * dcap + base + (uint32_t)__popcll(db & ((1ull << lane_id()) - 1))] = (uint32_t)(p * 32 + sub);
-    }
-    const uint32_t ce = mx_scan32(c, sub), ck = mx_scan32(c != 0 ? 1u : 0u, sub);
-    const uint32_t te = __shfl(ce, (int)(g0 + 31), 64), tk = __shfl(ck, (int)(g0 + 31), 64);
-    if (p < NP && sub == 0) { pe_cnt[p] = te; pk_cnt[p] = tk; }
-}
-
-// the deferred queries (segments of two or more entries): the exact-replay scan, one lane each; blockIdx.y = list,
-// a grid-stride loop over its device-side count
-__global__ __launch_bounds__(BLOCK) void k_mx_pdefer(const uint4 *__restrict__ prec, CfkView v, const uint32_t *__restrict__ dlist,
-                                                     const uint32_t *__restrict__ dcnt, uint32_t dcap, uint64_t *__restrict__ pe_cnt,
-                                                     uint32_t *__restrict__ pk_cnt, uint32_t *__restrict__ qc, uint32_t pack)
-{
-    const uint32_t nd = dcnt[blockIdx.y];
-    const uint32_t *lst = dlist + (size_t)blockIdx.y * dcap;
-    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < nd; i += gridDim.x * BLOCK) {
-        const uint32_t q = lst[i], p = q >> 5, sub = q & 31u;
-        const uint4 pr = prec[2 * (uint64_t)p];
-        uint32_t f = 0;
-        const uint32_t c = run_query<false, true>(v, make_query_ts(v, pr.x, pr.y + sub), &f);
-        qc[q] = (pack && c == 1) ? (MX_ONE | f) : c;
-        if (c) {
-            atomicAdd((unsigned long long *)&pe_cnt[p], (unsigned long long)c);
-            atomicAdd(&pk_cnt[p], 1u);
-        }
-    }
-}
-
-struct MxE {   // emitted entries and key records of the range txns
-    uint32_t *deps, *owner;          // [Ex]: TxnId rank, owning txn
-    uint32_t *kx_idx, *kx_end;       // [Kx]: covered-key index, end of its entries (absolute entry index)
-    uint64_t *kx_code;               // [Kx]: key code
-};
-
-__global__ __launch_bounds__(BLOCK) void k_mx_pemit(uint64_t NP, const uint4 *__restrict__ prec, const uint64_t *__restrict__ seg_key,
-                                                    CfkView v, const uint64_t *__restrict__ pe_off,
-                                                    const uint32_t *__restrict__ pk_off, MxE x, const uint32_t *__restrict__ qc)
-{
-    const uint64_t p = ((uint64_t)blockIdx.x * BLOCK + threadIdx.x) >> 5;
-    const uint32_t sub = threadIdx.x & 31u;
-    uint32_t c = 0, q = 0;
-    uint4 pr = make_uint4(0, 0, 0, 0);
-    bool act = false;
-    if (p < NP) {
-        pr = prec[2 * p];
-        q = qc[p * 32 + sub];
-        act = sub < pr.w;
-        c = act ? mx_qcount(q) : 0u;
-    }
-    const uint32_t ce = mx_scan32(c, sub), ck = mx_scan32(c != 0 ? 1u : 0u, sub);
-    if (!act || c == 0) return;
-    const uint64_t e = pe_off[p] + (ce - c);
-    const uint32_t seg = pr.y + sub;
-    if (q & MX_ONE) x.deps[e] = q & ~MX_ONE;
-    else run_query<true>(v, make_query_ts(v, pr.x, seg), x.deps + e);
-    const uint32_t kr = pk_off[p] + ck - 1;
-    x.kx_idx[kr] = pr.z + sub;
-    x.kx_code[kr] = seg_key[seg];
-    x.kx_end[kr] = (uint32_t)(e + c);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_mx_toff(uint32_t n, const uint32_t *__restrict__ rng_off, const uint64_t *__restrict__ poff,
-                                                   const uint64_t *__restrict__ pe_off, const uint32_t *__restrict__ pk_off,
-                                                   uint64_t *__restrict__ etoff, uint32_t *__restrict__ ktoff)
-{
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t > n) return;
-    const uint64_t p = poff[rng_off[t]];
-    etoff[t] = pe_off[p];
-    ktoff[t] = pk_off[p];
-}
-
-// the owning txn of every emitted entry (fallback union only)
-__global__ __launch_bounds__(BLOCK) void k_mx_owner(uint32_t n, const uint64_t *__restrict__ etoff, uint32_t *__restrict__ owner)
-{
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t >= n) return;
-    for (uint64_t e = etoff[t]; e < etoff[t + 1]; ++e) owner[e] = t;
-}
-
-// sort keys (txn, TxnId rank) of the emitted entries (fallback union)
-__global__ __launch_bounds__(BLOCK) void k_mx_sortkeys(uint64_t E, const uint32_t *__restrict__ deps, const uint32_t *__restrict__ owner,
-                                                       int rbits, uint64_t *__restrict__ key)
-{
-    const uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (e < E) key[e] = ((uint64_t)owner[e] << rbits) | deps[e];
-}
-
-__global__ __launch_bounds__(BLOCK) void k_mx_uflag(uint64_t E, const uint64_t *__restrict__ sk, uint32_t *__restrict__ f)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < E) f[i] = i == 0 || sk[i] != sk[i - 1];
-}
-
-struct MxKv {   // the key-txn KeyDeps (keydeps_core's view)
-    const uint64_t *arena_off, *kd_off, *u_off;
-    const int32_t *arena;
-    const uint32_t *key_idx, *dep_txn;
-};
-struct MxOut {
-    uint64_t *arena_off, *kd_off, *u_off;
-    int32_t *arena;
-    uint32_t *key_idx, *dep_txn;
-    uint64_t *kd_key;
-};
-// per-txn TxnId union of the emitted entries: idx_of_e[e] = index of entry e's TxnId in its txn's union,
-// dep_scr[e0 + i] = batch index of the i-th union TxnId, ucnt[t] = union size
-struct MxU {
-    const uint32_t *deps;
-    const uint64_t *etoff;
-    const uint32_t *txn_of_rank;
-    uint32_t *idx_of_e, *dep_scr, *ucnt;
-};
-
-// per txn: entry count routing into tier lists (txns without entries: none): E <= 16, <= 32, <= 64 (lane groups),
-// <= MX_MID_E (wave, LDS), <= MX_BLK_E (block); beyond: the sorted fallback (flag gst[1]).
-// gst: [0] block count, [1] fallback flag, [2] mid count, [3..5] 16 / 32 / 64-lane counts
-constexpr uint32_t MX_MID_E = 512, MX_BLK_E = 4096;
-struct MxLists {
-    uint32_t *l[5];   // 16, 32, 64, mid, block
-};
-// MX_RT chunks of BLOCK txns per workgroup: one list-counter add per list and workgroup (the five counters share one
-// line: per-256-txn adds serialised there); list order is free (each txn writes its own outputs)
-constexpr int MX_RT = 16;
-__global__ __launch_bounds__(BLOCK) void k_mx_route(uint32_t n, const uint64_t *__restrict__ etoff, MxLists L,
-                                                    uint64_t *__restrict__ gst)
-{
-    __shared__ uint32_t wcnt[5][MX_RT * WAVES], base[5];
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6;
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    int cs[MX_RT];
-    bool ovf = false;
-#pragma unroll
-    for (int r = 0; r < MX_RT; ++r) {
-        const uint32_t t = (blockIdx.x * MX_RT + (uint32_t)r) * BLOCK + threadIdx.x;
-        int c = -1;
-        if (t < n) {
-            const uint64_t E = etoff[t + 1] - etoff[t];
-            if (E == 0) c = -1;
-            else if (E <= 16) c = 0;
-            else if (E <= 32) c = 1;
-            else if (E <= 64) c = 2;
-            else if (E <= MX_MID_E) c = 3;
-            else if (E <= MX_BLK_E) c = 4;
-            else ovf = true;
-        }
-        cs[r] = c;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const uint32_t cnt = (uint32_t)__popcll(__ballot(c == k));
-            if (lane == 0) wcnt[k][r * WAVES + w] = cnt;
-        }
-    }
-    if (ovf) atomicOr((unsigned long long *)&gst[1], 1ull);
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        uint32_t tot = 0;
-        for (int q = 0; q < MX_RT * WAVES; ++q) { const uint32_t x = wcnt[threadIdx.x][q]; wcnt[threadIdx.x][q] = tot; tot += x; }
-        const int slot = threadIdx.x == 4 ? 0 : threadIdx.x == 3 ? 2 : 3 + (int)threadIdx.x;
-        base[threadIdx.x] = tot ? (uint32_t)atomicAdd((unsigned long long *)&gst[slot], (unsigned long long)tot) : 0u;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < MX_RT; ++r) {
-        const int c = cs[r];
-        const uint32_t t = (blockIdx.x * MX_RT + (uint32_t)r) * BLOCK + threadIdx.x;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const uint64_t bal = __ballot(c == k);
-            if (c == k) L.l[k][base[k] + wcnt[k][r * WAVES + w] + (uint32_t)__popcll(bal & lt)] = t;
-        }
-    }
-}
-
-// groups of S lanes (S = 16, 32, 64), one listed txn each (E <= S): register bitonic of (rank << 32 | local entry)
-template <int S>
-__global__ __launch_bounds__(BLOCK) void k_mx_union_seg(const uint32_t *__restrict__ list, const uint64_t *__restrict__ cnt, MxU u)
-{
-    constexpr uint32_t G = 64 / S;
-    const uint32_t lane = lane_id(), grp = lane / S, sub = lane & (S - 1);
-    const uint32_t li = (blockIdx.x * WAVES + (threadIdx.x >> 6)) * G + grp;
-    const bool live = li < (uint32_t)*cnt;
-    const uint32_t t = live ? list[li] : 0;
-    const uint64_t e0 = live ? u.etoff[t] : 0;
-    const uint32_t E = live ? (uint32_t)(u.etoff[t + 1] - e0) : 0;
-    const bool in = sub < E;
-    uint64_t x = in ? (((uint64_t)u.deps[e0 + sub] << 32) | sub) : ~0ull;
-#pragma unroll
-    for (uint32_t k = 2; k <= (uint32_t)S; k <<= 1) {
-#pragma unroll
-        for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
-            const uint64_t y = xor_lanes(x, (int)jj);
-            const bool up = k == (uint32_t)S || (lane & k) == 0, lower = (lane & jj) == 0;   // ascending per group
-            const uint64_t mn = x < y ? x : y, mx = x < y ? y : x;
-            x = (lower == up) ? mn : mx;
-        }
-    }
-    const uint64_t prev = shfl_up(x, 1);
-    const bool nw = in && (sub == 0 || (prev >> 32) != (x >> 32));
-    const uint64_t gmask = S == 64 ? ~0ull : (((1ull << S) - 1) << (grp * S));
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    const uint64_t bal = __ballot(nw) & gmask;
-    const uint32_t idx = (uint32_t)__popcll(bal & lt) + (nw ? 1u : 0u) - 1u;
-    if (in) {
-        u.idx_of_e[e0 + (uint32_t)x] = idx;
-        if (nw) u.dep_scr[e0 + idx] = u.txn_of_rank[(uint32_t)(x >> 32)];
-    }
-    if (live && sub == 0) u.ucnt[t] = (uint32_t)__popcll(bal);
-}
-
-// R values per lane sorted across the wave (element r * 64 + lane), ascending: partners 64 or more apart are registers
-// of the same lane, the others lanes (shuffles)
-template <int R>
-__device__ __forceinline__ void wave_reg_sort(uint64_t (&v)[R])
-{
-    const uint32_t lane = lane_id();
-#pragma unroll
-    for (uint32_t k = 2; k <= 64u * R; k <<= 1) {
-#pragma unroll
-        for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
-            if (jj >= 64) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const int r2 = r ^ (int)(jj >> 6);
-                    if (r2 > r) {
-                        const bool up = ((((uint32_t)r << 6) | lane) & k) == 0;
-                        const uint64_t a = v[r], b = v[r2];
-                        if ((a > b) == up) { v[r] = b; v[r2] = a; }
-                    }
-                }
-            } else {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const uint64_t y = xor_lanes(v[r], (int)jj);
-                    const bool up = ((((uint32_t)r << 6) | lane) & k) == 0, lower = (lane & jj) == 0;
-                    const uint64_t mn = v[r] < y ? v[r] : y, mx = v[r] < y ? y : v[r];
-                    v[r] = (lower == up) ? mn : mx;
-                }
-            }
-        }
-    }
-}
-
-// a txn's union over E <= 64 R entries in registers: sort (rank << 32 | entry), distinct ranks -> indices
-template <int R>
-__device__ __forceinline__ void mx_union_regs(const MxU &u, uint32_t t, uint64_t e0, uint32_t E)
-{
-    const uint32_t lane = lane_id();
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    uint64_t v[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint32_t i = ((uint32_t)r << 6) | lane;
-        v[r] = i < E ? (((uint64_t)u.deps[e0 + i] << 32) | i) : ~0ull;
-    }
-    wave_reg_sort<R>(v);
-    uint32_t base = 0;
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const uint64_t x = v[r];
-        uint64_t prev = shfl_up(x, 1);
-        if (r > 0) {
-            const uint64_t pl = shfl_idx(v[r - 1], 63);
-            if (lane == 0) prev = pl;
-        }
-        const uint32_t i = ((uint32_t)r << 6) | lane;
-        const bool in = i < E;
-        const bool nw = in && (i == 0 || (prev >> 32) != (x >> 32));
-        const uint64_t bal = __ballot(nw);
-        const uint32_t idx = base + (uint32_t)__popcll(bal & lt) + (nw ? 1u : 0u) - 1u;
-        if (in) {
-            u.idx_of_e[e0 + (uint32_t)x] = idx;
-            if (nw) u.dep_scr[e0 + idx] = u.txn_of_rank[(uint32_t)(x >> 32)];
-        }
-        base += (uint32_t)__popcll(bal);
-    }
-    if (lane == 0) u.ucnt[t] = base;
-}
-
-// wave per listed txn, 64 < E <= MX_MID_E: registers up to 256 entries, one wave's LDS bitonic beyond
-__global__ __launch_bounds__(BLOCK) void k_mx_union_mid(const uint32_t *__restrict__ list, const uint64_t *__restrict__ gst, MxU u)
-{
-    __shared__ uint64_t sbuf[WAVES][MX_MID_E];
-    const uint32_t lane = lane_id(), w = threadIdx.x >> 6, i = blockIdx.x * WAVES + w;
-    if (i >= (uint32_t)gst[2]) return;
-    const uint32_t t = list[i];
-    uint64_t *buf = sbuf[w];
-    const uint64_t e0 = u.etoff[t];
-    const uint32_t E = (uint32_t)(u.etoff[t + 1] - e0);
-    if (E <= 128) { mx_union_regs<2>(u, t, e0, E); return; }   // wave-uniform
-    if (E <= 256) { mx_union_regs<4>(u, t, e0, E); return; }
-    uint32_t n2 = 128;
-    while (n2 < E) n2 <<= 1;
-    for (uint32_t q = lane; q < n2; q += 64) buf[q] = q < E ? (((uint64_t)u.deps[e0 + q] << 32) | q) : ~0ull;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    wave_bitonic_lds(buf, n2);
-    const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    uint32_t distinct = 0;
-    for (uint32_t q0 = 0; q0 < E; q0 += 64) {
-        const uint32_t q = q0 + lane;
-        const bool in = q < E;
-        const uint64_t x = in ? buf[q] : 0;
-        const bool nw = in && (q == 0 || (buf[q - 1] >> 32) != (x >> 32));
-        const uint64_t bal = __ballot(nw);
-        const uint32_t idx = distinct + (uint32_t)__popcll(bal & lt) + (nw ? 1u : 0u) - 1u;
-        if (in) {
-            u.idx_of_e[e0 + (uint32_t)x] = idx;
-            if (nw) u.dep_scr[e0 + idx] = u.txn_of_rank[(uint32_t)(x >> 32)];
-        }
-        distinct += (uint32_t)__popcll(bal);
-    }
-    if (lane == 0) u.ucnt[t] = distinct;
-}
-
-// block per listed txn, 64 < E <= MX_BLK_E: LDS bitonic
-__global__ __launch_bounds__(BLOCK) void k_mx_union_block(const uint32_t *__restrict__ list, const uint64_t *__restrict__ gst, MxU u)
-{
-    __shared__ uint64_t buf[MX_BLK_E];
-    __shared__ uint32_t lds[WAVES];
-    const uint32_t b = blockIdx.x;
-    if (b >= (uint32_t)gst[0]) return;
-    const uint32_t t = list[b], tid = threadIdx.x;
-    const uint64_t e0 = u.etoff[t];
-    const uint32_t E = (uint32_t)(u.etoff[t + 1] - e0);
-    uint32_t n2 = 128;
-    while (n2 < E) n2 <<= 1;
-    for (uint32_t i = tid; i < n2; i += BLOCK) buf[i] = i < E ? (((uint64_t)u.deps[e0 + i] << 32) | i) : ~0ull;
-    __syncthreads();
-    for (uint32_t k = 2; k <= n2; k <<= 1)
-        for (uint32_t jj = k >> 1; jj > 0; jj >>= 1) {
-            for (uint32_t pi = tid; pi < (n2 >> 1); pi += BLOCK) {
-                const uint32_t i = ((pi & ~(jj - 1)) << 1) | (pi & (jj - 1)), l = i | jj;
-                const uint64_t xa = buf[i], ya = buf[l];
-                if ((xa > ya) == ((i & k) == 0)) { buf[i] = ya; buf[l] = xa; }
-            }
-            __syncthreads();
-        }
-    // distinct index: chunked scan of the "new value" flags (contiguous chunks per thread)
-    const uint32_t per = (E + BLOCK - 1) / BLOCK, lo = min(E, tid * per), hi = min(E, lo + per);
-    uint32_t c = 0;
-    for (uint32_t i = lo; i < hi; ++i) c += i == 0 || (buf[i] >> 32) != (buf[i - 1] >> 32);
-    uint32_t total;
-    uint32_t run = block_exclusive(c, OpAdd<uint32_t>(), lds, total);
-    for (uint32_t i = lo; i < hi; ++i) {
-        const uint64_t x = buf[i];
-        const bool nw = i == 0 || (x >> 32) != (buf[i - 1] >> 32);
-        run += nw;
-        u.idx_of_e[e0 + (uint32_t)x] = run - 1;
-        if (nw) u.dep_scr[e0 + run - 1] = u.txn_of_rank[(uint32_t)(x >> 32)];
-    }
-    if (tid == 0) u.ucnt[t] = total;
-}
-
-// global fallback (some txn beyond MX_BLK_E): from the (txn, rank) sort
-__global__ __launch_bounds__(BLOCK) void k_mx_union_sorted(uint64_t E, const uint64_t *__restrict__ sk, const uint32_t *__restrict__ sperm,
-                                                           const uint32_t *__restrict__ uflag, const uint32_t *__restrict__ ucum,
-                                                           const uint32_t *__restrict__ owner, int rbits, MxU u)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= E) return;
-    const uint32_t e = sperm[i];
-    const uint64_t e0 = u.etoff[owner[e]];
-    const uint32_t idx = ucum[i] + uflag[i] - 1 - ucum[e0];
-    u.idx_of_e[e] = idx;
-    if (uflag[i]) u.dep_scr[e0 + idx] = u.txn_of_rank[(uint32_t)(sk[i] & ((1ull << rbits) - 1))];
-}
-__global__ __launch_bounds__(BLOCK) void k_mx_ucnt_sorted(uint32_t n, const uint64_t *__restrict__ etoff, const uint32_t *__restrict__ ucum,
-                                                          uint32_t *__restrict__ ucnt)
-{
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t < n) ucnt[t] = ucum[etoff[t + 1]] - ucum[etoff[t]];
-}
-
-__global__ __launch_bounds__(BLOCK) void k_mx_sizes(uint32_t n, MxKv kv, const uint64_t *__restrict__ etoff,
-                                                    const uint32_t *__restrict__ ktoff, const uint32_t *__restrict__ ucnt,
-                                                    uint64_t *__restrict__ a_cnt, uint64_t *__restrict__ kd_cnt,
-                                                    uint64_t *__restrict__ u_cnt)
-{
-    const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t == n) { a_cnt[n] = 0; kd_cnt[n] = 0; u_cnt[n] = 0; }   // the exclusive scans over n + 1 end in the totals
-    if (t >= n) return;
-    const uint64_t ex = etoff[t + 1] - etoff[t];
-    const uint64_t kd = ktoff[t + 1] - ktoff[t];
-    a_cnt[t] = (kv.arena_off[t + 1] - kv.arena_off[t]) + kd + ex;
-    kd_cnt[t] = (kv.kd_off[t + 1] - kv.kd_off[t]) + kd;
-    u_cnt[t] = (kv.u_off[t + 1] - kv.u_off[t]) + (ex ? ucnt[t] : 0u);
-}
-
-// the combined layout. A workgroup owns BLOCK consecutive txns, whose output runs are one contiguous range of each
-// output array: each output element takes its txn from a chunk owner map (chunk_owners) and reads from that txn's
-// source (key txns: keydeps_core's result, with key codes; range txns: their key records, per-entry union indices and
-// union TxnIds), so every write is a whole-line access.
-__global__ __launch_bounds__(BLOCK) void k_mx_write(uint32_t n, MxKv kv, const uint64_t *__restrict__ etoff,
-                                                    const uint32_t *__restrict__ ktoff, MxE x,
-                                                    const uint32_t *__restrict__ idx_of_e, const uint32_t *__restrict__ dep_scr,
-                                                    const uint32_t *__restrict__ key_off, const uint64_t *__restrict__ key_code,
-                                                    MxOut o)
-{
-    __shared__ uint64_t ao[BLOCK + 1], ko[BLOCK + 1], uo[BLOCK + 1];   // output offsets
-    __shared__ uint64_t sa[BLOCK], sk[BLOCK], su[BLOCK];                // source bases: arena / keys / TxnIds
-    __shared__ uint32_t kdn[BLOCK], kofs[BLOCK];                        // range txn: key records; key txn: key_off
-    __shared__ uint32_t own[8 * BLOCK], red[WAVES];                     // chunk owner map (chunk_owners)
-    const uint32_t t0 = blockIdx.x * BLOCK, nt = min((uint32_t)BLOCK, n - t0), tid = threadIdx.x;
-    if (tid < nt) {
-        const uint32_t t = t0 + tid;
-        ao[tid] = o.arena_off[t]; ko[tid] = o.kd_off[t]; uo[tid] = o.u_off[t];
-        const uint64_t e0 = etoff[t], ex = etoff[t + 1] - e0;
-        if (ex) {
-            const uint32_t k0 = ktoff[t];
-            kdn[tid] = ktoff[t + 1] - k0;
-            sa[tid] = e0; sk[tid] = k0; su[tid] = e0;
-        } else {
-            kdn[tid] = 0xFFFFFFFFu;   // a key txn
-            sa[tid] = kv.arena_off[t]; sk[tid] = kv.kd_off[t]; su[tid] = kv.u_off[t];
-            kofs[tid] = key_off[t];
-        }
-    }
-    if (tid == 0) { ao[nt] = o.arena_off[t0 + nt]; ko[nt] = o.kd_off[t0 + nt]; uo[nt] = o.u_off[t0 + nt]; }
-    __syncthreads();
-    // per array, chunks of U * BLOCK outputs: the owner map of the chunk (chunk_owners), then U outputs per thread,
-    // interleaved across the block (whole-line stores), each reading its txn from the map
-    constexpr int U = 8;
-    uint32_t carry = 0;
-    for (uint64_t c0 = ao[0]; c0 < ao[nt]; c0 += (uint64_t)U * BLOCK) {
-        chunk_owners<U>(nt, ao, c0, own, red, carry);
-        int32_t v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t p = (uint32_t)u * BLOCK + tid;
-            const uint64_t j = c0 + p;
-            v[u] = 0;
-            if (j < ao[nt]) {
-                const uint32_t a = own[p];
-                const uint64_t i = j - ao[a];
-                const uint32_t kd = kdn[a];
-                if (kd == 0xFFFFFFFFu) v[u] = kv.arena[sa[a] + i];
-                else if (i < kd) v[u] = (int32_t)(kd + (x.kx_end[sk[a] + i] - (uint32_t)sa[a]));
-                else v[u] = (int32_t)idx_of_e[sa[a] + i - kd];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t j = c0 + (uint64_t)u * BLOCK + tid;
-            if (j < ao[nt]) o.arena[j] = v[u];
-        }
-    }
-    carry = 0;
-    for (uint64_t c0 = ko[0]; c0 < ko[nt]; c0 += (uint64_t)U * BLOCK) {
-        chunk_owners<U>(nt, ko, c0, own, red, carry);
-        uint32_t ki[U];
-        uint64_t kc[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t p = (uint32_t)u * BLOCK + tid;
-            const uint64_t j = c0 + p;
-            ki[u] = 0; kc[u] = 0;
-            if (j < ko[nt]) {
-                const uint32_t a = own[p];
-                const uint64_t i = j - ko[a];
-                if (kdn[a] == 0xFFFFFFFFu) {
-                    ki[u] = kv.key_idx[sk[a] + i];
-                    kc[u] = key_code[kofs[a] + ki[u]];
-                } else {
-                    ki[u] = x.kx_idx[sk[a] + i];
-                    kc[u] = x.kx_code[sk[a] + i];
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t j = c0 + (uint64_t)u * BLOCK + tid;
-            if (j < ko[nt]) { o.key_idx[j] = ki[u]; o.kd_key[j] = kc[u]; }
-        }
-    }
-    carry = 0;
-    for (uint64_t c0 = uo[0]; c0 < uo[nt]; c0 += (uint64_t)U * BLOCK) {
-        chunk_owners<U>(nt, uo, c0, own, red, carry);
-        uint32_t d[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint32_t p = (uint32_t)u * BLOCK + tid;
-            const uint64_t j = c0 + p;
-            d[u] = 0;
-            if (j < uo[nt]) {
-                const uint32_t a = own[p];
-                const uint64_t i = j - uo[a];
-                d[u] = kdn[a] == 0xFFFFFFFFu ? kv.dep_txn[su[a] + i] : dep_scr[su[a] + i];
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const uint64_t j = c0 + (uint64_t)u * BLOCK + tid;
-            if (j < uo[nt]) o.dep_txn[j] = d[u];
-        }
-    }
-}
-
-void keydeps_mixed(acc_ctx *ctx, const acc_range_batch_in *in, acc_keydeps_view *view, SharedDict *shared)
-{
     if (!in || !view) fail(ACC_E_ARG, "null argument");
-    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
-    const uint32_t n = in->n_txn;
-    const size_t R = (size_t)in->n_ranges;
-    if (R >= 0xFFFFFFFFull) fail(ACC_E_ARG, "n_ranges must be < 2^32");
-    hipStream_t st = ctx->stream;
-    ctx->kd_valid = false;
-
-    // ---- key txns (and the CFK snapshot): keydeps_core over the key part of the batch
-    acc_batch_in kin{ n, in->mem, in->n_pairs, in->txn_id, in->execute_at, in->status, in->key_off, in->key_code };
-    acc_keydeps_view kv{};
-    KdState ks;
-    ks.sparse = R > 0;
-    keydeps_core(ctx, &kin, &kv, &ks);
-    ctx->kd_valid = false;
-    if (shared) {
-        shared->valid = ks.have_dict; shared->dict = ks.dict; shared->owner = ks.owner;
-        if (shared->ready && shared->valid) shared->ready(*shared);
-    }
-    if (n == 0) {
-        kv.kd_key = ctx->get<uint64_t>("mx_kd_key", 1);
-        *view = kv;
-        ctx->kd_view = kv;
-        ctx->kd_valid = true;
-        return;
-    }
-    const uint32_t *key_off = stage_in(ctx, "in_key_off", in->key_off, (size_t)n + 1, in->mem);
-    const uint64_t *key_code = stage_in(ctx, "in_key_code", in->key_code, (size_t)in->n_pairs, in->mem);
-    const uint64_t *tl = stage_in(ctx, "in_tl", in->txn_id.lsb, n, in->mem);
-    const uint32_t *rng_off = stage_in(ctx, "in_rng_off", in->rng_off, (size_t)n + 1, in->mem);
-    const uint64_t *rs = stage_in(ctx, "in_rng_start", in->rng_start, R, in->mem);
-    const uint64_t *re = stage_in(ctx, "in_rng_end", in->rng_end, R, in->mem);
-
-    // ---- covered segments per range, work pieces
-    uint32_t nseg = 0;
-    if (ks.cfk) {
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, ks.seg_incl + ks.P - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        nseg = (uint32_t)(ctx->pinned[0] & 0xFFFFFFFFu);
-    }
-    const uint64_t *seg_key = ks.cfk ? ks.seg_key : ctx->get<uint64_t>("mx_seg_key", 1);   // written by k_v2_apply
-    // bucket directory: about one key per bucket
-    const uint32_t tbits = nseg ? (uint32_t)std::min(26, std::max(0, bits_for(nseg) - 1)) : 0u;
-    const size_t nbk = (size_t)1 << tbits;
-    uint32_t *bstart = ctx->get<uint32_t>("mx_bstart", nbk + 1);
-    if (nseg) {
-        uint32_t *bend = ctx->get<uint32_t>("mx_bend", nbk);
-        ACC_HIP(hipMemsetAsync(bend, 0, nbk * sizeof(uint32_t), st));
-        launch(ctx, "mx_buckets", k_mx_buckets, dim3(grid_for(nseg, BLOCK)), dim3(BLOCK), 0, nseg, tbits,
-               (const uint64_t *)seg_key, bend);
-        scan<uint32_t, OpMax<uint32_t>>(ctx, bend, bstart, nbk, true, bstart + nbk);
-    }
-    uint32_t *ra = ctx->get<uint32_t>("mx_ra", R + 1);
-    uint32_t *rowner = ctx->get<uint32_t>("mx_rowner", R + 1);
-    uint64_t *rcnt = ctx->get<uint64_t>("mx_rcnt", R + 1);
-    uint64_t *rpieces = ctx->get<uint64_t>("mx_rpieces", R + 1);
-    uint64_t *r_off = ctx->get<uint64_t>("mx_r_off", R + 2);
-    uint64_t *poff = ctx->get<uint64_t>("mx_poff", R + 2);
-    uint64_t *errs = ctx->get<uint64_t>("mx_errs", 1);
-    ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
-    launch(ctx, "mx_ranges", k_mx_ranges, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, tl, key_off, rng_off, rs, re,
-           in->end_inclusive, (const uint64_t *)seg_key, nseg, (const uint32_t *)bstart, tbits, ra, rowner, rcnt, rpieces, errs);
-    if (R) {
-        const uint64_t *si[2] = { rcnt, rpieces };
-        uint64_t *so[2] = { r_off, poff }, *stot[2] = { r_off + R, poff + R };
-        const size_t sn[2] = { R, R };
-        scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 2, si, so, sn, true, stot);
-    } else {
-        ACC_HIP(hipMemsetAsync(r_off, 0, 8, st));
-        ACC_HIP(hipMemsetAsync(poff, 0, 8, st));
-    }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, r_off + R, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 2, poff + R, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t merr = ctx->pinned[0];
-    if (merr & MX_ERR_DOMAIN) fail(ACC_E_ARG, "a range-domain txn lists keys or a key-domain txn lists ranges (TxnId.domain())");
-    if (merr & MX_ERR_EMPTY) fail(ACC_E_ARG, "range start must be below its end (Range: start >= end)");
-    if (merr & MX_ERR_UNSORTED) fail(ACC_E_ARG, "ranges of a txn must be sorted and deoverlapped (Ranges.ofSortedAndDeoverlapped)");
-    if (merr & MX_ERR_OFF) fail(ACC_E_ARG, "rng_off must be non-decreasing");
-    const uint64_t V = ctx->pinned[1], NP = ctx->pinned[2];
-    if (V >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 (range txn, covered key) queries in one batch");
-    ctx->stat("keydeps.range_key_queries", V);
-
-    // ---- count and emit per piece with the exact-replay scan
-    uint64_t *pe_cnt = ctx->get<uint64_t>("mx_pe_cnt", NP + 1);
-    uint64_t *pe_off = ctx->get<uint64_t>("mx_pe_off", NP + 2);
-    uint32_t *pk_cnt = ctx->get<uint32_t>("mx_pk_cnt", NP + 1);
-    uint32_t *pk_off = ctx->get<uint32_t>("mx_pk_off", NP + 2);
-    uint64_t *etoff = ctx->get<uint64_t>("mx_etoff", (size_t)n + 1);
-    uint32_t *ktoff = ctx->get<uint32_t>("mx_ktoff", (size_t)n + 1);
-    uint64_t Ex = 0, Kx = 0;
-    CfkView v{};
-    uint32_t *qc = ctx->get<uint32_t>("mx_qc", NP * 32);
-    uint4 *prec = ctx->get<uint4>("mx_prec", 2 * NP + 2);
-    if (NP) {
-        const uint32_t pack = ks.rbits <= 31;
-        const bool defer = NP * 32 < 0xFFFFFFFFull;
-        if (!ks.v1) {
-            // with deferral and packed single results the exact-replay scan only ever runs on segments of two or more
-            // entries (pcount / pdefer; pemit replays only lanes of two or more entries)
-            ks.v1view = build_v1_cfk(ctx, n, ks.P, ks.rbits, ks.tl, ks.owner, ks.rank, ks.seg_incl, ks.seg_start, ks.s_rank,
-                                     ks.s_exec, ks.s_info, ks.pair_pos, defer && pack);
-            ks.v1 = true;
-        }
-        v = ks.v1view;
-        launch(ctx, "mx_pieces", k_mx_pieces, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, (uint32_t)R, (const uint64_t *)poff,
-               (const uint32_t *)ra, (const uint32_t *)rowner, (const uint64_t *)rcnt, (const uint64_t *)r_off, rng_off, ks.rank,
-               n, ks.tl, prec);
-        const unsigned gcount = grid_for(NP * 32, BLOCK);
-        const uint32_t dcap = ((gcount + MX_DSLOTS - 1) / MX_DSLOTS) * BLOCK;   // lanes of the blocks of one list
-        uint32_t *dlist = defer ? ctx->get<uint32_t>("mx_dlist", (size_t)MX_DSLOTS * dcap) : nullptr;
-        uint32_t *dcnt = ctx->get<uint32_t>("mx_dcnt", MX_DSLOTS);
-        if (defer) ACC_HIP(hipMemsetAsync(dcnt, 0, MX_DSLOTS * sizeof(uint32_t), st));
-        launch(ctx, "mx_pcount", k_mx_pcount, dim3(gcount), dim3(BLOCK), 0, NP, (const uint4 *)prec, v, pe_cnt, pk_cnt, qc, pack,
-               dlist, dcnt, dcap);
-        if (defer)
-            launch(ctx, "mx_pdefer", k_mx_pdefer, dim3(8, MX_DSLOTS), dim3(BLOCK), 0, (const uint4 *)prec, v, (const uint32_t *)dlist,
-                   (const uint32_t *)dcnt, dcap, pe_cnt, pk_cnt, qc, pack);
-        scan<uint64_t, OpAdd<uint64_t>>(ctx, pe_cnt, pe_off, NP, true, pe_off + NP);
-        scan<uint32_t, OpAdd<uint32_t>>(ctx, pk_cnt, pk_off, NP, true, pk_off + NP);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, pe_off + NP, 8, hipMemcpyDeviceToHost, st));
-        ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, pk_off + NP, 4, hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        Ex = ctx->pinned[0];
-        Kx = ctx->pinned[1] & 0xFFFFFFFFull;
-        if (Ex >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 range-txn KeyDeps entries in one batch");
-    } else {
-        ACC_HIP(hipMemsetAsync(pe_off, 0, 8, st));
-        ACC_HIP(hipMemsetAsync(pk_off, 0, 4, st));
-    }
-    launch(ctx, "mx_toff", k_mx_toff, dim3(grid_for((size_t)n + 1, BLOCK)), dim3(BLOCK), 0, n, rng_off, (const uint64_t *)poff,
-           (const uint64_t *)pe_off, (const uint32_t *)pk_off, etoff, ktoff);
-    MxE mx;
-    mx.deps = ctx->get<uint32_t>("mx_deps", Ex + 1);
-    mx.owner = ctx->get<uint32_t>("mx_owner", Ex + 1);
-    mx.kx_idx = ctx->get<uint32_t>("mx_kx_idx", Kx + 1);
-    mx.kx_end = ctx->get<uint32_t>("mx_kx_end", Kx + 1);
-    mx.kx_code = ctx->get<uint64_t>("mx_kx_code", Kx + 1);
-    uint32_t *ucnt = ctx->get<uint32_t>("mx_ucnt", (size_t)n + 1);
-    uint32_t *idx_of_e = ctx->get<uint32_t>("mx_idx_of_e", Ex + 1);
-    uint32_t *dep_scr = ctx->get<uint32_t>("mx_dep_scr", Ex + 1);
-    MxU mu{ mx.deps, etoff, ks.txn_of_rank, idx_of_e, dep_scr, ucnt };
-    if (Ex) {
-        launch(ctx, "mx_pemit", k_mx_pemit, dim3(grid_for(NP * 32, BLOCK)), dim3(BLOCK), 0, NP, (const uint4 *)prec,
-               (const uint64_t *)seg_key, v, (const uint64_t *)pe_off, (const uint32_t *)pk_off, mx, (const uint32_t *)qc);
-        // per-txn TxnId unions: wave / block tiers, or one (txn, rank) sort when some txn is beyond the block tier
-        MxLists L;
-        static const char *lnames[5] = { "mx_l16", "mx_l32", "mx_l64", "mx_mid_list", "mx_blk_list" };
-        for (int k = 0; k < 5; ++k) L.l[k] = ctx->get<uint32_t>(lnames[k], n);
-        uint32_t *const mid_list = L.l[3], *const blk_list = L.l[4];
-        uint64_t *gst = ctx->get<uint64_t>("mx_gst", 6);
-        ACC_HIP(hipMemsetAsync(gst, 0, 48, st));
-        launch(ctx, "mx_route", k_mx_route, dim3(grid_for(n, (size_t)BLOCK * MX_RT)), dim3(BLOCK), 0, n, (const uint64_t *)etoff, L,
-               gst);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, gst, 48, hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        const uint64_t nblk = ctx->pinned[0], nmid = ctx->pinned[2];
-        const uint64_t nsmall[3] = { ctx->pinned[3], ctx->pinned[4], ctx->pinned[5] };
-        ctx->stat("keydeps.range_block_txns", nblk);
-        ctx->stat("keydeps.range_mid_txns", nmid);
-        if (!ctx->pinned[1]) {
-            if (nsmall[0])
-                launch(ctx, "mx_union_s16", k_mx_union_seg<16>, dim3((unsigned)((nsmall[0] + 4 * WAVES - 1) / (4 * WAVES))),
-                       dim3(BLOCK), 0, (const uint32_t *)L.l[0], (const uint64_t *)(gst + 3), mu);
-            if (nsmall[1])
-                launch(ctx, "mx_union_s32", k_mx_union_seg<32>, dim3((unsigned)((nsmall[1] + 2 * WAVES - 1) / (2 * WAVES))),
-                       dim3(BLOCK), 0, (const uint32_t *)L.l[1], (const uint64_t *)(gst + 4), mu);
-            if (nsmall[2])
-                launch(ctx, "mx_union_s64", k_mx_union_seg<64>, dim3((unsigned)((nsmall[2] + WAVES - 1) / WAVES)),
-                       dim3(BLOCK), 0, (const uint32_t *)L.l[2], (const uint64_t *)(gst + 5), mu);
-            if (nmid)
-                launch(ctx, "mx_union_mid", k_mx_union_mid, dim3((unsigned)((nmid + WAVES - 1) / WAVES)), dim3(BLOCK), 0,
-                       (const uint32_t *)mid_list, (const uint64_t *)gst, mu);
-            if (nblk)
-                launch(ctx, "mx_union_block", k_mx_union_block, dim3((unsigned)nblk), dim3(BLOCK), 0,
-                       (const uint32_t *)blk_list, (const uint64_t *)gst, mu);
-        } else {
-            const int tbits = bits_for(n);
-            if (tbits + ks.rbits > 64) fail(ACC_E_CAP, "batch too large for the (txn, TxnId rank) composite key");
-            uint64_t *skey = ctx->get<uint64_t>("mx_skey", Ex);
-            uint32_t *uflag = ctx->get<uint32_t>("mx_uflag", Ex + 1);
-            uint32_t *ucum = ctx->get<uint32_t>("mx_ucum", Ex + 1);
-            launch(ctx, "mx_owner", k_mx_owner, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint64_t *)etoff, mx.owner);
-            launch(ctx, "mx_sortkeys", k_mx_sortkeys, dim3(grid_for(Ex, BLOCK)), dim3(BLOCK), 0, Ex, (const uint32_t *)mx.deps,
-                   (const uint32_t *)mx.owner, ks.rbits, skey);
-            Sorted so = radix_sort(ctx, "mx_rs", skey, nullptr, Ex, tbits + ks.rbits);
-            launch(ctx, "mx_uflag", k_mx_uflag, dim3(grid_for(Ex, BLOCK)), dim3(BLOCK), 0, Ex, (const uint64_t *)so.keys, uflag);
-            scan<uint32_t, OpAdd<uint32_t>>(ctx, uflag, ucum, Ex, true, ucum + Ex);
-            launch(ctx, "mx_union_sorted", k_mx_union_sorted, dim3(grid_for(Ex, BLOCK)), dim3(BLOCK), 0, Ex,
-                   (const uint64_t *)so.keys, (const uint32_t *)so.vals, (const uint32_t *)uflag, (const uint32_t *)ucum,
-                   (const uint32_t *)mx.owner, ks.rbits, mu);
-            launch(ctx, "mx_ucnt_sorted", k_mx_ucnt_sorted, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint64_t *)etoff,
-                   (const uint32_t *)ucum, ucnt);
-        }
-    }
-
-    // ---- combined offsets and the combined layout
-    MxKv mkv{ kv.arena_off, kv.kd_off, kv.u_off, kv.arena, kv.key_idx, kv.dep_txn };
-    uint64_t *a_cnt = ctx->get<uint64_t>("mx_a_cnt", (size_t)n + 1);
-    uint64_t *kd_cnt = ctx->get<uint64_t>("mx_kd_cnt", (size_t)n + 1);
-    uint64_t *u_cnt = ctx->get<uint64_t>("mx_u_cnt", (size_t)n + 1);
-    launch(ctx, "mx_sizes", k_mx_sizes, dim3(grid_for((size_t)n + 1, BLOCK)), dim3(BLOCK), 0, n, mkv, (const uint64_t *)etoff,
-           (const uint32_t *)ktoff, (const uint32_t *)ucnt, a_cnt, kd_cnt, u_cnt);
-    MxOut o;
-    o.arena_off = ctx->get<uint64_t>("mx_arena_off", (size_t)n + 1);
-    o.kd_off = ctx->get<uint64_t>("mx_kd_off", (size_t)n + 1);
-    o.u_off = ctx->get<uint64_t>("mx_u_off", (size_t)n + 1);
-    uint64_t *mtot = ctx->get<uint64_t>("mx_totals", 3);
-    {   // the three combined offset arrays in one launch (over n + 1: the last element is each total), totals staged
-        const uint64_t *si[3] = { a_cnt, kd_cnt, u_cnt };
-        uint64_t *so[3] = { o.arena_off, o.kd_off, o.u_off }, *stot[3] = { mtot, mtot + 1, mtot + 2 };
-        const size_t sn[3] = { (size_t)n + 1, (size_t)n + 1, (size_t)n + 1 };
-        scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 3, si, so, sn, true, stot);
-    }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, mtot, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t TA = ctx->pinned[0], TK = ctx->pinned[1], TU = ctx->pinned[2];
-    o.arena = ctx->get<int32_t>("mx_arena", TA + 1);
-    o.key_idx = ctx->get<uint32_t>("mx_key_idx", TK + 1);
-    o.kd_key = ctx->get<uint64_t>("mx_kd_key", TK + 1);
-    o.dep_txn = ctx->get<uint32_t>("mx_dep_txn", TU + 1);
-    launch(ctx, "mx_write", k_mx_write, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, mkv, (const uint64_t *)etoff,
-           (const uint32_t *)ktoff, mx, (const uint32_t *)idx_of_e, (const uint32_t *)dep_scr, key_off, key_code, o);
-    ctx->sync();
-    *view = acc_keydeps_view{ n, TA, TK, TU, kv.total_edges + Ex, o.arena_off, o.arena, o.kd_off, o.key_idx, o.u_off,
-                              o.dep_txn, o.kd_key };
-    ctx->kd_view = *view;
-    ctx->kd_valid = true;
+    CfkBuild cb = build_cfk(ctx, in, CfkOpts{});
+    keydeps_of(ctx, cb, view);
 }
 
 // ---------------------------------------------------------------- CFK snapshot for the other scans (recovery.hip)
 
-void cfk_snapshot(acc_ctx *ctx, const acc_batch_in *in, CfkSnapshot &out)
+uint32_t cfk_nseg(acc_ctx *ctx, const CfkBuild &cb)
 {
-    acc_keydeps_view kv{};
-    KdState ks;
-    keydeps_core(ctx, in, &kv, &ks, true);
-    ctx->kd_valid = false;
-    out = CfkSnapshot{};
-    out.n = in->n_txn;
-    out.P = (size_t)in->n_pairs;
-    if (!ks.cfk) return;
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, ks.seg_incl + ks.P - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, cb.seg_incl + cb.P - 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     ctx->sync();
-    const uint32_t nseg = (uint32_t)(ctx->pinned[0] & 0xFFFFFFFFu);   // seg_incl = inclusive count of segment starts
-    const uint64_t *seg_key = ks.seg_key;   // written by k_v2_apply
-    out.cfk = true; out.nseg = nseg; out.rbits = ks.rbits; out.rank = ks.rank; out.txn_of_rank = ks.txn_of_rank;
-    out.seg_start = ks.seg_start; out.seg_key = seg_key; out.s_rank = ks.s_rank; out.s_exec = ks.s_exec;
-    out.s_info = ks.s_info; out.perm = ks.perm; out.tm = ks.tm; out.tl = ks.tl; out.tn = ks.tn; out.em = ks.em;
-    out.el = ks.el; out.en = ks.en; out.key_off = ks.key_off;
+    return (uint32_t)(ctx->pinned[0] & 0xFFFFFFFFu);   // seg_incl = inclusive count of segment starts
+}
+
+CfkBuild cfk_snapshot(acc_ctx *ctx, const acc_batch_in *in)
+{
+    CfkOpts opts;
+    opts.seg_keys = true;
+    CfkBuild cb = build_cfk(ctx, in, opts);
+    ctx->kd_valid = false;
+    if (cb.cfk) cb.nseg = cfk_nseg(ctx, cb);
+    return cb;
 }
 
 }  // namespace acc

@@ -6,6 +6,7 @@
 #include "ctx.hpp"
 
 #include <algorithm>
+#include <vector>
 
 namespace acc {
 
@@ -932,5 +933,26 @@ inline int bits_for(uint64_t max_value)
 {
     return max_value == 0 ? 0 : 64 - __builtin_clzll(max_value);
 }
+
+#ifdef ACC_PHASE_PROF
+// Tuning builds (tools/build_prof.sh): the host side of a kernel's phase counters. prof_arm zeroes the named buffer of
+// `words` counters on `st` and stores its address in the kernel's __device__ pointer `symbol`; prof_read brings the
+// counters back after the launch (a stream sync: a profiled pass is serialised).
+template <class Sym>
+inline unsigned long long *prof_arm(acc_ctx *ctx, const char *name, const Sym &symbol, size_t words, hipStream_t st)
+{
+    unsigned long long *buf = ctx->get<unsigned long long>(name, words);
+    ACC_HIP(hipMemsetAsync(buf, 0, words * sizeof(unsigned long long), st));
+    ACC_HIP(hipMemcpyToSymbolAsync(symbol, &buf, sizeof buf, 0, hipMemcpyHostToDevice, st));
+    return buf;
+}
+inline std::vector<unsigned long long> prof_read(const unsigned long long *buf, size_t words, hipStream_t st)
+{
+    std::vector<unsigned long long> h(words);
+    ACC_HIP(hipMemcpyAsync(h.data(), buf, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipStreamSynchronize(st));
+    return h;
+}
+#endif
 
 }  // namespace acc

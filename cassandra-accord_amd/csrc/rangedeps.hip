@@ -44,17 +44,6 @@ enum : uint64_t {
     ERR_RNG_OFF = 1u << 11,
 };
 
-__device__ __forceinline__ uint32_t witnesses(uint32_t kind)
-{
-    // Kind.witnesses() (primitives/Txn.java:221-236) as a mask over Kind ordinals; LocalOnly is rejected in prep
-    switch (kind) {
-    case 0: case 2: return 1u << 1;
-    case 1: case 3: return (1u << 0) | (1u << 1);
-    case 4:         return (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4);
-    default:        return 0;
-    }
-}
-
 __device__ __forceinline__ uint32_t width_class(uint64_t s, uint64_t e)
 {
     const uint64_t w = e - s;                 // >= 1 after validation
@@ -1259,18 +1248,12 @@ using namespace rd;
 // tuning build: rows for one k_rd_build_seg launch of `blocks` workgroups; rd_prof_print after it (serialises the tier)
 static unsigned long long *rd_prof_arm(acc_ctx *ctx, uint32_t blocks)
 {
-    const size_t rows = (size_t)blocks * WAVES;
-    unsigned long long *buf = ctx->get<unsigned long long>("rd_prof", 8 * rows);
-    ACC_HIP(hipMemsetAsync(buf, 0, 8 * rows * sizeof(unsigned long long), ctx->stream));
-    ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_rd_prof), &buf, sizeof buf, 0, hipMemcpyHostToDevice, ctx->stream));
-    return buf;
+    return prof_arm(ctx, "rd_prof", HIP_SYMBOL(g_rd_prof), 8 * (size_t)blocks * WAVES, ctx->stream);
 }
 static void rd_prof_print(acc_ctx *ctx, const char *tier, unsigned long long *buf, uint32_t blocks)
 {
     const size_t rows = (size_t)blocks * WAVES;
-    std::vector<unsigned long long> h(8 * rows);
-    ACC_HIP(hipMemcpyAsync(h.data(), buf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    ACC_HIP(hipStreamSynchronize(ctx->stream));
+    const std::vector<unsigned long long> h = prof_read(buf, 8 * rows, ctx->stream);
     double sum[4] = {};
     size_t w = 0;
     for (size_t r = 0; r < rows; ++r) {
@@ -1489,16 +1472,12 @@ void rangedeps_batch(acc_ctx *ctx, const acc_range_batch_in *in, acc_rangedeps_v
             v.cap = ctx->bufs["rd_ent"].bytes / sizeof(uint64_t);
             ACC_HIP(hipMemsetAsync(v.cursor, 0, 8, st));
 #ifdef ACC_PHASE_PROF
-            unsigned long long *sbp = ctx->get<unsigned long long>("stab_prof", 8 * (size_t)nsb);
-            ACC_HIP(hipMemsetAsync(sbp, 0, 8 * (size_t)nsb * sizeof(unsigned long long), st));
-            ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_stab_prof), &sbp, sizeof sbp, 0, hipMemcpyHostToDevice, st));
+            unsigned long long *sbp = prof_arm(ctx, "stab_prof", HIP_SYMBOL(g_stab_prof), 8 * (size_t)nsb, st);
 #endif
             launch(ctx, "rd_stab", k_rd_stab, dim3(nsb), dim3(BLOCK), 0, v);
 #ifdef ACC_PHASE_PROF
             {
-                std::vector<unsigned long long> h(8 * (size_t)nsb);
-                ACC_HIP(hipMemcpyAsync(h.data(), sbp, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-                ACC_HIP(hipStreamSynchronize(st));
+                const std::vector<unsigned long long> h = prof_read(sbp, 8 * (size_t)nsb, st);
                 for (int f = 1; f <= 2; ++f) {
                     double sum[6] = {};
                     size_t nb = 0;

@@ -6,7 +6,7 @@
 // a window of the key's txns (before / from / all around X's insert position), a kind test
 // (X.kind().witnessedBy()), a status test and, for WITH / WITHOUT, whether X is in the entry's missing[].
 //
-// Device plan (the CFK snapshot of keydeps.hip, stages 1-3, is shared):
+// Device plan (the CFK snapshot is keydeps.hip's build_cfk, read here as its CfkBuild record):
 //   1. query ranks    X need not be a batch member: binary search of X over the dictionary's distinct timestamps
 //                     gives lo = #timestamps < X and eq = (one equals X), so "TxnId < X" is rank < lo and
 //                     "executeAt <= X" is exec rank < lo + eq.
@@ -17,7 +17,7 @@
 //                     query's entries come out key by key in TxnId order (the map visiting order).
 //   4. build          Deps.Builder: keys with >= 1 entry, one (query, TxnId rank) radix sort for the sorted unique
 //                     TxnIds and each entry's index, the Java keysToTxnIds layout.
-#include "dict.hpp"
+#include "keydeps.hpp"
 
 namespace acc {
 
@@ -31,18 +31,6 @@ enum : uint64_t {
 struct RcParams {
     uint32_t started_at, test_dep, test_status, exec_after;
 };
-
-// Timestamp.compareTo (primitives/Timestamp.java:208-217): msb, then lsb >>> 16 and lsb & 0x1E (both inside
-// lsb & IDENTITY_LSB, unsigned), then signed node
-__device__ __forceinline__ int rc_ts_cmp(uint64_t am, uint64_t al, int32_t an, uint64_t bm, uint64_t bl, int32_t bn)
-{
-    constexpr uint64_t ID = 0xFFFFFFFFFFFF001EULL;
-    if (am != bm) return am < bm ? -1 : 1;
-    const uint64_t a1 = al & ID, b1 = bl & ID;
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (an != bn) return an < bn ? -1 : 1;
-    return 0;
-}
 
 // Kind.witnessedBy() (primitives/Txn.java:247-262) as a mask over Kind ordinals: EphemeralRead -> Nothing,
 // Read -> WsOrSyncPoints, Write -> AnyGloballyVisible, SyncPoint / ExclusiveSyncPoint -> ExclusiveSyncPoints
@@ -127,8 +115,8 @@ __global__ __launch_bounds__(BLOCK) void k_rc_query(uint32_t nq, const uint64_t 
     uint32_t lo = 0, hi = nr;
     auto cmp_rank = [&](uint32_t r) {
         const uint32_t src = s.src_of_rank[r];
-        return src < s.n ? rc_ts_cmp(s.tm[src], s.tl[src], s.tn[src], xm, xl, xn)
-                         : rc_ts_cmp(s.em[src - s.n], s.el[src - s.n], s.en[src - s.n], xm, xl, xn);
+        return src < s.n ? ts_cmp(s.tm[src], s.tl[src], s.tn[src], xm, xl, xn)
+                         : ts_cmp(s.em[src - s.n], s.el[src - s.n], s.en[src - s.n], xm, xl, xn);
     };
     while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (cmp_rank(m) < 0) lo = m + 1; else hi = m; }
     qlo[q] = lo;
@@ -369,8 +357,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     if (rq->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
     hipStream_t st = ctx->stream;
     ctx->kd_valid = false;
-    CfkSnapshot s;
-    cfk_snapshot(ctx, in, s);
+    const CfkBuild s = cfk_snapshot(ctx, in);
     const uint32_t nq = rq->n_query, n = s.n;
     const size_t P = s.P;
     const uint32_t mem = rq->mem;
@@ -394,10 +381,10 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     if (s.cfk) {
         const size_t m = 2 * (size_t)n;
         uint32_t *sor = ctx->get<uint32_t>("rc_src_of_rank", m);
-        launch(ctx, "rc_src_of_rank", k_rc_src_of_rank, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, m, s.rank, sor, nranks);
+        launch(ctx, "rc_src_of_rank", k_rc_src_of_rank, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, m, (const uint32_t *)s.dict.rank, sor, nranks);
         rs.src_of_rank = sor;
         launch(ctx, "rc_missing", k_rc_missing, dim3(grid_for(P, BLOCK)), dim3(BLOCK), 0, P, n, rq->n_missing, moff, mtxn,
-               s.rank, errs);
+               (const uint32_t *)s.dict.rank, errs);
     }
     uint32_t *qlo = ctx->get<uint32_t>("rc_qlo", nq);
     uint8_t *qeq = ctx->get<uint8_t>("rc_qeq", nq);
@@ -406,7 +393,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
            (int)rq->test_kinds, qlo, qeq, qmask, errs);
 
     const RcParams prm{ rq->started_at, rq->test_dep, rq->test_status, (uint32_t)(rq->flags & ACC_FULL_EXECUTES_AFTER) };
-    RcCfk c{ s.seg_key, s.seg_start, s.s_rank, s.s_exec, s.perm, s.rank, moff, mtxn, s.s_info, s.cfk ? s.nseg : 0u,
+    RcCfk c{ s.seg_key, s.seg_start, s.s_rank, s.s_exec, s.perm, s.dict.rank, moff, mtxn, s.s_info, s.cfk ? s.nseg : 0u,
              (uint32_t)P };
     uint32_t *item_q = ctx->get<uint32_t>("rc_item_q", Qp);
     uint32_t *item_a = ctx->get<uint32_t>("rc_item_a", Qp);
@@ -457,7 +444,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     ctx->sync();
     const uint64_t E = ctx->pinned[0], TK = ctx->pinned[1];
     if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 recovery-scan entries in one call");
-    const int rbits = s.rbits;
+    const int rbits = s.dict.rbits;
     const int qbits = bits_for(nq ? nq - 1 : 0);
     if (E && qbits + rbits > 64) fail(ACC_E_CAP, "too many queries for the (query, TxnId rank) composite key");
     uint64_t *ent = ctx->get<uint64_t>("rc_ent", E);
@@ -487,7 +474,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
         if (nq) scan<uint64_t, OpAdd<uint64_t>>(ctx, reinterpret_cast<const uint64_t *>(u_cnt), u_off, nq, true, u_off + nq);
         launch(ctx, "rc_body", k_rc_body, dim3(grid_for(E, BLOCK)), dim3(BLOCK), 0, E, (const uint64_t *)so.keys,
                (const uint32_t *)so.vals, (const uint32_t *)uflag, (const uint32_t *)uincl, rbits, qoff, (const uint64_t *)kpos,
-               (const uint64_t *)epos, (const uint64_t *)arena_off, (const uint64_t *)u_off, s.txn_of_rank, arena, dep_txn);
+               (const uint64_t *)epos, (const uint64_t *)arena_off, (const uint64_t *)u_off, (const uint32_t *)s.dict.txn_of_rank, arena, dep_txn);
     } else {
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
     }
@@ -555,7 +542,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_check(RrCmds c, uint32_t *__restri
     uint64_t e = 0;
     int prev = 1;
     if (i > 0) {
-        prev = rc_ts_cmp(c.tm[i - 1], c.tl[i - 1], c.tn[i - 1], c.tm[i], c.tl[i], c.tn[i]);
+        prev = ts_cmp(c.tm[i - 1], c.tl[i - 1], c.tn[i - 1], c.tm[i], c.tl[i], c.tn[i]);
         if (prev > 0) e |= RR_ERR_ORDER;
     }
     tflag[i] = prev != 0 ? 1u : 0u;
@@ -570,7 +557,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_check(RrCmds c, uint32_t *__restri
     else
         for (uint32_t j = d0; j < d1; ++j) {
             if (!c.dk[j] && c.ds[j] >= c.de[j]) { e |= RR_ERR_DEPS; break; }
-            if (j > d0 && rc_ts_cmp(c.dm[j - 1], c.dl[j - 1], c.dn[j - 1], c.dm[j], c.dl[j], c.dn[j]) > 0) { e |= RR_ERR_DEPS; break; }
+            if (j > d0 && ts_cmp(c.dm[j - 1], c.dl[j - 1], c.dn[j - 1], c.dm[j], c.dl[j], c.dn[j]) > 0) { e |= RR_ERR_DEPS; break; }
         }
     if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
 }
@@ -640,10 +627,10 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
     }
     // lower = #entries with TxnId < X, upper = #entries with TxnId <= X
     uint32_t lo = 0, hi = c.n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (rc_ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
     const uint32_t lower = lo;
     hi = c.n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (rc_ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) <= 0) lo = m + 1; else hi = m; }
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) <= 0) lo = m + 1; else hi = m; }
     const uint32_t upper = lo;
     uint32_t a = 0, w = c.n;
     if (started_at == 0) w = lower;                     // STARTED_BEFORE: txnId < X (:897-898)
@@ -659,10 +646,10 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
 __device__ bool rr_deps_intersect(const RrCmds &c, uint32_t i, uint64_t xm, uint64_t xl, int32_t xn)
 {
     uint32_t lo = c.doff[i], hi = c.doff[i + 1];
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (rc_ts_cmp(c.dm[m], c.dl[m], c.dn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.dm[m], c.dl[m], c.dn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
     const uint32_t r0 = c.roff[i], r1 = c.roff[i + 1];
     const bool ei = c.end_incl != 0;
-    for (uint32_t j = lo; j < c.doff[i + 1] && rc_ts_cmp(c.dm[j], c.dl[j], c.dn[j], xm, xl, xn) == 0; ++j) {
+    for (uint32_t j = lo; j < c.doff[i + 1] && ts_cmp(c.dm[j], c.dl[j], c.dn[j], xm, xl, xn) == 0; ++j) {
         const uint64_t s = c.ds[j];
         if (c.dk[j]) {
             uint32_t a = r0, b = r1;   // first range whose end reaches the key
@@ -699,11 +686,11 @@ __device__ bool rr_command_passes(const RrCmds &c, const RcParams &p, uint32_t i
     if (!(((mask >> ((c.tl[i] >> 1) & 7u)) & 1u))) return false;   // testKind.test(txnId.kind())
     if (hist) {
         if (p.test_status != 0 || p.test_dep != 2) return false;      // historical: ANY_STATUS + ANY_DEPS only
-        if (p.exec_after && rc_ts_cmp(c.tm[i], c.tl[i], c.tn[i], xm, xl, xn) <= 0) return false;   // executeAt = txnId
+        if (p.exec_after && ts_cmp(c.tm[i], c.tl[i], c.tn[i], xm, xl, xn) <= 0) return false;   // executeAt = txnId
         return true;
     }
     if (f & ACC_RCMD_ERASED) return false;
-    const int ex_cmp = rc_ts_cmp(c.em[i], c.el[i], c.en[i], xm, xl, xn);
+    const int ex_cmp = ts_cmp(c.em[i], c.el[i], c.en[i], xm, xl, xn);
     // STARTED_BEFORE falls through into ANY's test (:897-901)
     if (p.started_at != 1 && p.test_dep != 2 && ex_cmp < 0) return false;
     const uint32_t st = c.status[i];

@@ -618,23 +618,13 @@ struct Wo {
     int32_t *out;
 };
 
-// Timestamp.compareTo (primitives/Timestamp.java:208-217): msb, then lsb & IDENTITY_LSB (lowHlc, identity flags), node
-__device__ __forceinline__ int wo_cmp(uint64_t am, uint64_t al, int32_t an, uint64_t bm, uint64_t bl, int32_t bn)
-{
-    if (am != bm) return am < bm ? -1 : 1;
-    const uint64_t a1 = al & 0xFFFFFFFFFFFF001EULL, b1 = bl & 0xFFFFFFFFFFFF001EULL;
-    if (a1 != b1) return a1 < b1 ? -1 : 1;
-    if (an != bn) return an < bn ? -1 : 1;
-    return 0;
-}
-
 __device__ __forceinline__ bool wo_contains(const WoSet &s, uint64_t g, uint64_t m, uint64_t l, int32_t n)
 {
     if (!s.off) return false;
     uint64_t lo = s.off[g], hi = s.off[g + 1];
     while (lo < hi) {
         const uint64_t mid = (lo + hi) >> 1;
-        const int c = wo_cmp(s.m[mid], s.l[mid], s.n[mid], m, l, n);
+        const int c = ts_cmp(s.m[mid], s.l[mid], s.n[mid], m, l, n);
         if (c == 0) return true;
         if (c < 0) lo = mid + 1; else hi = mid;
     }
@@ -649,7 +639,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_set_check(uint32_t ng, WoSet s, ui
     if (q < ng && s.off[q + 1] < s.off[q]) bad = true;
     if (q < ns) {
         const uint64_t g = ub64(s.off, 0, (uint64_t)ng + 1, q) - 1;
-        if (q > s.off[g] && wo_cmp(s.m[q - 1], s.l[q - 1], s.n[q - 1], s.m[q], s.l[q], s.n[q]) >= 0) bad = true;
+        if (q > s.off[g] && ts_cmp(s.m[q - 1], s.l[q - 1], s.n[q - 1], s.m[q], s.l[q], s.n[q]) >= 0) bad = true;
     }
     if (__ballot(bad) && bad) atomicOr((unsigned long long *)err, 4ull);
 }

@@ -1,0 +1,40 @@
+// ts.hpp — the one definition of Timestamp order and of Kind.witnesses() on the device, shared by every path that
+// compares TxnIds / executeAts or filters by kind (keydeps, rangedeps, cfk, cfkdeps, conflicts, recovery, rmm).
+// latest.hip's Ballot compare and wire.hip's Big::cmp are other orders and keep their own code.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace acc {
+
+// Timestamp words in compare order (Timestamp.compareTo, primitives/Timestamp.java:208-217): w0 = msb (unsigned),
+// w1 = lsb & IDENTITY_LSB (lowHlc then identity flags, unsigned compare is exact because lowHlc < 2^48),
+// w2 = node ^ 0x80000000 (signed -> unsigned order). Equal words <=> Timestamp.equals (:244-249).
+constexpr uint64_t IDENTITY_LSB = 0xFFFFFFFFFFFF001EULL;
+
+__device__ __forceinline__ uint64_t ts_w1(uint64_t lsb) { return lsb & IDENTITY_LSB; }
+__device__ __forceinline__ uint64_t ts_w2(int32_t node) { return (uint64_t)((uint32_t)node ^ 0x80000000u); }
+
+// Timestamp.compareTo (primitives/Timestamp.java:208-217): msb, then lsb & IDENTITY_LSB, then the signed node
+__device__ __forceinline__ int ts_cmp(uint64_t am, uint64_t al, int32_t an, uint64_t bm, uint64_t bl, int32_t bn)
+{
+    if (am != bm) return am < bm ? -1 : 1;
+    uint64_t a1 = ts_w1(al), b1 = ts_w1(bl);
+    if (a1 != b1) return a1 < b1 ? -1 : 1;
+    if (an != bn) return an < bn ? -1 : 1;
+    return 0;
+}
+
+// Kind.witnesses() as a bitmask over Kind ordinals (primitives/Txn.java:221-236); 0 = throws.
+__device__ __forceinline__ uint32_t witnesses(uint32_t kind)
+{
+    switch (kind) {
+    case 0: case 2: return 1u << 1;                                   // Read, EphemeralRead -> Ws
+    case 1: case 3: return (1u << 0) | (1u << 1);                     // Write, SyncPoint -> RsOrWs
+    case 4:         return (1u << 0) | (1u << 1) | (1u << 3) | (1u << 4);  // ESP -> AnyGloballyVisible
+    default:        return 0;
+    }
+}
+
+}  // namespace acc

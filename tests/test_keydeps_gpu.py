@@ -384,3 +384,56 @@ def test_txn_with_more_than_65536_keys(ctx):
     k, d, a = o.txn(big)
     assert len(d) > 100 and int(np.max(k)) > 65536
     assert_same(g, o, b.n_txn, ">65536 keys")
+
+
+_PAIR_SORT_CASES = {}
+
+
+def pair_sort_case(mode):
+    """(batch, oracle result) of the smallest batch that reaches pair-sort mode `mode` (csrc/keydeps.hpp PairPlan),
+    built once for both device paths."""
+    import oracle
+    if mode in _PAIR_SORT_CASES:
+        return _PAIR_SORT_CASES[mode]
+    if mode == 3:
+        # TxnId-ordered, 70,000 txns: one Write near the end lists 70,000 keys, every other txn 2 of them, so
+        # bits(n - 1) = 17 and the key-slot bits = 17 (34 > 32: no room for (txn, slot) beside a 32-bit key)
+        rng = np.random.RandomState(0x3A)
+        n = nk = 70_000
+        big = n - 100
+        kinds = rng.choice([W.READ, W.WRITE], size=n)
+        kinds[big] = W.WRITE
+        msb, lsb, node = W.encode_ts(np.ones(n), np.arange(1, n + 1), kinds.astype(np.uint64) << np.uint64(1),
+                                     1 + np.arange(n) % 8)
+        k1 = rng.randint(0, nk, size=n)
+        k2 = (k1 + 1 + rng.randint(0, nk - 1, size=n)) % nk
+        two = np.sort(np.stack([k1, k2], axis=1), axis=1)
+        keys = np.concatenate([two[:big].ravel(), np.arange(nk), two[big + 1:].ravel()])
+        counts = np.full(n, 2)
+        counts[big] = nk
+        off = np.zeros(n + 1, np.uint32)
+        np.cumsum(counts, out=off[1:])
+        b = W.Batch(msb, lsb, node.astype(np.int32), msb.copy(), lsb.copy(), node.astype(np.int32).copy(),
+                    np.full(n, W.PREACCEPTED, np.uint8), off, W.int_key_code(keys))
+    else:
+        b = W.keydeps_batch(3000, 4, 300, 0x1234, "uniform", status_model="model", window=800)
+        if mode in (0, 2):
+            # key codes over the whole u64 range, order preserved: code - 2^31 < 300, so nothing wraps
+            kc = (b.key_code - np.uint64(1 << 31)) * np.uint64(0x003EADBEEF123457) + np.uint64((1 << 63) - (1 << 61))
+            b = W.Batch(b.txn_msb, b.txn_lsb, b.txn_node, b.exe_msb, b.exe_lsb, b.exe_node, b.status, b.key_off, kc)
+        if mode in (1, 2):
+            b = b.permuted(np.random.RandomState(7).permutation(b.n_txn))
+    _PAIR_SORT_CASES[mode] = (b, oracle.keydeps_batch(b))
+    return _PAIR_SORT_CASES[mode]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2, 3, 4])
+def test_pair_sort_modes(ctx, mode):
+    """Each of the five pair sorts of the CFK build (stat keydeps.pair_sort_mode): 0 sorted batch, key codes of more
+    than 32 varying bits; 1 unsorted, key bits + rank bits <= 64; 2 unsorted, beyond 64 (two sorts); 3 sorted,
+    bits(n - 1) + key-slot bits > 32; 4 sorted, (txn, slot) packed beside the key. Every array against the oracle."""
+    b, o = pair_sort_case(mode)
+    g = ctx.calculate_partial_deps(b)
+    assert ctx.stats()["keydeps.pair_sort_mode"] == mode
+    assert g.total_edges == o.total_edges
+    assert_same(g, o, b.n_txn, f"pair sort mode {mode}")
