@@ -970,12 +970,6 @@ __global__ __launch_bounds__(BLOCK) void k_cd_out4(uint32_t nkeys, const uint32_
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_cd_widen(uint32_t n, const uint32_t *__restrict__ in, uint64_t *__restrict__ out)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
 // ---- hot keys: the replay's closed form, data-parallel over a key's updates
 // A key with more than acc_opts.cfk_hot (default 64) updates in the batch is not replayed by one lane: its final state is
 // computed from the update stream directly. Its TxnInfos are every TxnId its snapshot, its updates or their deps name

@@ -31,12 +31,6 @@ __global__ __launch_bounds__(BLOCK) void k_dm_node_word(size_t n, const int32_t 
     if (i < n) out[i] = (uint64_t)((uint32_t)node[i] ^ 0x80000000u);   // Node.Id signed order as unsigned
 }
 
-__global__ __launch_bounds__(BLOCK) void k_dm_widen(size_t n, const uint32_t *__restrict__ in, uint64_t *__restrict__ out)
-{
-    const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
 // Range start < end (Range ctor); err |= 1
 __global__ __launch_bounds__(BLOCK) void k_dm_range_check(size_t n, const uint64_t *__restrict__ s, const uint64_t *__restrict__ e,
                                                           uint64_t *__restrict__ err)
@@ -385,7 +379,7 @@ void merge_half(acc_ctx *ctx, const char *ns, uint32_t mem, uint32_t ng, uint64_
     const uint64_t vand[3] = { ~0ull, IDENTITY_LSB, ~0ull };   // Timestamp.IDENTITY_LSB (Timestamp.java:41)
     DenseRank vd = dense_rank(ctx, "dm_vdict", NV, 3, vw, vand, nullptr, false);
     uint64_t *krank64 = ctx->get<uint64_t>("dm_krank64", NK);
-    launch(ctx, "dm_widen", k_dm_widen, dim3(grid_for(NK, BLOCK)), dim3(BLOCK), 0, (size_t)NK, (const uint32_t *)kd.rank, krank64);
+    launch(ctx, "dm_widen", k_widen_u32, dim3(grid_for(NK, BLOCK)), dim3(BLOCK), 0, (size_t)NK, (const uint32_t *)kd.rank, krank64);
     // ---- the rank-space union (validation included: sorted unique keys / TxnIds, headers, entry ranges)
     acc_merge_in mi{ ACC_MEM_DEVICE, ng, R, grp_off, key_off, krank64, val_off, vd.rank, k2v_off, k2v };
     acc_merge_view mv{};

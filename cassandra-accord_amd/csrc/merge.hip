@@ -226,12 +226,6 @@ __global__ __launch_bounds__(BLOCK) void k_m_fix_headers(uint32_t ng, const uint
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_widen(uint64_t n, const uint32_t *__restrict__ in, uint64_t *__restrict__ out)
-{
-    uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
 // key slot (index into key_code) of every k2v entry position, for the (g, key, value) records
 __global__ __launch_bounds__(BLOCK) void k_m_key_of_slot(uint64_t R, const uint64_t *__restrict__ key_off,
                                                          const uint64_t *__restrict__ val_off,
@@ -832,10 +826,10 @@ void keydeps_merge(acc_ctx *ctx, const acc_merge_in *in, acc_merge_view *view)
         const uint64_t *kw[1] = { key_code };
         DenseRank kd = dense_rank(ctx, "m_kdict", NK, 1, kw, nullptr, nullptr, false);
         uint64_t *kr64 = ctx->get<uint64_t>("m_kr64", NK);
-        launch(ctx, "m_widen", k_widen, dim3(grid_for(NK, BLOCK)), dim3(BLOCK), 0, NK, (const uint32_t *)kd.rank, kr64);
+        launch(ctx, "m_widen", k_widen_u32, dim3(grid_for(NK, BLOCK)), dim3(BLOCK), 0, (size_t)NK, (const uint32_t *)kd.rank, kr64);
         ACC_HIP(hipMemcpyAsync(ctx->pinned, kd.count_dev, 8, hipMemcpyDeviceToHost, st));
         uint64_t *vw64 = ctx->get<uint64_t>("m_vw64", NV);
-        launch(ctx, "m_widen", k_widen, dim3(grid_for(NV, BLOCK)), dim3(BLOCK), 0, NV, txn_rank, vw64);
+        launch(ctx, "m_widen", k_widen_u32, dim3(grid_for(NV, BLOCK)), dim3(BLOCK), 0, (size_t)NV, txn_rank, vw64);
         const uint64_t *vw[1] = { vw64 };
         DenseRank vd = dense_rank(ctx, "m_vdict", NV, 1, vw, nullptr, nullptr, false);
         ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, vd.count_dev, 8, hipMemcpyDeviceToHost, st));

@@ -782,6 +782,21 @@ static __global__ void k_iota(uint32_t *__restrict__ out, size_t n)
     if (i < n) out[i] = (uint32_t)i;
 }
 
+// out[p] = in[p], widened (u32 counts or ranks as keys of a 64-bit sort or scan)
+[[maybe_unused]] static __global__ __launch_bounds__(BLOCK) void k_widen_u32(size_t n, const uint32_t *__restrict__ in, uint64_t *__restrict__ out)
+{
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p < n) out[p] = in[p];
+}
+
+// out[p] = in[perm[p]]
+[[maybe_unused]] static __global__ __launch_bounds__(BLOCK) void k_permute_u64(size_t n, const uint32_t *__restrict__ perm,
+                                                              const uint64_t *__restrict__ in, uint64_t *__restrict__ out)
+{
+    const size_t p = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p < n) out[p] = in[perm[p]];
+}
+
 struct Sorted {
     uint64_t *keys;
     uint32_t *vals;

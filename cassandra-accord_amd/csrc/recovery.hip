@@ -265,12 +265,6 @@ __global__ __launch_bounds__(BLOCK) void k_rc_emit(uint64_t nchunks, RcCfk c, Rc
     }
 }
 
-__global__ __launch_bounds__(BLOCK) void k_rc_widen(uint64_t n, const uint32_t *__restrict__ in, uint64_t *__restrict__ out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = in[i];
-}
-
 __global__ __launch_bounds__(BLOCK) void k_rc_kept(uint32_t Qp, const unsigned long long *__restrict__ item_cnt,
                                                    uint64_t *__restrict__ kept)
 {
@@ -423,7 +417,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     const unsigned gW = (unsigned)((NC + WAVES - 1) / WAVES);
     if (NC) {
         launch(ctx, "rc_count", k_rc_count, dim3(gW), dim3(BLOCK), 0, NC, c, prm, chs, chunk_cnt, item_cnt);
-        launch(ctx, "rc_widen", k_rc_widen, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
+        launch(ctx, "rc_widen", k_widen_u32, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, (size_t)NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt64, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
         ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
@@ -570,13 +564,6 @@ __global__ __launch_bounds__(BLOCK) void k_rr_first(uint32_t n, const uint32_t *
     const uint32_t r = tincl[i] - 1;
     trank[i] = r;
     if (tflag[i]) first_of[r] = i;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rr_gather64(uint64_t n, const uint32_t *__restrict__ perm, const uint64_t *__restrict__ in,
-                                                       uint64_t *__restrict__ out)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) out[i] = in[perm[i]];
 }
 
 // sorted (start, end) -> dictionary flags (a new distinct range)
@@ -920,7 +907,7 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     if (R) {
         Sorted by_end = radix_sort(ctx, "rr_rs1", c.re, nullptr, R, 64);
         uint64_t *sg = ctx->get<uint64_t>("rr_sg", R);
-        launch(ctx, "rr_gather", k_rr_gather64, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, R, (const uint32_t *)by_end.vals, c.rs, sg);
+        launch(ctx, "rr_gather", k_permute_u64, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, (size_t)R, (const uint32_t *)by_end.vals, c.rs, sg);
         Sorted by_start = radix_sort(ctx, "rr_rs2", sg, by_end.vals, R, 64);
         uint32_t *dflag = ctx->get<uint32_t>("rr_dflag", R);
         launch(ctx, "rr_dflag", k_rr_dflag, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, R, (const uint64_t *)by_start.keys,
@@ -968,7 +955,7 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     if (NC) {
         launch(ctx, "rr_count", k_rr_scan<false>, dim3(gW), dim3(BLOCK), 0, NC, c, Q, prm, ch, chunk_cnt,
                (const uint64_t *)nullptr, (uint64_t *)nullptr);
-        launch(ctx, "rr_widen", k_rc_widen, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
+        launch(ctx, "rr_widen", k_widen_u32, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, (size_t)NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt64, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
         ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));

@@ -597,12 +597,6 @@ __global__ __launch_bounds__(BLOCK) void k_json_dict_str(uint64_t nranks, const 
     for (uint32_t k = 0; k < d.len; ++k) dpool[soff[r] + k] = pool[d.value + k];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_json_widen(uint64_t n, const uint32_t *__restrict__ a, uint64_t *__restrict__ b)
-{
-    const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) b[i] = a[i];
-}
-
 static void check_json(uint64_t e)
 {
     if (e & E_OFF) fail(ACC_E_ARG, "doc_off must start at 0, be non-decreasing and end at the byte count");
@@ -680,7 +674,7 @@ void deps_from_json(acc_ctx *ctx, const acc_json_in *in, acc_json_deps_view *vie
                       (const Datum *)dat, dk, dn, dv, dh, dl);
     uint8_t *dpool = nullptr;
     if (NDICT && NS) {
-        launch(ctx, "json_u32_to_u64", k_json_widen, dim3(grid_for(NDICT, BLOCK)), dim3(BLOCK), 0, NDICT, (const uint32_t *)dl, dlen64);
+        launch(ctx, "json_u32_to_u64", k_widen_u32, dim3(grid_for(NDICT, BLOCK)), dim3(BLOCK), 0, (size_t)NDICT, (const uint32_t *)dl, dlen64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, dlen64, dso, NDICT, true, dso + NDICT);
         dpool = ctx->get<uint8_t>("js_dict_pool", NS + 1);
         launch(ctx, "json_dict_str", k_json_dict_str, dim3(grid_for(NDICT, BLOCK)), dim3(BLOCK), 0, NDICT, (const uint32_t *)dr.first,

@@ -62,6 +62,27 @@ def test_block_and_global_tiers(ctx):
     assert_same(g, oracle.rangedeps_batch(rb), "global tier")
 
 
+def test_stab_retry():
+    """The stabbing pass's capacity retry. A fresh context sizes the pair buffer for 16 pairs per query (16 * Q + 1024,
+    plus the arena's half of headroom: 506,016 pairs for this batch's Q = 21,020); the batch emits over 4.6 million
+    (its total_edges after deduplication: 4,641,805), so the first pass only counts and a second one writes. The
+    context remembers the need: the same batch again takes one pass."""
+    import oracle
+    from accord_amd.deps import Context
+    rb = rd_cases.dense(7, n=6000, key_bits=9, max_width_log2=7, ranges_per_txn=3)
+    o = oracle.rangedeps_batch(rb)
+    q = rb.keys.n_pairs + rb.n_ranges
+    assert o.total_edges > (16 * q + 1024) * 3 // 2
+    with Context(0) as c:
+        g1 = c.calculate_partial_range_deps(rb)
+        p1 = c.stats()["rangedeps.stab_passes"]
+        g2 = c.calculate_partial_range_deps(rb)
+        p2 = c.stats()["rangedeps.stab_passes"]
+    assert (p1, p2) == (2, 1)
+    assert_same(g1, o, "stab retry, first call")
+    assert_same(g2, o, "stab retry, second call")
+
+
 @pytest.mark.parametrize("wide", [False, True])
 def test_identical_ranges(ctx, wide):
     """Range commands sharing one stored range (64 keys, widths <= 8: ~500 distinct ranges for ~1,500 range txns), so
