@@ -48,7 +48,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_map_reduce_full", "acc_map_reduce_full_ranges", "acc_latest_deps_merge", "acc_partial_deps_batch",
            "acc_deps_from_json", "acc_deps_to_json",
            "acc_cfk_create", "acc_cfk_destroy", "acc_cfk_update", "acc_cfk_view", "acc_cfk_apply", "acc_cfk_snap_to_batch",
-           "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_max_conflicts",
+           "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_ranges_of", "acc_ranges_with", "acc_ranges_subtract", "acc_ranges_merge_touching", "acc_ranges_select",
@@ -58,7 +58,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
 
 class Opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("cfk_hot", C.c_uint32), ("lv_tier", C.c_uint32),
-                ("lv_chunk", C.c_uint32), ("reserved2", C.c_uint32)]
+                ("lv_chunk", C.c_uint32), ("cfq_wave_cap", C.c_uint32)]
 
 
 class TsCols(C.Structure):
@@ -288,6 +288,11 @@ class CfkBatchView(C.Structure):
     _fields_ = [("batch", BatchIn), ("missing_off", C.c_void_p), ("missing_txn", C.c_void_p), ("n_missing", C.c_uint64)]
 
 
+class CfkQueries(C.Structure):
+    _fields_ = [("n_query", C.c_uint32), ("mem", C.c_uint32), ("n_pairs", C.c_uint64), ("txn_id", TsCols),
+                ("execute_at", TsCols), ("key_off", C.c_void_p), ("key_code", C.c_void_p)]
+
+
 class ConflictsIn(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("n_upd", C.c_uint32), ("end_inclusive", C.c_uint32), ("n_keys", C.c_uint64),
                 ("n_ranges", C.c_uint64), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
@@ -490,6 +495,8 @@ def load():
         L.acc_cfk_state.restype = C.c_int
         L.acc_cfk_missing.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkBatchView)]
         L.acc_cfk_missing.restype = C.c_int
+        L.acc_cfk_keydeps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkQueries), C.POINTER(KeydepsView)]
+        L.acc_cfk_keydeps.restype = C.c_int
         L.acc_maxconflicts_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.acc_maxconflicts_create.restype = C.c_int
         L.acc_maxconflicts_destroy.argtypes = [C.c_void_p]

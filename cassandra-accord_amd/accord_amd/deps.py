@@ -50,11 +50,12 @@ class Context:
 
     def __init__(self, device: int = 0, timing: bool = False, force_replay: bool = False, *, cfk_hot: int = 0,
                  lv_tier: str = "auto", lv_chunk: int = 0, no_window_tier: bool = False, rd_wide_sort: bool = False,
-                 pd_serial: bool = False):
+                 pd_serial: bool = False, cfq_wave_cap: int = 0):
         """acc_opts, fixed for the context's life (the library reads no environment): timing = per-kernel HIP events;
         the rest force code paths for tests (force_replay: the exact replay scan; cfk_hot: the closed-form threshold of
         acc_cfk_apply; lv_tier / lv_chunk: the levelise walk; no_window_tier: the KeyDeps sorting tiers; rd_wide_sort:
-        RangeDeps 64-bit sort keys) or trade speed for memory (pd_serial: acc_partial_deps_batch on one buffer set)."""
+        RangeDeps 64-bit sort keys; cfq_wave_cap: the hit count up to which acc_cfk_keydeps builds a query's KeyDeps in one
+        wave) or trade speed for memory (pd_serial: acc_partial_deps_batch on one buffer set)."""
         self.timing_enabled = timing
         self.device = device
         self._lib = L.load()
@@ -62,7 +63,7 @@ class Context:
         flags = ((L.ACC_OPT_TIMING if timing else 0) | (L.ACC_OPT_FORCE_REPLAY if force_replay else 0) |
                  (L.ACC_OPT_NO_WINDOW_TIER if no_window_tier else 0) | (L.ACC_OPT_RD_WIDE_SORT if rd_wide_sort else 0) |
                  (L.ACC_OPT_PD_SERIAL if pd_serial else 0))
-        opts = L.Opts(flags, 0, int(cfk_hot), self.LV_TIERS[lv_tier], int(lv_chunk), 0)
+        opts = L.Opts(flags, 0, int(cfk_hot), self.LV_TIERS[lv_tier], int(lv_chunk), int(cfq_wave_cap))
         rc = self._lib.acc_create(device, C.byref(opts), C.byref(h))
         if rc != L.ACC_OK:
             raise _ERRORS.get(rc, AccordError)(f"acc_create failed ({rc})")
@@ -1059,11 +1060,49 @@ class CfkStore:
         self.ctx.check(self.ctx._lib.acc_cfk_state(self.ctx.handle, self._h, C.byref(s)))
         return _snap_host(self.ctx, s)
 
+    def keydeps(self, queries: dict) -> "BatchKeyDeps":
+        """PreAccept.calculatePartialDeps' key half for new txns against the resident store (acc_cfk_keydeps):
+        queries = dict(msb, lsb, node: the TxnIds; optional xmsb, xlsb, xnode: their executeAts, default the TxnIds;
+        key_off, key_code: each query's keys, sorted unique). Host arrays in, host out: per query the KeyDeps in the
+        acc_keydeps_view layout, key_idx into the query's keys, kd_key their codes, dep_txn = indices into the store's
+        view (TxnId order). The store is read in place and not modified."""
+        q = queries
+        a = dict(qm=np.ascontiguousarray(q["msb"], dtype=np.uint64), ql=np.ascontiguousarray(q["lsb"], dtype=np.uint64),
+                 qn=np.ascontiguousarray(q["node"], dtype=np.int32), ko=np.ascontiguousarray(q["key_off"], dtype=np.uint32),
+                 kc=np.ascontiguousarray(q["key_code"], dtype=np.uint64))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ex = L.TsCols(None, None, None)
+        if q.get("xmsb") is not None:
+            a.update(xm=np.ascontiguousarray(q["xmsb"], dtype=np.uint64), xl=np.ascontiguousarray(q["xlsb"], dtype=np.uint64),
+                     xn=np.ascontiguousarray(q["xnode"], dtype=np.int32))
+            ex = L.TsCols(p("xm"), p("xl"), p("xn"))
+        n = len(a["qm"])
+        qi = L.CfkQueries(n, L.ACC_MEM_HOST, len(a["kc"]), L.TsCols(p("qm"), p("ql"), p("qn")), ex, p("ko"), p("kc"))
+        view = L.KeydepsView()
+        self.ctx.check(self.ctx._lib.acc_cfk_keydeps(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
+        return self.ctx.copy_out(view, None)
+
     def missing_view(self) -> "L.CfkBatchView":
         """The store's txn-major view with each pair's missing[] as txn indices (device), for cfk_map_reduce_full."""
         bv = L.CfkBatchView()
         self.ctx.check(self.ctx._lib.acc_cfk_missing(self.ctx.handle, self._h, C.byref(bv)))
         return bv
+
+
+def _execute_at_after(part: dict, q: dict):
+    """The executeAt a store holds for each query's txn once `part` is applied: that of the txn's last update in part
+    when its status carries one (ACCEPTED .. APPLIED), else the TxnId (TxnInfo.create, CommandsForKey.java:669-670)."""
+    ident = np.uint64(0xFFFFFFFFFFFF001E)      # Timestamp.equals ignores the other flag bits
+    last = {}
+    for u, (m, l, n, st) in enumerate(zip(part["msb"], part["lsb"], part["node"], part["status"])):
+        if int(st) != 0xFF:                    # 0xFF: a save status without InternalStatus, no change
+            last[(int(m), int(np.uint64(l) & ident), int(n))] = u
+    xm, xl, xn = (np.array(q[k], copy=True) for k in ("msb", "lsb", "node"))
+    for i, (m, l, n) in enumerate(zip(q["msb"], q["lsb"], q["node"])):
+        u = last.get((int(m), int(np.uint64(l) & ident), int(n)))
+        if u is not None and 3 <= int(part["status"][u]) <= 6:
+            xm[i], xl[i], xn[i] = part["xmsb"][u], part["xlsb"][u], part["xnode"][u]
+    return xm, xl, xn
 
 
 class ReplicaStore:
@@ -1081,16 +1120,28 @@ class ReplicaStore:
         self.cfk = CfkStore(ctx)
         self.mc = MaxConflictsMap(ctx, end_inclusive)
 
-    def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool = True) -> dict:
+    def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True) -> dict:
         """part: the batch's updates (cfk_update_stream layout); queries: its PreAccept queries (default: one per
         command first seen in part). Returns dict(propose = MaxConflicts.get + fast path per query, keydeps = the
-        KeyDeps of every txn of the store after the batch, when scan)."""
+        KeyDeps of every txn of the store after the batch, when scan). scan="new": instead keydeps_new = the KeyDeps of
+        the queries alone, scanned against the updated store in place (acc_cfk_keydeps): the rows the whole-store scan
+        would give for them, nothing recomputed for stored txns. A query without executeAt columns (xmsb, xlsb, xnode)
+        takes the executeAt the batch leaves its txn with."""
         from . import workload as W
         q = W.preaccept_queries(part) if queries is None else queries
         out = dict(propose=self.mc.get(q))
         self.mc.update(W.conflicts_updates(part, self.end_inclusive))
         self.cfk.apply_deps(part)
-        if scan:
+        if isinstance(scan, str):
+            if scan != "new":
+                raise ValueError(f"scan must be True, False or 'new', not {scan!r}")
+            nq = dict(msb=q["msb"], lsb=q["lsb"], node=q["node"], key_off=q["part_off"], key_code=q["part_start"])
+            if q.get("xmsb") is not None:
+                nq.update(xmsb=q["xmsb"], xlsb=q["xlsb"], xnode=q["xnode"])
+            else:
+                nq.update(zip(("xmsb", "xlsb", "xnode"), _execute_at_after(part, q)))
+            out["keydeps_new"] = self.cfk.keydeps(nq)
+        elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
         return out
 

@@ -38,6 +38,7 @@ void cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *up);
 void cfk_state(acc_cfk *cfk, acc_cfk_snap *out);
 void cfk_missing(acc_cfk *cfk, acc_cfk_batch_view *out);
 void cfk_free(acc_cfk *cfk);
+void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
 acc_cfk *cfk_new(int device);
 }  // namespace acc
 
@@ -300,6 +301,15 @@ int acc_cfk_missing(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_batch_view *out)
 {
     if (!ctx) return ACC_E_ARG;
     return acc_guard(ctx, [&] { acc::cfk_missing(cfk, out); });
+}
+
+int acc_cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *out_view)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_keydeps(ctx, cfk, q, out_view);
+    });
 }
 
 int acc_keydeps_copy_out(acc_ctx *ctx, acc_keydeps_out *out)

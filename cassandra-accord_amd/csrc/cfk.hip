@@ -14,6 +14,7 @@
 //      + m; key lists merge (a command registers on keys it was not yet on);
 //   4. key offsets by one scan, then every column is written once into the other buffer set, and the sets swap.
 #include "dict.hpp"
+#include "cfkquery.hpp"
 
 struct acc_cfk {
     int device = 0;
@@ -493,6 +494,23 @@ void cfk_missing(acc_cfk *cfk, acc_cfk_batch_view *out)
     out->missing_off = cfk->bmiss_off;
     out->missing_txn = cfk->bmiss_txn;
     out->n_missing = cfk->bnm;
+}
+
+// the resident state as acc_cfk_keydeps scans it (cfkquery.hip)
+CfkResident cfk_resident(const acc_cfk *cfk)
+{
+    const acc_cfk::KeyMajor &k = cfk->km;
+    const acc_cfk::Set &S = cfk->set[cfk->cur];
+    CfkResident r;
+    r.n_txn = cfk->n;
+    r.deps = cfk->deps;
+    r.nk = k.nk;
+    r.key = k.key; r.ent_off = k.ent_off;
+    r.em = k.em; r.el = k.el; r.en = k.en;
+    r.xm = k.xm; r.xl = k.xl; r.xn = k.xn;
+    r.st = k.st;
+    r.tm = S.tm; r.tl = S.tl; r.tn = S.tn;
+    return r;
 }
 
 void cfk_view(acc_cfk *cfk, acc_batch_in *out)

@@ -1,0 +1,639 @@
+// cfkquery.hip — acc_cfk_keydeps: PreAccept.calculatePartialDeps' key half for a batch of NEW transactions against the
+// resident CommandsForKey store (messages/PreAccept.java:107-138, 245-265 -> impl/InMemoryCommandStore.java:257-292 ->
+// CommandsForKey.mapReduceActive, local/CommandsForKey.java:614-650). The reference computes deps for the incoming txn
+// against the live CommandsForKey and recomputes nothing for stored txns; so does this: the store's key-major segments
+// (acc_cfk::km, cfk.hip) are scanned in place, no (key, TxnId) pair of the store is sorted and no segment is rebuilt.
+// Work = the queries' (query, key) pairs + the segment prefixes (entries with TxnId < executeAt) they read.
+//
+//   1. validate   per query: kind, domain, offsets, keys sorted unique (before anything indexes by them)
+//   2. locate     per pair: the key's segment (binary search of km.key), end = first entry with TxnId >= S = executeAt
+//                 (binary search of the segment's TxnId columns), its 256-entry chunks
+//   3. max        one wave per chunk (its pair read from a chunk -> pair map): M = the largest executeAt < S among
+//                 COMMITTED / STABLE / APPLIED Writes of the prefix (closed form of the FAST bisection + the walk down
+//                 to a Write) and the count of committed entries whose executeAt compares equal to S; pairs of several
+//                 chunks fold their chunks' partials (one wave per pair). Two or more ties: ACC_E_STATE (the bisection
+//                 could land on either).
+//   4. count      entries the map function emits: a pair of one chunk (a short prefix, the common case) by the wave
+//                 that just found its M, the chunks of longer pairs one wave each; one device scan gives every offset
+//   5. emit       the same walk; each emitted entry as its index in the store's txn-major view (lower bound of its
+//                 TxnId in the view's sorted TxnId columns), pair by pair in TxnId order
+//   6. build      KeyDeps.Builder per query (utils/RelationMultiMap.java:201-260): queries with at most cfq_wave_cap
+//                 hits sort / unique / look up in one wave's LDS; larger ones go through one radix sort of
+//                 (query, txn index), a unique flag scan and a binary search per hit. Both leave the sorted unique
+//                 txn indices in the hit slots, which one scan compacts into dep_txn.
+//
+// Results live in cq_* buffers only: acc_cfk_apply_deps trades the context's cd_* / cb_* buffers with the store.
+#include "keydeps.hpp"
+#include "cfkquery.hpp"
+
+namespace acc {
+
+namespace cq {
+
+constexpr uint32_t CH = 256;          // segment entries per work chunk: one wave, four per lane
+constexpr uint32_t CAP_MAX = 1024;    // hits of a query the one-wave build tier holds in LDS (u64 each, per wave)
+
+enum : uint64_t { E_KIND_ARG = 1, E_KIND_STATE = 2, E_RANGE = 4, E_OFF = 8, E_KEYS = 16, E_TIE = 32 };
+
+struct Queries {
+    const uint64_t *qm, *ql, *xm, *xl;   // TxnId, executeAt (= TxnId columns when the caller gave none)
+    const int32_t *qn, *xn;
+    const uint32_t *off;                 // [nq + 1]
+    const uint64_t *key;                 // [Qp]
+    uint32_t nq, Qp;
+};
+
+struct Pairs {
+    const uint32_t *q, *a, *w;           // per pair: query, first entry of the segment, prefix length
+    const uint64_t *chunk_off;           // [Qp + 1]
+    const uint32_t *item;                // [chunks] the pair of every chunk
+    uint32_t Qp;
+};
+
+// a chunk's (and, in a pair's first chunk slot, the pair's) M and tie count: f = has M << 31 | min(ties, 3)
+struct Part {
+    uint64_t *m, *l;
+    int32_t *n;
+    uint32_t *f;
+};
+
+struct Best {
+    uint64_t m, l;
+    int32_t n;
+    uint32_t has;
+};
+
+__device__ __forceinline__ bool committed(uint32_t st) { return st >= ACC_ST_COMMITTED && st <= ACC_ST_APPLIED; }
+
+__device__ __forceinline__ void best_take(Best &b, uint64_t m, uint64_t l, int32_t n, uint32_t has)
+{
+    if (has && (!b.has || ts_cmp(m, l, n, b.m, b.l, b.n) > 0)) { b.m = m; b.l = l; b.n = n; b.has = 1; }
+}
+
+__device__ __forceinline__ Best wave_best(Best b)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint64_t om = shfl_xor(b.m, d), ol = shfl_xor(b.l, d);
+        const int32_t on = (int32_t)shfl_xor((uint32_t)b.n, d);
+        const uint32_t oh = shfl_xor(b.has, d);
+        best_take(b, om, ol, on, oh);
+    }
+    return b;
+}
+
+// first index in [0, n) with a[idx] > v
+template <class T>
+__device__ __forceinline__ uint32_t upper(const T *a, uint32_t n, T v)
+{
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
+    return lo;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cq_validate(Queries Q, uint64_t *__restrict__ errs)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= Q.nq) return;
+    uint64_t e = 0;
+    const uint64_t l = Q.ql[q];
+    const uint32_t kind = (uint32_t)(l >> 1) & 7u;
+    if (kind > ACC_KIND_LOCAL_ONLY) e |= E_KIND_ARG;          // Kind.ofOrdinal
+    else if (witnesses(kind) == 0) e |= E_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+    if (l & 1u) e |= E_RANGE;
+    const uint32_t k0 = Q.off[q], k1 = Q.off[q + 1];
+    if (k1 < k0 || k1 > Q.Qp || (q == 0 && k0 != 0) || (q == Q.nq - 1 && k1 != Q.Qp)) e |= E_OFF;
+    else
+        for (uint32_t j = k0 + 1; j < k1; ++j)
+            if (Q.key[j - 1] >= Q.key[j]) { e |= E_KEYS; break; }
+    if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
+}
+
+// per pair: the prefix [a, a + w) of its key's segment the scan visits, whether the entry at its end is a committed
+// entry executing at S (it counts towards the tie rule), and its chunks
+__global__ __launch_bounds__(BLOCK) void k_cq_locate(Queries Q, CfkResident s, uint32_t *__restrict__ pair_q,
+                                                     uint32_t *__restrict__ pair_a, uint32_t *__restrict__ pair_w,
+                                                     uint8_t *__restrict__ pair_t0, uint64_t *__restrict__ chunks)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q.Qp) return;
+    const uint32_t q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
+    uint32_t a = 0, w = 0, t0 = 0;
+    const uint64_t k = Q.key[i];
+    uint32_t lo = 0, hi = s.nk;
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
+    if (lo < s.nk && s.key[lo] == k) {
+        const uint32_t s0 = s.ent_off[lo], s1 = s.ent_off[lo + 1];
+        const uint64_t Sm = Q.xm[q], Sl = Q.xl[q];
+        const int32_t Sn = Q.xn[q];
+        uint32_t x = s0, y = s1;
+        while (x < y) {
+            const uint32_t m = (x + y) >> 1;
+            if (ts_cmp(s.em[m], s.el[m], s.en[m], Sm, Sl, Sn) < 0) x = m + 1; else y = m;
+        }
+        a = s0;
+        w = x - s0;
+        // entries past it have TxnId > S, and executeAt >= TxnId
+        if (x < s1 && committed(s.st[x]) && ts_cmp(s.xm[x], s.xl[x], s.xn[x], Sm, Sl, Sn) == 0) t0 = 1;
+    }
+    pair_q[i] = q;
+    pair_a[i] = a;
+    pair_w[i] = w;
+    pair_t0[i] = (uint8_t)t0;
+    chunks[i] = (w + CH - 1) / CH;
+}
+
+// per pair: the pair of each of its chunks, so a chunk's wave reads its pair instead of searching the offsets
+__global__ __launch_bounds__(BLOCK) void k_cq_items(uint32_t Qp, const uint64_t *__restrict__ chunk_off, uint32_t *__restrict__ item)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Qp) return;
+    for (uint64_t c = chunk_off[i], c1 = chunk_off[i + 1]; c < c1; ++c) item[c] = i;
+}
+
+// the per-entry switch of CommandsForKey.mapReduceActive (:628-647) and the map function's p1 test (PreAccept.java:253-259)
+struct ChunkCtx {
+    uint32_t item, q, base, end, wk, has_m;
+    uint64_t qm, ql, Mm, Ml;
+    int32_t qn, Mn;
+};
+
+__device__ __forceinline__ bool emitted(const CfkResident &s, const ChunkCtx &c, uint32_t e)
+{
+    const uint64_t el = s.el[e];
+    if (!((c.wk >> ((uint32_t)(el >> 1) & 7u)) & 1u)) return false;
+    const uint32_t st = s.st[e];
+    if (st == ACC_ST_TRANSITIVELY_KNOWN || st == ACC_ST_INVALID_OR_TRUNCATED) return false;
+    if (committed(st) && c.has_m && ts_cmp(s.xm[e], s.xl[e], s.xn[e], c.Mm, c.Ml, c.Mn) < 0) return false;
+    if (ts_w1(el) == ts_w1(c.ql) && s.em[e] == c.qm && s.en[e] == c.qn) return false;
+    return true;
+}
+
+__device__ __forceinline__ uint32_t chunk_count(const CfkResident &s, const ChunkCtx &c)
+{
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < CH / 64; ++u) {
+        const uint32_t e = c.base + u * 64 + lane_id();
+        cnt += (uint32_t)__popcll(__ballot(e < c.end && emitted(s, c, e)));
+    }
+    return cnt;
+}
+
+// one wave per chunk: the chunk's part of maxCommittedBefore and of the tie count. A pair of one chunk (a short prefix:
+// the common case) has its M right here, so its wave counts the emitted entries as well (the entries are still in cache).
+__global__ __launch_bounds__(BLOCK) void k_cq_max(uint64_t nchunks, Queries Q, CfkResident s, Pairs P,
+                                                  const uint8_t *__restrict__ pair_t0, Part part, uint64_t *__restrict__ chunk_cnt,
+                                                  uint64_t *__restrict__ errs)
+{
+    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (cw >= nchunks) return;
+    const uint32_t item = P.item[cw];
+    const uint32_t q = P.q[item];
+    const uint64_t c0 = P.chunk_off[item];
+    const uint32_t base = P.a[item] + (uint32_t)(cw - c0) * CH, end = P.a[item] + P.w[item];
+    const uint64_t Sm = Q.xm[q], Sl = Q.xl[q];
+    const int32_t Sn = Q.xn[q];
+    Best b{ 0, 0, 0, 0 };
+    uint32_t ties = cw == c0 ? pair_t0[item] : 0u;
+#pragma unroll
+    for (uint32_t u = 0; u < CH / 64; ++u) {
+        const uint32_t e = base + u * 64 + lane_id();
+        bool tie = false;
+        if (e < end && committed(s.st[e])) {
+            const uint64_t xm = s.xm[e], xl = s.xl[e];
+            const int32_t xn = s.xn[e];
+            const int c = ts_cmp(xm, xl, xn, Sm, Sl, Sn);
+            tie = c == 0;
+            if (c < 0 && ((uint32_t)(s.el[e] >> 1) & 7u) == ACC_KIND_WRITE) best_take(b, xm, xl, xn, 1u);
+        }
+        ties += (uint32_t)__popcll(__ballot(tie));
+    }
+    b = wave_best(b);
+    if (lane_id() == 0) {
+        part.m[cw] = b.m; part.l[cw] = b.l; part.n[cw] = b.n;
+        part.f[cw] = (b.has << 31) | min(ties, 3u);
+        if (ties >= 2) atomicOr((unsigned long long *)errs, (unsigned long long)E_TIE);
+    }
+    if (P.chunk_off[item + 1] - c0 == 1) {
+        ChunkCtx c;
+        c.item = item; c.q = q; c.base = base; c.end = end;
+        c.qm = Q.qm[q]; c.ql = Q.ql[q]; c.qn = Q.qn[q];
+        c.wk = witnesses((uint32_t)(c.ql >> 1) & 7u);
+        c.has_m = b.has; c.Mm = b.m; c.Ml = b.l; c.Mn = b.n;
+        const uint32_t cnt = chunk_count(s, c);
+        if (lane_id() == 0) chunk_cnt[cw] = cnt;
+    }
+}
+
+// one wave per pair of several chunks: the chunks' parts folded into the pair's first chunk slot
+__global__ __launch_bounds__(BLOCK) void k_cq_fold(Pairs P, Part part, uint64_t *__restrict__ errs)
+{
+    const uint32_t i = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (i >= P.Qp) return;
+    const uint64_t c0 = P.chunk_off[i], c1 = P.chunk_off[i + 1];
+    if (c1 - c0 <= 1) return;
+    Best b{ 0, 0, 0, 0 };
+    uint32_t ties = 0;
+    for (uint64_t c = c0 + lane_id(); c < c1; c += 64) {
+        const uint32_t f = part.f[c];
+        best_take(b, part.m[c], part.l[c], part.n[c], f >> 31);
+        ties = min(ties + (f & 3u), 3u);
+    }
+    b = wave_best(b);
+    ties = wave_inclusive(ties, OpAdd<uint32_t>());   // <= 3 * 64
+    ties = shfl_idx(ties, 63);
+    if (lane_id() == 0) {
+        part.m[c0] = b.m; part.l[c0] = b.l; part.n[c0] = b.n;
+        part.f[c0] = (b.has << 31) | min(ties, 3u);
+        if (ties >= 2) atomicOr((unsigned long long *)errs, (unsigned long long)E_TIE);
+    }
+}
+
+// what one wave needs of its chunk's pair and query, M read from the pair's first chunk slot
+__device__ __forceinline__ ChunkCtx chunk_ctx(uint64_t cw, const Queries &Q, const Pairs &P, const Part &part)
+{
+    ChunkCtx c;
+    c.item = P.item[cw];
+    c.q = P.q[c.item];
+    const uint64_t c0 = P.chunk_off[c.item];
+    c.base = P.a[c.item] + (uint32_t)(cw - c0) * CH;
+    c.end = P.a[c.item] + P.w[c.item];
+    c.qm = Q.qm[c.q]; c.ql = Q.ql[c.q]; c.qn = Q.qn[c.q];
+    c.wk = witnesses((uint32_t)(c.ql >> 1) & 7u);
+    c.has_m = part.f[c0] >> 31;
+    c.Mm = part.m[c0]; c.Ml = part.l[c0]; c.Mn = part.n[c0];
+    return c;
+}
+
+// one wave per chunk of a pair of several chunks (k_cq_max counted the others)
+__global__ __launch_bounds__(BLOCK) void k_cq_count(uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
+                                                    uint64_t *__restrict__ chunk_cnt)
+{
+    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (cw >= nchunks) return;
+    const uint32_t item = P.item[cw];
+    if (P.chunk_off[item + 1] - P.chunk_off[item] == 1) return;
+    const ChunkCtx c = chunk_ctx(cw, Q, P, part);
+    const uint32_t cnt = chunk_count(s, c);
+    if (lane_id() == 0) chunk_cnt[cw] = cnt;
+}
+
+// per pair (and the end sentinel): its first hit slot; per pair: does its key get a KeyDeps entry
+__global__ __launch_bounds__(BLOCK) void k_cq_epos(uint32_t Qp, const uint64_t *__restrict__ chunk_off,
+                                                   const uint64_t *__restrict__ chunk_eoff, uint64_t *__restrict__ epos,
+                                                   uint64_t *__restrict__ kept)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i > Qp) return;
+    const uint64_t e0 = chunk_eoff[chunk_off[i]];
+    epos[i] = e0;
+    if (i < Qp) kept[i] = chunk_eoff[chunk_off[i + 1]] > e0 ? 1u : 0u;
+}
+
+// per query (and the end sentinel): arena and key offsets; per query: its hits when they exceed the one-wave tier's cap
+__global__ __launch_bounds__(BLOCK) void k_cq_qoff(uint32_t nq, const uint32_t *__restrict__ qoff, const uint64_t *__restrict__ kpos,
+                                                   const uint64_t *__restrict__ epos, uint32_t cap, uint64_t *__restrict__ arena_off,
+                                                   uint64_t *__restrict__ kd_off, uint64_t *__restrict__ gcnt)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q > nq) return;
+    const uint32_t b = qoff[q];
+    arena_off[q] = kpos[b] + epos[b];
+    kd_off[q] = kpos[b];
+    if (q < nq) {
+        const uint64_t h = epos[qoff[q + 1]] - epos[b];
+        gcnt[q] = h > cap ? h : 0u;
+    }
+}
+
+// the count pass's walk, compacting in position order: every emitted entry as its index in the store's txn-major view
+__global__ __launch_bounds__(BLOCK) void k_cq_emit(uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
+                                                   const uint64_t *__restrict__ chunk_eoff, const uint64_t *__restrict__ epos,
+                                                   const uint64_t *__restrict__ gcnt, const uint64_t *__restrict__ goff, int tb,
+                                                   uint32_t *__restrict__ hit, uint64_t *__restrict__ gkey)
+{
+    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (cw >= nchunks) return;
+    const ChunkCtx c = chunk_ctx(cw, Q, P, part);
+    const uint64_t lt = (1ull << lane_id()) - 1;
+    uint64_t out = chunk_eoff[cw];
+    const bool big = gcnt[c.q] != 0;
+    const uint64_t gbase = big ? goff[c.q] - epos[Q.off[c.q]] : 0;   // hit slot -> slot among the sorting tier's hits
+#pragma unroll
+    for (uint32_t u = 0; u < CH / 64; ++u) {
+        const uint32_t e = c.base + u * 64 + lane_id();
+        const bool m = e < c.end && emitted(s, c, e);
+        const uint64_t bal = __ballot(m);
+        if (m) {
+            const uint64_t xm = s.em[e], xl = s.el[e];
+            const int32_t xn = s.en[e];
+            uint32_t lo = 0, hi = s.n_txn;
+            while (lo < hi) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
+            }
+            const uint64_t p = out + (uint64_t)__popcll(bal & lt);
+            hit[p] = lo;
+            if (big) gkey[gbase + p] = ((uint64_t)c.q << tb) | lo;
+        }
+        out += (uint64_t)__popcll(bal);
+    }
+}
+
+// AbstractBuilder: a key with entries gets its end offset (keys.length + entries through it), its index and its code
+__global__ __launch_bounds__(BLOCK) void k_cq_header(Queries Q, const uint32_t *__restrict__ pair_q, const uint64_t *__restrict__ kpos,
+                                                     const uint64_t *__restrict__ epos, const uint64_t *__restrict__ arena_off,
+                                                     int32_t *__restrict__ arena, uint32_t *__restrict__ key_idx,
+                                                     uint64_t *__restrict__ kd_key)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q.Qp) return;
+    if (epos[i + 1] == epos[i]) return;
+    const uint32_t q = pair_q[i], b = Q.off[q], e = Q.off[q + 1];
+    const uint64_t kd = kpos[e] - kpos[b];
+    arena[arena_off[q] + (kpos[i] - kpos[b])] = (int32_t)(kd + (epos[i + 1] - epos[b]));
+    key_idx[kpos[i]] = i - b;
+    kd_key[kpos[i]] = Q.key[i];
+}
+
+// build tier 1, one wave per query with 1..cap hits: sort in LDS, unique in place, every hit's position by binary search.
+// Leaves the sorted unique txn indices in the query's first hit slots (uflag 1), the rest flagged 0.
+__global__ __launch_bounds__(BLOCK) void k_cq_build_wave(uint32_t nq, const uint32_t *__restrict__ qoff, const uint64_t *__restrict__ epos,
+                                                         const uint64_t *__restrict__ arena_off, const uint64_t *__restrict__ kd_off,
+                                                         uint32_t cap, const uint32_t *__restrict__ hit, int32_t *__restrict__ arena,
+                                                         uint32_t *__restrict__ uflag, uint32_t *__restrict__ uval)
+{
+    __shared__ uint64_t lds[WAVES][CAP_MAX];
+    const uint32_t q = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (q >= nq) return;
+    const uint64_t h0 = epos[qoff[q]];
+    const uint64_t h64 = epos[qoff[q + 1]] - h0;
+    if (h64 == 0 || h64 > cap) return;
+    const uint32_t H = (uint32_t)h64, lane = lane_id();
+    uint64_t *buf = lds[threadIdx.x >> 6];
+    uint32_t n2 = 128;
+    while (n2 < H) n2 <<= 1;
+    for (uint32_t i = lane; i < n2; i += 64) buf[i] = i < H ? (uint64_t)hit[h0 + i] : ~0ull;
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    wave_bitonic_lds(buf, n2);
+    // unique, in place: round r compacts sorted positions [64 r, 64 r + 64) to positions <= their own
+    uint32_t U = 0;
+    uint64_t last = ~0ull;
+    const uint64_t lt = (1ull << lane) - 1;
+    for (uint32_t base = 0; base < H; base += 64) {
+        const uint32_t i = base + lane;
+        const uint64_t a = i < H ? buf[i] : ~0ull;
+        uint64_t prev = shfl_up(a, 1);
+        if (lane == 0) prev = last;
+        const bool f = i < H && a != prev;
+        const uint64_t bal = __ballot(f);
+        __builtin_amdgcn_wave_barrier();
+        if (f) buf[U + (uint32_t)__popcll(bal & lt)] = a;
+        U += (uint32_t)__popcll(bal);
+        last = shfl_idx(a, 63);
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    const uint64_t body = arena_off[q] + (kd_off[q + 1] - kd_off[q]);
+    for (uint32_t i = lane; i < H; i += 64) {
+        const uint64_t v = hit[h0 + i];
+        uint32_t lo = 0, hi = U;
+        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (buf[m] < v) lo = m + 1; else hi = m; }
+        arena[body + i] = (int32_t)lo;
+        uflag[h0 + i] = i < U ? 1u : 0u;
+        uval[h0 + i] = i < U ? (uint32_t)buf[i] : 0u;
+    }
+}
+
+// build tier 2 over the sorted (query, txn index) keys: first occurrences, left in the hit slots of their query
+__global__ __launch_bounds__(BLOCK) void k_cq_guniq(uint64_t G, const uint64_t *__restrict__ sk, int tb, const uint32_t *__restrict__ qoff,
+                                                    const uint64_t *__restrict__ epos, const uint64_t *__restrict__ goff,
+                                                    uint32_t *__restrict__ gflag, uint32_t *__restrict__ uflag, uint32_t *__restrict__ uval)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= G) return;
+    const uint64_t k = sk[g];
+    const uint32_t f = (g == 0 || sk[g - 1] != k) ? 1u : 0u;
+    gflag[g] = f;
+    const uint32_t q = (uint32_t)(k >> tb);
+    const uint64_t p = epos[qoff[q]] + (g - goff[q]);
+    uflag[p] = f;
+    uval[p] = (uint32_t)(k & ((1ull << tb) - 1));
+}
+
+// every sorting-tier hit's index into its query's sorted unique txn indices
+__global__ __launch_bounds__(BLOCK) void k_cq_gbody(uint64_t G, const uint64_t *__restrict__ gkey, const uint64_t *__restrict__ sk,
+                                                    const uint32_t *__restrict__ ginc, int tb, const uint64_t *__restrict__ gcnt,
+                                                    const uint64_t *__restrict__ goff, const uint64_t *__restrict__ arena_off,
+                                                    const uint64_t *__restrict__ kd_off, int32_t *__restrict__ arena)
+{
+    const uint64_t g = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (g >= G) return;
+    const uint64_t k = gkey[g];
+    const uint32_t q = (uint32_t)(k >> tb);
+    const uint64_t g0 = goff[q];
+    uint64_t lo = g0, hi = g0 + gcnt[q];
+    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (sk[m] < k) lo = m + 1; else hi = m; }
+    arena[arena_off[q] + (kd_off[q + 1] - kd_off[q]) + (g - g0)] = (int32_t)(ginc[lo] - ginc[g0]);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cq_deps(uint64_t E, const uint32_t *__restrict__ uflag, const uint32_t *__restrict__ uval,
+                                                   const uint32_t *__restrict__ upos, uint32_t *__restrict__ dep_txn)
+{
+    const uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (p < E && uflag[p]) dep_txn[upos[p]] = uval[p];
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cq_uoff(uint32_t nq, const uint32_t *__restrict__ qoff, const uint64_t *__restrict__ epos,
+                                                   const uint32_t *__restrict__ upos, uint64_t *__restrict__ u_off)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q <= nq) u_off[q] = upos[epos[qoff[q]]];
+}
+
+static void check_cq_errors(uint64_t e)
+{
+    if (e & E_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in a query TxnId");
+    if (e & E_RANGE) fail(ACC_E_ARG, "range-domain queries against the resident store are not supported");
+    if (e & E_OFF) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+    if (e & E_KEYS) fail(ACC_E_ARG, "keys of a query must be sorted and unique (Keys.ofSortedUnique)");
+    if (e & E_KIND_STATE) fail(ACC_E_STATE, "Kind.witnesses(): unhandled kind LocalOnly (AssertionError)");
+    if (e & E_TIE)
+        fail(ACC_E_STATE, "two or more committed entries of one key execute at a query's executeAt: the FAST bisection "
+                          "of committed[] is not determined");
+}
+
+}  // namespace cq
+
+using namespace cq;
+
+void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keydeps_view *view)
+{
+    if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    const CfkResident s = cfk_resident(cfk);
+    if (!s.deps && s.n_txn)
+        fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): it has no key-major CommandsForKey to scan");
+    if (in->n_pairs >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs in one call (>= 2^32 - 1)");
+    hipStream_t st = ctx->stream;
+    ctx->kd_valid = false;
+    const uint32_t nq = in->n_query, Qp = (uint32_t)in->n_pairs, mem = in->mem;
+    uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
+    cap = std::min(cap, CAP_MAX);
+
+    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", (size_t)nq + 1);
+    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", (size_t)nq + 1);
+    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", (size_t)nq + 1);
+    if (nq == 0) {
+        if (Qp) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+        ACC_HIP(hipMemsetAsync(arena_off, 0, 8, st));
+        ACC_HIP(hipMemsetAsync(kd_off, 0, 8, st));
+        ACC_HIP(hipMemsetAsync(u_off, 0, 8, st));
+        ctx->sync();
+        *view = acc_keydeps_view{ 0, 0, 0, 0, 0, arena_off, ctx->get<int32_t>("cq_arena", 1), kd_off,
+                                  ctx->get<uint32_t>("cq_key_idx", 1), u_off, ctx->get<uint32_t>("cq_dep_txn", 1),
+                                  ctx->get<uint64_t>("cq_kd_key", 1) };
+        ctx->kd_view = *view;
+        ctx->kd_valid = true;
+        return;
+    }
+
+    Queries Q{};
+    Q.nq = nq;
+    Q.Qp = Qp;
+    Q.off = stage_in(ctx, "cq_in_off", in->key_off, (size_t)nq + 1, mem);
+    Q.key = stage_in(ctx, "cq_in_key", in->key_code, Qp, mem);
+    Q.qm = stage_in(ctx, "cq_in_qm", in->txn_id.msb, nq, mem);
+    Q.ql = stage_in(ctx, "cq_in_ql", in->txn_id.lsb, nq, mem);
+    Q.qn = stage_in(ctx, "cq_in_qn", in->txn_id.node, nq, mem);
+    if (in->execute_at.msb) {
+        Q.xm = stage_in(ctx, "cq_in_xm", in->execute_at.msb, nq, mem);
+        Q.xl = stage_in(ctx, "cq_in_xl", in->execute_at.lsb, nq, mem);
+        Q.xn = stage_in(ctx, "cq_in_xn", in->execute_at.node, nq, mem);
+    } else {
+        Q.xm = Q.qm; Q.xl = Q.ql; Q.xn = Q.qn;
+    }
+
+    // ---- validate: nothing below indexes by an offset or trusts key order before this has passed
+    uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
+    ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
+    launch(ctx, "cq_validate", k_cq_validate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, errs);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    check_cq_errors(ctx->pinned[0]);
+
+    // ---- locate: prefixes and chunks
+    uint32_t *pair_q = ctx->get<uint32_t>("cq_pair_q", Qp);
+    uint32_t *pair_a = ctx->get<uint32_t>("cq_pair_a", Qp);
+    uint32_t *pair_w = ctx->get<uint32_t>("cq_pair_w", Qp);
+    uint8_t *pair_t0 = ctx->get<uint8_t>("cq_pair_t0", Qp);
+    uint64_t *chunks = ctx->get<uint64_t>("cq_chunks", Qp);
+    uint64_t *chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
+    if (Qp) {
+        launch(ctx, "cq_locate", k_cq_locate, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, pair_q, pair_a, pair_w, pair_t0, chunks);
+        scan<uint64_t, OpAdd<uint64_t>>(ctx, chunks, chunk_off, Qp, true, chunk_off + Qp);
+    } else {
+        ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
+    }
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_off + Qp, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    const uint64_t NC = ctx->pinned[0];
+    if (NC >= (1ull << 33)) fail(ACC_E_CAP, "the queries read too many segment entries in one call (>= 2^41)");
+    uint32_t *chunk_item = ctx->get<uint32_t>("cq_chunk_item", NC);
+    const Pairs P{ pair_q, pair_a, pair_w, chunk_off, chunk_item, Qp };
+
+    // ---- M and the tie count, the count pass, every offset
+    Part part{ ctx->get<uint64_t>("cq_part_m", NC), ctx->get<uint64_t>("cq_part_l", NC), ctx->get<int32_t>("cq_part_n", NC),
+               ctx->get<uint32_t>("cq_part_f", NC) };
+    uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
+    uint64_t *chunk_eoff = ctx->get<uint64_t>("cq_chunk_eoff", NC + 1);
+    const unsigned gW = (unsigned)((NC + WAVES - 1) / WAVES);
+    if (NC) {
+        launch(ctx, "cq_items", k_cq_items, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off, chunk_item);
+        launch(ctx, "cq_max", k_cq_max, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, (const uint8_t *)pair_t0, part, chunk_cnt, errs);
+        launch(ctx, "cq_fold", k_cq_fold, dim3(grid_for(Qp, WAVES)), dim3(BLOCK), 0, P, part, errs);
+        launch(ctx, "cq_count", k_cq_count, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, part, chunk_cnt);
+        scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt, chunk_eoff, NC, true, chunk_eoff + NC);
+    } else {
+        ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
+    }
+    uint64_t *epos = ctx->get<uint64_t>("cq_epos", (size_t)Qp + 1);
+    uint64_t *kept = ctx->get<uint64_t>("cq_kept", Qp);
+    uint64_t *kpos = ctx->get<uint64_t>("cq_kpos", (size_t)Qp + 1);
+    launch(ctx, "cq_epos", k_cq_epos, dim3(grid_for((size_t)Qp + 1, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off,
+           (const uint64_t *)chunk_eoff, epos, kept);
+    if (Qp) scan<uint64_t, OpAdd<uint64_t>>(ctx, kept, kpos, Qp, true, kpos + Qp);
+    else ACC_HIP(hipMemsetAsync(kpos, 0, 8, st));
+    uint64_t *gcnt = ctx->get<uint64_t>("cq_gcnt", nq);
+    uint64_t *goff = ctx->get<uint64_t>("cq_goff", (size_t)nq + 1);
+    launch(ctx, "cq_qoff", k_cq_qoff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)kpos,
+           (const uint64_t *)epos, cap, arena_off, kd_off, gcnt);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, gcnt, goff, nq, true, goff + nq);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, chunk_eoff + NC, 8, hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 2, kpos + Qp, 8, hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 3, goff + nq, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    check_cq_errors(ctx->pinned[0]);
+    const uint64_t E = ctx->pinned[1], TK = ctx->pinned[2], G = ctx->pinned[3];
+    if (TK + E >= 0x7FFFFFFFull) fail(ACC_E_CAP, "more than 2^31-1 KeyDeps ints in one call");
+
+    // ---- emit
+    const int tb = std::max(1, bits_for(s.n_txn ? s.n_txn - 1 : 0));
+    const int qbits = bits_for(nq - 1);
+    uint32_t *hit = ctx->get<uint32_t>("cq_hit", E);
+    uint64_t *gkey = ctx->get<uint64_t>("cq_gkey", G);
+    if (E)
+        launch(ctx, "cq_emit", k_cq_emit, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, part, (const uint64_t *)chunk_eoff,
+               (const uint64_t *)epos, (const uint64_t *)gcnt, (const uint64_t *)goff, tb, hit, gkey);
+
+    // ---- KeyDeps.Builder layout
+    int32_t *arena = ctx->get<int32_t>("cq_arena", TK + E);
+    uint32_t *key_idx = ctx->get<uint32_t>("cq_key_idx", TK);
+    uint64_t *kd_key = ctx->get<uint64_t>("cq_kd_key", TK);
+    uint32_t *dep_txn = ctx->get<uint32_t>("cq_dep_txn", E);
+    uint64_t TU = 0;
+    if (E) {
+        launch(ctx, "cq_header", k_cq_header, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, (const uint32_t *)pair_q,
+               (const uint64_t *)kpos, (const uint64_t *)epos, (const uint64_t *)arena_off, arena, key_idx, kd_key);
+        uint32_t *uflag = ctx->get<uint32_t>("cq_uflag", E);
+        uint32_t *uval = ctx->get<uint32_t>("cq_uval", E);
+        uint32_t *upos = ctx->get<uint32_t>("cq_upos", E + 1);
+        if (E > G)
+            launch(ctx, "cq_build_wave", k_cq_build_wave, dim3(grid_for(nq, WAVES)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)epos,
+                   (const uint64_t *)arena_off, (const uint64_t *)kd_off, cap, (const uint32_t *)hit, arena, uflag, uval);
+        if (G) {
+            const uint64_t *sk = radix_sort_keys(ctx, "cq_rs", gkey, G, 0, tb + qbits);
+            uint32_t *gflag = ctx->get<uint32_t>("cq_gflag", G);
+            uint32_t *ginc = ctx->get<uint32_t>("cq_ginc", G);
+            launch(ctx, "cq_guniq", k_cq_guniq, dim3(grid_for(G, BLOCK)), dim3(BLOCK), 0, G, sk, tb, Q.off, (const uint64_t *)epos,
+                   (const uint64_t *)goff, gflag, uflag, uval);
+            scan<uint32_t, OpAdd<uint32_t>>(ctx, gflag, ginc, G, false);
+            launch(ctx, "cq_gbody", k_cq_gbody, dim3(grid_for(G, BLOCK)), dim3(BLOCK), 0, G, (const uint64_t *)gkey, sk,
+                   (const uint32_t *)ginc, tb, (const uint64_t *)gcnt, (const uint64_t *)goff, (const uint64_t *)arena_off,
+                   (const uint64_t *)kd_off, arena);
+        }
+        scan<uint32_t, OpAdd<uint32_t>>(ctx, uflag, upos, E, true, upos + E);
+        launch(ctx, "cq_deps", k_cq_deps, dim3(grid_for(E, BLOCK)), dim3(BLOCK), 0, E, (const uint32_t *)uflag, (const uint32_t *)uval,
+               (const uint32_t *)upos, dep_txn);
+        launch(ctx, "cq_uoff", k_cq_uoff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)epos,
+               (const uint32_t *)upos, u_off);
+        ACC_HIP(hipMemcpyAsync(ctx->pinned, upos + E, 4, hipMemcpyDeviceToHost, st));
+        ctx->sync();
+        TU = ctx->pinned[0] & 0xFFFFFFFFull;
+    } else {
+        ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
+        ctx->sync();
+    }
+    ctx->stat("cfq.pairs", Qp);
+    ctx->stat("cfq.chunks", NC);
+    ctx->stat("cfq.hits", E);
+    ctx->stat("cfq.sorted_hits", G);
+    *view = acc_keydeps_view{ nq, TK + E, TK, TU, E, arena_off, arena, kd_off, key_idx, u_off, dep_txn, kd_key };
+    ctx->kd_view = *view;
+    ctx->kd_valid = true;
+}
+
+}  // namespace acc

@@ -128,7 +128,8 @@ typedef struct acc_opts {
                                  of the replay (0: 64) */
     uint32_t lv_tier;         /* ACC_LV_* */
     uint32_t lv_chunk;        /* the LDS walk's dependency chunk cap in entries (0: as large as the LDS allows) */
-    uint32_t reserved2;
+    uint32_t cfq_wave_cap;    /* acc_cfk_keydeps: queries with at most this many emitted entries build their KeyDeps in
+                                 one wave's LDS, larger ones through the sorting tier (0: 1024; clamped to 1..1024) */
 } acc_opts;
 
 /* Timestamp / TxnId as three SoA columns: Timestamp.msb, Timestamp.lsb, Node.Id.id
@@ -889,6 +890,38 @@ int  acc_cfk_snap_to_batch(acc_ctx *ctx, const acc_cfk_snap *snap, acc_cfk_batch
 int  acc_cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *updates);
 int  acc_cfk_state(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_snap *out);
 int  acc_cfk_missing(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_batch_view *out);
+
+/* PreAccept.calculatePartialDeps' key half for a batch of queries against a resident store: query q runs
+ * CommandsForKey.mapReduceActive (local/CommandsForKey.java:614-650) on the CFK of each of its keys with
+ * startedBefore = execute_at[q], testKind = txn_id[q].kind().witnesses(), and txn_id[q] itself never emitted.
+ * The store (one that acc_cfk_apply_deps maintains, or an empty one) is read in place: its key-major segments are
+ * scanned where they lie, nothing of it is re-sorted and the deps of stored txns are not recomputed, so the work is
+ * the queries' (query, key) pairs plus the segment prefixes (entries with TxnId < executeAt) they read.
+ * Per (query, key) pair, with S = the query's executeAt: end = the first entry with TxnId >= S (Timestamp.compareTo);
+ * M = the largest executeAt among the entries below end that are COMMITTED / STABLE / APPLIED Writes with executeAt < S
+ * (the closed form of the FAST bisection of committed[] and the walk down to a Write; none: nothing is pruned); every
+ * entry below end is emitted whose kind the query's kind witnesses, whose status is neither TRANSITIVELY_KNOWN nor
+ * INVALID_OR_TRUNCATED, that is not a committed-class entry with executeAt < M, and whose TxnId is not
+ * Timestamp.equals to the query's. A key without a CFK contributes nothing.
+ * Tie rule: the closed form and the reference's bisection can differ only when two or more committed-class entries of
+ * one key have an executeAt compare-equal to S (the bisection may land on either); the reference never holds such a
+ * state (executeAt is unique per command). A pair that sees two or more fails the call with ACC_E_STATE.
+ * The result is an acc_keydeps_view with n_txn = n_query in the acc_keydeps_batch layout per query: key_idx into the
+ * query's own keys (keys with at least one dep), kd_key their codes, dep_txn = KeyDeps.txnIds as indices into the
+ * store's acc_cfk_view txn order, ascending. It is the context's last KeyDeps result (acc_keydeps_copy_out copies it),
+ * valid until the next compute call on the context. The store is not modified. Errors: a range-domain or
+ * invalid-kind TxnId, offsets that do not start at 0 / decrease / end off n_pairs, unsorted or duplicate keys of a
+ * query: ACC_E_ARG; a LocalOnly TxnId (Kind.witnesses() throws) or a non-empty status-only store (acc_cfk_update):
+ * ACC_E_STATE. An empty store, n_query == 0 and queries without keys give empty results. */
+typedef struct acc_cfk_queries {
+    uint32_t    n_query, mem;      /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t    n_pairs;           /* key_off[n_query] */
+    acc_ts_cols txn_id;            /* [n_query] any TxnId, store member or not */
+    acc_ts_cols execute_at;        /* [n_query]; execute_at.msb == NULL: executeAt = txnId for every query */
+    const uint32_t *key_off;       /* [n_query+1] */
+    const uint64_t *key_code;      /* [n_pairs] sorted unique per query (Keys) */
+} acc_cfk_queries;
+int  acc_cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *out_view);
 
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
