@@ -102,6 +102,7 @@ void ctx_destroy(acc_ctx *ctx)
         if (ctx->join_ev[i]) (void)hipEventDestroy(ctx->join_ev[i]);
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
+    if (ctx->lane_ev) (void)hipEventDestroy(ctx->lane_ev);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     acc_ctx *child = ctx->child;

@@ -56,11 +56,20 @@ struct acc_ctx {
     static constexpr int NAUX = 3;
     hipStream_t aux[NAUX] = {};
     hipEvent_t fork_ev = nullptr, join_ev[NAUX] = {};
+    hipEvent_t lane_ev = nullptr;          // a point of the side lane (aux[0]) the main stream waits for: lane_mark / lane_wait
+    bool lane_open = false;                // between lane_fork and lane_join: aux[0] may be running beside the main stream
     hipStream_t launch_stream = nullptr;   // where acc::launch enqueues (nullptr = `stream`)
     // decoupled look-back scan status, double buffered: each scan zeroes the words the previous scan dirtied in
-    // the other buffer, so no memset launch precedes a scan (acc::scan, prims.hpp)
-    size_t scan_cap = 0, scan_dirty[2] = {0, 0};
-    int scan_par = 0;
+    // the other buffer, so no memset launch precedes a scan (acc::scan, prims.hpp). Stream order is what makes the
+    // double buffering safe, so there is one set per stream that may scan: [0] the context stream, [1] the side lane
+    // (aux[0], while launch_stream points at it), which runs scans and sorts beside the main stream's kernels.
+    struct ScanState {
+        size_t cap = 0, dirty[2] = {0, 0};
+        int par = 0;
+    };
+    ScanState scan_st[2];
+    // the lane a scan or sort helper is being enqueued on: 0 main, 1 the side lane, -1 a stream that may not scan
+    int scan_lane() const { return !launch_stream ? 0 : launch_stream == aux[0] ? 1 : -1; }
     // one-sweep radix status words per sort tag, double buffered the same way (acc::radix_sort, prims.hpp)
     struct OsState {
         size_t cap = 0, dirty[2] = {0, 0};
@@ -76,8 +85,8 @@ struct acc_ctx {
     std::unordered_map<std::string, acc::Buf> bufs;
     // buffers replaced by a larger allocation while kernels may still read them: freed at the next sync
     std::vector<void *> graveyard;
-    // pinned host staging for small read-backs (sizes, flags); words [PINNED_SLOTS, +512) hold slotted partials
-    static constexpr size_t PINNED_WORDS = 1024, PINNED_SLOTS = 512;
+    // pinned host staging for small read-backs (sizes, flags); words [PINNED_SLOTS, +1024) hold slotted partials
+    static constexpr size_t PINNED_WORDS = 1536, PINNED_SLOTS = 512;
     uint64_t *pinned = nullptr;
     // timing
     std::vector<acc::TimingSlot> slots;
@@ -203,6 +212,7 @@ struct acc_ctx {
     {
         if (!fork_ev) {
             ACC_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+            ACC_HIP(hipEventCreateWithFlags(&lane_ev, hipEventDisableTiming));
             for (int i = 0; i < NAUX; ++i) {
                 ACC_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
                 ACC_HIP(hipEventCreateWithFlags(&join_ev[i], hipEventDisableTiming));
@@ -221,6 +231,15 @@ struct acc_ctx {
         launch_stream = nullptr;
     }
 
+    // The side lane: aux[0] forked from the main stream to run a chain of small kernels, scans and sorts beside it, across
+    // host syncs of the main stream (sync() below frees nothing while the lane is open). lane_join is a no-op when no
+    // lane is open, so every consumer of a stage that may have left one open calls it before it reads the lane's
+    // results or reuses its buffers. The main stream can wait for an intermediate point too (lane_mark / lane_wait).
+    void lane_fork() { fork(1); lane_open = true; }
+    void lane_join() { if (lane_open) { join(1); lane_open = false; } }
+    void lane_mark() { ACC_HIP(hipEventRecord(lane_ev, aux[0])); }
+    void lane_wait() { ACC_HIP(hipStreamWaitEvent(stream, lane_ev, 0)); }
+
     // after a failure inside a call: no launch is left pointing at a side stream, and every stream is drained before
     // the next call (or a sync) frees graveyard buffers a side-stream kernel may still read. Errors are ignored here:
     // the failure being reported is the first one.
@@ -230,11 +249,17 @@ struct acc_ctx {
         for (int i = 0; i < NAUX; ++i)
             if (aux[i]) (void)hipStreamSynchronize(aux[i]);
         if (stream) (void)hipStreamSynchronize(stream);
+        lane_open = false;   // drained above
     }
 
+    // Synchronises the main stream only. Replaced buffers are freed and timing events resolved only when no side lane
+    // is open: a lane kernel may still read a buffer the lane itself has replaced since, and its events may be
+    // pending. Both wait for the first sync after lane_join. (The write tiers' fork / join in keydeps_runs has no sync
+    // between the two.)
     void sync()
     {
         ACC_HIP(hipStreamSynchronize(stream));
+        if (lane_open) return;
         for (void *p : graveyard) ACC_HIP(hipFree(p));
         graveyard.clear();
         if (!pending.empty()) resolve_timing();

@@ -15,7 +15,13 @@ struct Dictionary {
     bool batch_sorted = false;        // txns given in TxnId order
     bool fast = false;                // sorted-batch dictionary taken
     bool ties_pending = false;        // its executeAt-tie check (g[6]) is still to be read by the caller
-    uint64_t hg[8] = {};              // prep words: ts word masks [0..2], key mask [3], errors [4], unsorted [5]
+    uint64_t hg[8] = {};              // prep words: ts word masks [0..2], key mask [3], errors [4], unsorted [5],
+                                      // OR of the key counts [6], executeAts that differ from their TxnId [7]
+    uint64_t nbc = 0;                 // prep: keys of the bumped committed txns (ts.hpp) = entries of the bumped committed list
+    bool fast_ok = false;             // prep: the sorted-batch dictionary applies
+    // the sorted-batch dictionary's sorted bumped executeAts (valid while fast): txn of the k-th smallest = bsrc[sb_vals[k]]
+    uint32_t nb = 0;
+    const uint32_t *sb_vals = nullptr, *bsrc = nullptr;
 };
 
 // Dense order ranks of n composite keys of nw (1..3) u64 words, most significant first, compared unsigned after
@@ -32,8 +38,18 @@ DenseRank dense_rank(acc_ctx *ctx, const char *tag, size_t n, int nw, const uint
                      const uint64_t *xor_mask, bool want_first);
 
 // key_off/key_code: the key-domain part (P pairs); owner[P] receives the txn of every pair; g[8] scratch words.
-// the prep / dictionary flag words: g[0..7], then the prep pass's slotted partials (64 slots x 8 words), zeroed by one fill
-constexpr size_t PREP_G_WORDS = 8 + 64 * 8;
+// the prep / dictionary flag words: g[0..7], then the prep pass's slotted partials (PREP_SLOTS rows of PREP_ROW words, nine
+// of them used), zeroed by one fill
+constexpr uint32_t PREP_SLOTS = 64, PREP_ROW = 16;
+constexpr size_t PREP_G_WORDS = 8 + (size_t)PREP_SLOTS * PREP_ROW;
+// prep_dictionary = prep_batch (the prep pass and its host sync: validation, the masks, sortedness, out.fast_ok, out.nbc;
+// allocates the rank arrays) + build_dictionary (the ranks; enqueued on ctx->cur(): a caller that has work independent
+// of the ranks runs the sorted-batch dictionary on the side lane beside it, which needs out.fast_ok and defer_ties).
+void prep_batch(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
+                const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status, const uint32_t *key_off,
+                const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out);
+void build_dictionary(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
+                      const uint64_t *em, const uint64_t *el, const int32_t *en, uint64_t *g, Dictionary &out, bool defer_ties);
 void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
                      const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status,
                      const uint32_t *key_off, const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out,

@@ -208,8 +208,8 @@ __device__ __forceinline__ void block_or_n(uint64_t (&v)[NW], uint64_t *dst)
 // owner[], key order within a txn (Keys.ofSortedUnique), the key-code varying-bit mask. Pair indices are bounded by P
 // (a malformed key_off is reported, never followed out of bounds). One chunk of BLOCK txns per block (full occupancy:
 // a few resident blocks per CU left every chunk's HBM round trips exposed, 0.11 ms for config 2); each block folds its
-// words into one of PREP_SLOTS slot rows of g (same-address atomics serialise at the L2) and the host ORs the rows.
-constexpr uint32_t PREP_SLOTS = 64;   // 64 x 8 words = ctx->pinned's slot area
+// words into one of PREP_SLOTS slot rows of g (same-address atomics serialise at the L2) and the host ORs the rows
+// (words 0-6) or adds them up (7: the bumped txns; 8: the keys of the bumped committed txns, ts.hpp).
 
 __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const uint64_t *__restrict__ tm, const uint64_t *__restrict__ tl,
                                                     const int32_t *__restrict__ tn, const uint64_t *__restrict__ em,
@@ -222,6 +222,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const 
     const uint32_t tid = threadIdx.x;
     uint64_t m0 = 0, m1 = 0, m2 = 0, km = 0, errs = 0, unsorted = 0, ornk = 0;
     uint32_t differs = 0;
+    unsigned long long bckeys = 0;
     const uint64_t r0 = tm[0], r1 = ts_w1(tl[0]), r2 = ts_w2(tn[0]);
     const uint64_t kref = P ? key_code[0] : 0;
     if (blockIdx.x == 0 && tid == 0 && key_off[n] != P) errs |= ERR_KEY_TOTAL;
@@ -231,6 +232,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const 
         __syncthreads();   // the previous chunk's ko[] readers are done
         if (tid < tcnt) ko[tid] = key_off[t];
         if (tid == 0) ko[tcnt] = key_off[t0 + tcnt];
+        bool bc = false;
         if (t < n) {
             // executeAt != txnId (Timestamp.equals): these are the only executeAts the sorted-batch
             // dictionary has to sort
@@ -244,12 +246,16 @@ __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const 
             uint32_t kind = (uint32_t)(tl[t] >> 1) & 7u;
             if (kind >= 6) errs |= ERR_BAD_KIND;
             else if (kind == 5) errs |= ERR_LOCAL_ONLY;
+            bc = bumped_committed(status[t], kind, d);
             if (t + 1 < n && ts_cmp(tm[t], tl[t], tn[t], tm[t + 1], tl[t + 1], tn[t + 1]) >= 0) unsorted = 1;
         }
         __syncthreads();
         const bool bad = tid < tcnt && ko[tid + 1] < ko[tid];
         if (bad) errs |= ERR_KEY_OFF;
-        else if (tid < tcnt) ornk |= ko[tid + 1] - ko[tid];   // bounds the keys per txn (pair packing)
+        else if (tid < tcnt) {
+            ornk |= ko[tid + 1] - ko[tid];   // bounds the keys per txn (pair packing)
+            if (bc) bckeys += ko[tid + 1] - ko[tid];
+        }
         if (!__syncthreads_or(bad ? 1 : 0) && P) {
             const uint32_t a = (uint32_t)min((size_t)ko[0], P), b = (uint32_t)min((size_t)ko[tcnt], P);
             for (uint32_t j = a + tid; j < b; j += BLOCK) {
@@ -262,15 +268,18 @@ __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const 
             }
         }
     }
-    uint64_t *gs = g + 8 * (blockIdx.x % PREP_SLOTS);
+    uint64_t *gs = g + PREP_ROW * (blockIdx.x % PREP_SLOTS);
     uint64_t v[7] = { m0, m1, m2, km, errs, unsorted, ornk };
     block_or_n<7>(v, gs);
     __shared__ uint32_t s_nd;
-    if (tid == 0) s_nd = 0;
+    __shared__ unsigned long long s_bck;
+    if (tid == 0) { s_nd = 0; s_bck = 0; }
     __syncthreads();
     if (differs) atomicAdd(&s_nd, differs);
+    if (bckeys) atomicAdd(&s_bck, bckeys);
     __syncthreads();
     if (tid == 0 && s_nd) atomicAdd((unsigned long long *)&gs[7], (unsigned long long)s_nd);
+    if (tid == 0 && s_bck) atomicAdd((unsigned long long *)&gs[8], s_bck);
 }
 
 // ---- sorted-batch dictionary: TxnIds are already in order; only the differing executeAts (B) are sorted.
@@ -514,44 +523,64 @@ void redo_general_dictionary(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const
 // timestamps (rank[t] = TxnId of t, rank[n + t] = executeAt of t; equal <=> Timestamp.equals). Shared by the
 // KeyDeps and RangeDeps paths. Throws the first validation error. defer_ties: the sorted-batch dictionary's tie check
 // (g[6]) is left to the caller's next sync (out.ties_pending), which then calls redo_general_dictionary on a tie.
-void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
-                     const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status,
-                     const uint32_t *key_off, const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out,
-                     bool defer_ties)
+//
+// prep_batch: the prep pass and its host sync. The rank arrays are allocated here, so the kernels a caller enqueues
+// before build_dictionary can already take their addresses.
+void prep_batch(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
+                const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status, const uint32_t *key_off,
+                const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out)
 {
     hipStream_t st = ctx->stream;
-    // ---- 1. prep
-    static_assert(8 * PREP_SLOTS <= acc_ctx::PINNED_WORDS - acc_ctx::PINNED_SLOTS, "slot rows fit the pinned area");
-    static_assert(PREP_G_WORDS == 8 + 8 * PREP_SLOTS, "g and the prep slots share one buffer");
+    static_assert(PREP_ROW * PREP_SLOTS <= acc_ctx::PINNED_WORDS - acc_ctx::PINNED_SLOTS, "slot rows fit the pinned area");
+    static_assert(PREP_G_WORDS == 8 + PREP_ROW * PREP_SLOTS, "g and the prep slots share one buffer");
+    static_assert(PREP_ROW >= 9, "seven OR words and two sums per slot row");
     uint64_t *gslots = g + 8;   // g has PREP_G_WORDS words
     ACC_HIP(hipMemsetAsync(g, 0, PREP_G_WORDS * sizeof(uint64_t), st));
     uint32_t *bflag = ctx->get<uint32_t>("bflag", n);
     launch(ctx, "prep_txn", k_prep_txn, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, P, tm, tl, tn, em, el, en, status,
            key_off, key_code, owner, bflag, gslots);
-    // the last key_off entry must equal P
-    uint64_t hg[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint64_t hg[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }, nbc = 0;
     {
         // (key_off[n] == P is checked by the kernel: ERR_KEY_TOTAL)
         uint64_t *hs = ctx->pinned + acc_ctx::PINNED_SLOTS;
-        ACC_HIP(hipMemcpyAsync(hs, gslots, 8 * PREP_SLOTS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        ACC_HIP(hipMemcpyAsync(hs, gslots, PREP_ROW * PREP_SLOTS * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         ctx->sync();
         for (uint32_t r = 0; r < PREP_SLOTS; ++r) {
-            for (int w = 0; w < 7; ++w) hg[w] |= hs[8 * r + w];
-            hg[7] += hs[8 * r + 7];
+            for (int w = 0; w < 7; ++w) hg[w] |= hs[PREP_ROW * r + w];
+            hg[7] += hs[PREP_ROW * r + 7];
+            nbc += hs[PREP_ROW * r + 8];
         }
     }
     check_errors(hg[4]);
-    const bool batch_sorted = hg[5] == 0;
-
-    // ---- 2. dictionary: order ranks over 2N timestamps
     const TsPlan plan = ts_plan(hg);
     const size_t m = 2 * (size_t)n;
-    uint32_t *rank = ctx->get<uint32_t>("rank", m);
-    uint32_t *txn_of_rank = ctx->get<uint32_t>("txn_of_rank", m);
-    const uint64_t nb = hg[7];
-    bool fast_dict = batch_sorted && plan.b0 + plan.b1 + plan.b2 <= 64 && nb < n;
+    out.rank = ctx->get<uint32_t>("rank", m);
+    out.txn_of_rank = ctx->get<uint32_t>("txn_of_rank", m);
+    out.rbits = bits_for(m - 1);
+    out.batch_sorted = hg[5] == 0;
+    out.fast_ok = out.batch_sorted && plan.b0 + plan.b1 + plan.b2 <= 64 && hg[7] < n;
+    out.fast = false;
+    out.ties_pending = false;
+    out.nbc = nbc;
+    out.nb = 0;
+    out.sb_vals = out.bsrc = nullptr;
+    memcpy(out.hg, hg, sizeof hg);
+}
+
+// build_dictionary: order ranks over the 2N timestamps of a batch prep_batch has passed. Enqueued on ctx->cur(); the
+// sorted-batch dictionary with defer_ties has no host sync, so it can run on the side lane (the other cases use the
+// context stream: the general sort and the undeferred tie check sync it).
+void build_dictionary(acc_ctx *ctx, uint32_t n, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
+                      const uint64_t *em, const uint64_t *el, const int32_t *en, uint64_t *g, Dictionary &out, bool defer_ties)
+{
+    const TsPlan plan = ts_plan(out.hg);
+    uint32_t *rank = out.rank, *txn_of_rank = out.txn_of_rank;
+    const uint64_t nb = out.hg[7];
+    bool fast_dict = out.fast_ok;
+    if (ctx->launch_stream && !(fast_dict && defer_ties)) fail(ACC_E_STATE, "internal: this dictionary syncs the context stream");
     out.ties_pending = false;
     if (fast_dict) {
+        const uint32_t *bflag = ctx->get<uint32_t>("bflag", n);
         uint32_t *bidx = ctx->get<uint32_t>("bidx", (size_t)n + 1);
         scan<uint32_t, OpAdd<uint32_t>>(ctx, bflag, bidx, n, true, bidx + n);
         uint64_t *bkey = ctx->get<uint64_t>("bkey", nb);
@@ -564,9 +593,13 @@ void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, con
                (const uint64_t *)tkey, (const uint64_t *)sb.keys, (const uint32_t *)bflag, rank, txn_of_rank, g);
         launch(ctx, "rank_b_sorted", k_rank_b_sorted, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, n, (uint32_t)nb,
                (const uint64_t *)tkey, (const uint64_t *)sb.keys, (const uint32_t *)sb.vals, (const uint32_t *)bsrc, rank, g);
+        out.nb = (uint32_t)nb;
+        out.sb_vals = sb.vals;
+        out.bsrc = bsrc;
         if (defer_ties) {
             out.ties_pending = true;
         } else {
+            hipStream_t st = ctx->stream;
             ACC_HIP(hipMemcpyAsync(ctx->pinned, g + 6, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
             ctx->sync();
             if (ctx->pinned[0]) {   // an executeAt equals another timestamp: dense ranks need the general dictionary
@@ -577,12 +610,16 @@ void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, con
     }
     if (!fast_dict) general_ranks(ctx, n, tm, tl, tn, em, el, en, plan, g, rank, txn_of_rank);
     ctx->stat("keydeps.fast_dictionary", fast_dict ? 1 : 0);
-    out.rank = rank;
-    out.txn_of_rank = txn_of_rank;
-    out.rbits = bits_for(m - 1);
-    out.batch_sorted = batch_sorted;
     out.fast = fast_dict;
-    memcpy(out.hg, hg, sizeof hg);
+}
+
+void prep_dictionary(acc_ctx *ctx, uint32_t n, size_t P, const uint64_t *tm, const uint64_t *tl, const int32_t *tn,
+                     const uint64_t *em, const uint64_t *el, const int32_t *en, const uint8_t *status,
+                     const uint32_t *key_off, const uint64_t *key_code, uint32_t *owner, uint64_t *g, Dictionary &out,
+                     bool defer_ties)
+{
+    prep_batch(ctx, n, P, tm, tl, tn, em, el, en, status, key_off, key_code, owner, g, out);
+    build_dictionary(ctx, n, tm, tl, tn, em, el, en, g, out, defer_ties);
 }
 
 }  // namespace acc

@@ -10,7 +10,10 @@
 //   build_cfk      argument checks; staged inputs; prep and the order-rank dictionary of the 2N timestamps
 //                  (dictionary.hip); the pairs sorted by (key, TxnId rank) by one of five sorts (sort_pairs); the
 //                  columns: one segment per key = CommandsForKey.txns, tile counts, the run-based scan's class lists,
-//                  rank directory and bumped committed list (build_columns).
+//                  rank directory and bumped committed list (build_columns). A TxnId-ordered batch with a packed pair
+//                  sort runs the dictionary, and behind it the bumped committed (segment, executeAt) order made from
+//                  the txn side (bc_from_txns), on the context's side lane beside the pair sort; the lane is still
+//                  open when build_cfk returns and the next stage joins it (acc_ctx::lane_join).
 //   keydeps_runs   no executeAt ties: a query is a union of sorted runs over its segment (see "v2" below). Count pass
 //                  (a record per pair), mark pass and scans (result sizes, stream txns / big txns), then the stream
 //                  passes on the context stream while the big txns' tiers (window, sorting, wave) run on a side
@@ -22,8 +25,9 @@
 // keys and the sparse compaction, then its range part. cfk_snapshot = build_cfk alone.
 //
 // Host syncs of a tie-free batch, and what each one reads:
-//   1. prep (prep_dictionary): the varying-bit masks of the timestamp and key words, validation errors, sortedness,
-//      the number of executeAts that differ from their TxnId: they pick the dictionary and the pair sort.
+//   1. prep (prep_batch): the varying-bit masks of the timestamp and key words, validation errors, sortedness,
+//      the number of executeAts that differ from their TxnId, the keys of the bumped committed txns: they pick the
+//      dictionary and the pair sort and size the side lane's sort.
 //   2. columns (build_columns): the tile totals (bumped committed count: the size of the next sort), the error and
 //      tie words of the dictionary kernels. A sorted-batch dictionary that met a tie is redone by the general sort
 //      here and the columns built again (one more sync).
@@ -147,12 +151,7 @@ constexpr int NCNT = 9;    // 6 list counts, bumped-committed count, last-unbump
 constexpr int NRD = 8;     // the rank directory's columns (all but the segment count)
 __device__ __forceinline__ bool cnt_is_max(int q) { return q == 7; }
 
-// Kind class for the Kinds predicates (Txn.java:140-152): Read 0, Write 1, SyncPoint/ExclusiveSyncPoint 2;
-// EphemeralRead and LocalOnly are witnessed by no predicate (3 = none).
-__device__ __forceinline__ uint32_t kind_class(uint32_t kind)
-{
-    return kind == 0 ? 0u : kind == 1 ? 1u : (kind == 3 || kind == 4) ? 2u : 3u;
-}
+// (kind_class: ts.hpp)
 // witness mask over kinds -> mask over classes
 __device__ __forceinline__ uint32_t wk_classes(uint32_t wk)
 {
@@ -434,7 +433,7 @@ __global__ __launch_bounds__(BLOCK) void k_v2_apply(size_t P, const uint32_t *__
             o.bc_exec[b] = e;
             o.bc_kind[b] = (uint8_t)(s_info[p] >> 3);
             o.bc_pm_in[b] = ((uint64_t)seg << 32) | ((uint64_t)e + 1);
-            o.bc_key[b] = ((uint64_t)seg << rbits) | e;
+            if (o.bc_key) o.bc_key[b] = ((uint64_t)seg << rbits) | e;
         }
         if ((code[i] >> 4) & 1u) run[7] = (uint32_t)p + 1;
         if (p == P - 1 && P % RD_W == 0) {
@@ -457,6 +456,63 @@ __global__ __launch_bounds__(BLOCK) void k_v2_bcs_cols(uint32_t nbc, const uint6
     if (i >= nbc) return;
     bcs_exec[i] = (uint32_t)(skeys[i] & rmask);
     lastw_in[i] = bc_kind[svals[i]] == 1 ? i + 1 : 0;
+}
+
+// ---- the same order from the txn side (build_cfk, on the side lane beside the pair sort). Segments are the distinct
+// compacted key codes in ascending order, so (segment, executeAt) order = (compacted key code, executeAt rank) order,
+// and "bumped committed" is a per-txn property (ts.hpp): the list can be made from the batch's txn-major arrays before
+// any pair is sorted. The bumped txns are taken in executeAt order (the dictionary has sorted them), each contributing
+// its keys, so a stable sort by key code alone finishes the order: keys of (kc << (rbits + 1)) | execRank << 1 | isWrite
+// sorted on the kc bits, the low bits riding along.
+
+// cnt[k] = key count of the k-th bumped txn in executeAt order when it is bumped committed, else 0; bt[k] = that txn
+__global__ __launch_bounds__(BLOCK) void k_bcx_counts(uint32_t nb, const uint32_t *__restrict__ sperm, const uint32_t *__restrict__ bsrc,
+                                                      const uint8_t *__restrict__ status, const uint64_t *__restrict__ tl,
+                                                      const uint32_t *__restrict__ key_off, uint32_t *__restrict__ bt,
+                                                      uint32_t *__restrict__ cnt)
+{
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    if (k >= nb) return;
+    const uint32_t t = bsrc[sperm[k]];
+    bt[k] = t;
+    cnt[k] = bumped_committed(status[t], (uint32_t)(tl[t] >> 1) & 7u, true) ? key_off[t + 1] - key_off[t] : 0u;
+}
+
+// One block per BLOCK bumped txns: their output range [off[k0], off[k0 + cnt]) is walked coalesced, each entry finding its
+// txn in the block's offsets in LDS (txns that contribute nothing share their offset with the next one). off[] is the
+// exclusive scan of k_bcx_counts' counts (off[nb] = the total = the prep pass's count, the size of out).
+__global__ __launch_bounds__(BLOCK) void k_bcx_expand(uint32_t nb, uint32_t n, const uint32_t *__restrict__ bt, const uint32_t *__restrict__ off,
+                                                      const uint32_t *__restrict__ key_off, const uint64_t *__restrict__ key_code,
+                                                      const uint32_t *__restrict__ rank, const uint64_t *__restrict__ tl, Runs rk,
+                                                      int rbits, uint64_t nout, uint64_t *__restrict__ out)
+{
+    __shared__ uint32_t so[BLOCK + 1], st[BLOCK];
+    const uint32_t tid = threadIdx.x, k0 = blockIdx.x * BLOCK;
+    if (k0 >= nb) return;
+    const uint32_t cnt = min((uint32_t)BLOCK, nb - k0);
+    if (tid < cnt) { so[tid] = off[k0 + tid]; st[tid] = bt[k0 + tid]; }
+    if (tid == 0) so[cnt] = off[k0 + cnt];
+    __syncthreads();
+    const uint64_t hi = min((uint64_t)so[cnt], nout);
+    for (uint64_t j = (uint64_t)so[0] + tid; j < hi; j += BLOCK) {
+        uint32_t lo = 0, up = cnt;   // last i with so[i] <= j
+        while (up - lo > 1) { const uint32_t m = (lo + up) >> 1; if (so[m] <= j) lo = m; else up = m; }
+        const uint32_t t = st[lo];
+        const uint64_t kc = pext_runs(key_code[key_off[t] + (uint32_t)(j - so[lo])], rk);
+        const uint64_t w = ((uint32_t)(tl[t] >> 1) & 7u) == 1u ? 1u : 0u;
+        out[j] = (kc << (rbits + 1)) | ((uint64_t)rank[n + t] << 1) | w;
+    }
+}
+
+// k_v2_bcs_cols for the keys above: the executeAt rank and the Write bit are in the sorted key itself
+__global__ __launch_bounds__(BLOCK) void k_bcx_cols(uint32_t nbc, const uint64_t *__restrict__ skeys, uint64_t rmask,
+                                                    uint32_t *__restrict__ bcs_exec, uint64_t *__restrict__ lastw_in)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= nbc) return;
+    const uint64_t x = skeys[i];
+    bcs_exec[i] = (uint32_t)((x >> 1) & rmask);
+    lastw_in[i] = (x & 1u) ? i + 1 : 0;
 }
 
 __device__ __forceinline__ uint32_t rd_cbc(const uint4 *rdir, uint32_t p);   // the rank directory, below
@@ -2426,6 +2482,47 @@ __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_
 
 // ---------------------------------------------------------------- host orchestration
 
+// What the prep words fix of the pair sort, before any rank exists: the key compaction, the rank and slot widths, and
+// whether the sort will be a packed keys-only one (modes 3 and 4, which sort_pairs then tells apart).
+static bool pair_plan(CfkBuild &cb)
+{
+    PairPlan &pp = cb.pp;
+    pp.rk = make_runs(cb.dict.hg[3]);
+    pp.rbits = cb.dict.rbits;
+    pp.sb = std::max(1, bits_for(cb.dict.hg[6]));   // bounds the key slot within a txn (hg[6] = OR of the key counts)
+    return cb.dict.batch_sorted && pp.rk.bits <= 32;
+}
+
+// The bumped committed entries in (segment, executeAt) order from the txn side (kernels k_bcx_*), enqueued on the side
+// lane behind the sorted-batch dictionary: counts of the bumped txns in executeAt order, their exclusive scan, the expand,
+// a keys-only sort on the key-code bits (nbc from the prep sync sizes it), the columns and the nearest-Write scan.
+static void bc_from_txns(acc_ctx *ctx, CfkBuild &cb)
+{
+    const uint32_t n = cb.n, nb = cb.dict.nb;
+    const uint64_t nbc = cb.dict.nbc;
+    const PairPlan &pp = cb.pp;
+    const int rbits = cb.dict.rbits;
+    uint32_t *bt = ctx->get<uint32_t>("bcx_txn", nb);
+    uint32_t *cnt = ctx->get<uint32_t>("bcx_cnt", nb);
+    uint32_t *off = ctx->get<uint32_t>("bcx_off", (size_t)nb + 1);
+    uint64_t *keys = ctx->get<uint64_t>("bcx_key", nbc);
+    cb.bcs_exec = ctx->get<uint32_t>("v2_bcs_exec", nbc);
+    uint64_t *lw_in = ctx->get<uint64_t>("v2_bcs_lw_in64", nbc);
+    cb.bcs_lastw64 = ctx->get<uint64_t>("v2_bcs_lastw64", nbc);
+    cb.bc_side = true;
+    if (nbc == 0) return;   // (then nothing reads the arrays: every segment's range of the list is empty)
+    ctx->stat("keydeps.bc_sort_passes", (uint64_t)((pp.rk.bits + 7) / 8));
+    launch(ctx, "bcx_counts", k_bcx_counts, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, nb, cb.dict.sb_vals, cb.dict.bsrc, cb.status,
+           cb.tl, cb.key_off, bt, cnt);
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, cnt, off, nb, true, off + nb);
+    launch(ctx, "bcx_expand", k_bcx_expand, dim3(grid_for(nb, BLOCK)), dim3(BLOCK), 0, nb, n, (const uint32_t *)bt,
+           (const uint32_t *)off, cb.key_off, cb.key_code, (const uint32_t *)cb.dict.rank, cb.tl, pp.rk, rbits, nbc, keys);
+    const uint64_t *sk = radix_sort_keys(ctx, "rs_bcx", keys, nbc, rbits + 1, pp.rk.bits);
+    launch(ctx, "bcx_cols", k_bcx_cols, dim3(grid_for(nbc, BLOCK)), dim3(BLOCK), 0, (uint32_t)nbc, sk,
+           (uint64_t)((1ull << rbits) - 1), cb.bcs_exec, lw_in);
+    scan<uint64_t, OpMax<uint64_t>>(ctx, lw_in, cb.bcs_lastw64, nbc, false);
+}
+
 // The sorted pairs of a batch: the permutation (entry -> input pair index) and what the column kernels have to know
 // about the sort that made it. The mode itself is in the record's PairPlan.
 struct PairSort {
@@ -2441,7 +2538,9 @@ struct PairSort {
 // Pairs sorted by (key, TxnId rank) by the cheapest of five sorts (PairPlan::mode, stat keydeps.pair_sort_mode):
 // a batch given in TxnId order needs no rank in the sort key, and a key code of few varying bits leaves room to pack
 // the pair index (or the pair's txn and slot) into a keys-only sort.
-static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb)
+// keys_only (modes 3 and 4, the dictionary still running on the side lane): the pair-key launch reads no rank and leaves
+// the txn records to k_txn_info, which build_columns launches once the ranks are there.
+static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb, bool keys_only)
 {
     const uint32_t n = cb.n;
     const size_t P = cb.P;
@@ -2449,10 +2548,7 @@ static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb)
     const uint64_t *key_code = cb.key_code;
     const uint32_t *owner = cb.owner, *rank = cb.dict.rank;
     const int rbits = cb.dict.rbits;
-    PairPlan &pp = cb.pp;
-    pp.rk = make_runs(cb.dict.hg[3]);
-    pp.rbits = rbits;
-    pp.sb = std::max(1, bits_for(cb.dict.hg[6]));   // bounds the key slot within a txn (hg[6] = OR of the key counts)
+    PairPlan &pp = cb.pp;   // rk, rbits, sb: pair_plan
     uint64_t *pkey = ctx->get<uint64_t>("pair_key", P);
     const unsigned gP = grid_for(P, BLOCK);
     PairSort s;
@@ -2465,10 +2561,10 @@ static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb)
         const bool m4 = bits_for((uint64_t)n - 1) + pp.sb <= 32;
         pp.mode = m4 ? 4 : 3;
         TxnInfoArgs ti;   // the txn records (k_txn_info) by the same launch: the ranks are final unless ties turn up
-        ti.n = n; ti.status = cb.status; ti.tl = cb.tl; ti.tinfo = cb.tinfo; ti.bigflag = cb.bigflag;
+        if (!keys_only) { ti.n = n; ti.status = cb.status; ti.tl = cb.tl; ti.tinfo = cb.tinfo; ti.bigflag = cb.bigflag; }
         launch(ctx, "pair_keys", k_pair_keys, dim3(grid_for(std::max<size_t>(P, n), BLOCK)), dim3(BLOCK), 0, P, key_code,
                owner, key_off, rank, (const uint32_t *)nullptr, pp, 0, pkey, ti);
-        s.tinfo_done = true;
+        s.tinfo_done = !keys_only;
         const uint64_t *sp = radix_sort_keys(ctx, "rs_pair", pkey, P, 32, pp.rk.bits);
         uint32_t *perm = ctx->get<uint32_t>("pair_perm", P + V2_ITEMS);
         if (m4) s.sp_m4 = sp;
@@ -2502,7 +2598,9 @@ static PairSort sort_pairs(acc_ctx *ctx, CfkBuild &cb)
 // The rank-dependent columns of the CFK (txn records, the gather into (key, TxnId) order, tile counts, the run-based
 // scan's column set), then the build's host sync: ctx->pinned receives the tile totals, g[4..6] as staged by
 // k_v2_apply, and the bumped-query count. Run again when the deferred tie check finds the sorted-batch ranks invalid.
-static void build_columns(acc_ctx *ctx, CfkBuild &cb, const PairSort &s, bool tinfo_done)
+// lane_open (first run of a build that forked the side lane): the main stream waits for the ranks before the txn records.
+// The lane stays open across the build's sync (acc_ctx::sync frees nothing meanwhile).
+static void build_columns(acc_ctx *ctx, CfkBuild &cb, const PairSort &s, bool tinfo_done, bool lane_open)
 {
     const uint32_t n = cb.n;
     const size_t P = cb.P;
@@ -2516,6 +2614,7 @@ static void build_columns(acc_ctx *ctx, CfkBuild &cb, const PairSort &s, bool ti
     uint32_t *totals = ctx->get<uint32_t>("v2_totals", 16);
     uint64_t rk_mask = 0;   // the bits the key compaction keeps (k_v2_apply rebuilds segment key codes from them)
     for (int r = 0; r < pp.rk.n; ++r) rk_mask |= (pp.rk.len[r] >= 64 ? ~0ull : ((1ull << pp.rk.len[r]) - 1)) << pp.rk.lo[r];
+    if (lane_open) ctx->lane_wait();
     if (!tinfo_done)
         launch(ctx, "txn_info", k_txn_info, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, rank, cb.status, cb.tl, cb.key_off,
                cb.tinfo, cb.bigflag);
@@ -2587,13 +2686,31 @@ CfkBuild build_cfk(acc_ctx *ctx, const acc_batch_in *in, CfkOpts opts)
     cb.g = ctx->get<uint64_t>("g", PREP_G_WORDS);
     cb.owner = ctx->get<uint32_t>("owner", P);
     // the sorted-batch dictionary's tie check is read at the columns' sync below (one host sync fewer)
-    prep_dictionary(ctx, n, P, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.status, cb.key_off, cb.key_code, cb.owner, cb.g,
-                    cb.dict, true);
+    prep_batch(ctx, n, P, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.status, cb.key_off, cb.key_code, cb.owner, cb.g, cb.dict);
+    // A TxnId-ordered batch whose pair sort packs its keys (modes 3, 4) reads no rank until the txn records are written:
+    // the sorted-batch dictionary, and behind it the bumped committed order made from the txn side, run on the side lane
+    // (aux[0]) while the context stream sorts the pairs. The main stream waits for the ranks in build_columns; the lane
+    // itself is still open when build_cfk returns and is joined by whoever comes next (keydeps_runs ahead of its count
+    // pass, keydeps_of ahead of the replay, cfk_snapshot, the tie branch below), so its tail runs under the build's host
+    // sync. A failure in between leaves the lane to acc_ctx::recover. Every other case keeps one stream.
+    const bool overlap = pair_plan(cb) && cb.dict.fast_ok && cb.pp.rk.bits + cb.dict.rbits + 1 <= 64;
+    ctx->stat("keydeps.build_overlap", overlap ? 1 : 0);
+    ctx->stat("keydeps.bc_sort_passes", 0);
+    if (overlap) ctx->lane_fork();
+    else build_dictionary(ctx, n, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.g, cb.dict, true);
 
     // ---- pairs sorted by (key, TxnId rank)
     cb.tinfo = ctx->get<uint4>("tinfo", n);
     cb.bigflag = ctx->get<uint32_t>("v3_bigflag", n);
-    const PairSort ps = sort_pairs(ctx, cb);
+    const PairSort ps = sort_pairs(ctx, cb, overlap);
+    if (overlap) {
+        // (enqueued after the pair sort: the context stream's long kernels are not held up by the lane's many launches)
+        ctx->launch_stream = ctx->aux[0];
+        build_dictionary(ctx, n, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.g, cb.dict, true);
+        ctx->lane_mark();   // the ranks
+        bc_from_txns(ctx, cb);
+        ctx->launch_stream = nullptr;
+    }
     cb.perm = ps.ps.vals;
     if (!ps.flags_done)
         launch(ctx, "seg_flags", k_seg_flags, dim3(grid_for(P, BLOCK)), dim3(BLOCK), 0, P, (const uint64_t *)ps.ps.keys,
@@ -2616,22 +2733,33 @@ CfkBuild build_cfk(acc_ctx *ctx, const acc_batch_in *in, CfkOpts opts)
     cb.cols.bc_exec = ctx->get<uint32_t>("v2_bc_exec", P);
     cb.cols.bc_kind = ctx->get<uint8_t>("v2_bc_kind", P);
     cb.cols.bc_pm_in = ctx->get<uint64_t>("v2_bc_pm_in", P);
-    cb.cols.bc_key = ctx->get<uint64_t>("v2_bc_key", P);
+    cb.cols.bc_key = cb.bc_side ? nullptr : ctx->get<uint64_t>("v2_bc_key", P);
     // the count / mark passes' accumulators, zeroed by the column kernels (txn records, k_v2_apply); bigflag above
     cb.tot = ctx->get<uint64_t>("v3_tot", 4);   // E, big txns, a 9-16-key big txn, stream txns with a run record
     cb.gstat = ctx->get<uint64_t>("v2_gstat", GSTAT_N + 6);   // + the batch totals and E / big counts (k_v3_ucompact)
-    build_columns(ctx, cb, ps, ps.tinfo_done);
+    build_columns(ctx, cb, ps, ps.tinfo_done, overlap);
     if (cb.dict.ties_pending && ctx->pinned[6]) {
         // an executeAt equals another timestamp: the sorted-batch ranks are not dense ranks; the general dictionary,
         // then the rank-dependent columns again (the pair order does not depend on ranks in a sorted batch)
         check_errors(ctx->pinned[4]);
+        ctx->lane_join();   // the general dictionary rewrites the ranks the lane reads, and reuses its scan and sort words
         redo_general_dictionary(ctx, n, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.g, cb.dict);
-        build_columns(ctx, cb, ps, false);
+        if (cb.bc_side) {
+            // the lane's list was made with the sorted-batch ranks: not used. The batch takes the replay path if the general dictionary finds the tie too, else keydeps_runs
+            // sorts cols.bc_key as written with the new ranks.
+            cb.bc_side = false;
+            cb.cols.bc_key = ctx->get<uint64_t>("v2_bc_key", P);
+            ctx->stat("keydeps.bc_sort_passes", 0);
+        }
+        build_columns(ctx, cb, ps, false, false);
     }
     cb.dict.ties_pending = false;
     memcpy(cb.htot, ctx->pinned, sizeof cb.htot);
     check_errors(ctx->pinned[4]);
     cb.ties = ctx->pinned[6] != 0;
+    // the two predicates of "bumped committed" (per txn in the prep pass, per position in the columns) must agree
+    if (cb.bc_side && !cb.ties && (uint64_t)cb.htot[6] != cb.dict.nbc)
+        fail(ACC_E_STATE, "internal: bumped committed count of the prep pass differs from the columns'");
     ctx->stat("keydeps.path_replay", cb.ties || (ctx->flags & ACC_OPT_FORCE_REPLAY) ? 1 : 0);
     ctx->stat("keydeps.exec_ties", cb.ties ? 1 : 0);
     ctx->stat("keydeps.batch_sorted", cb.dict.batch_sorted ? 1 : 0);
@@ -2704,14 +2832,28 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     uint32_t *const bigflag = cb.bigflag;
     uint64_t *const tot = cb.tot, *const gstat = cb.gstat;
     const uint32_t nbc = cb.htot[6];
-    if (segbits + rbits > 64) fail(ACC_E_ARG, "batch too large for the (segment, executeAt) composite key");
-    Sorted bcs = radix_sort(ctx, "rs_bc", cols.bc_key, nullptr, nbc, segbits + rbits);
-    uint32_t *bcs_exec = ctx->get<uint32_t>("v2_bcs_exec", nbc);
-    uint64_t *bcs_lw_in = ctx->get<uint64_t>("v2_bcs_lw_in64", nbc), *bcs_lw64 = ctx->get<uint64_t>("v2_bcs_lastw64", nbc);
-    launch(ctx, "v2_bcs_cols", k_v2_bcs_cols, dim3(grid_for(nbc, BLOCK)), dim3(BLOCK), 0, nbc, (const uint64_t *)bcs.keys,
-           (const uint32_t *)bcs.vals, (const uint8_t *)cols.bc_kind, (uint64_t)((1ull << rbits) - 1), bcs_exec, bcs_lw_in);
+    uint32_t *bcs_exec = cb.bcs_exec;
+    uint64_t *bcs_lw64 = cb.bcs_lastw64;
     uint64_t *bc_pm64 = ctx->get<uint64_t>("v2_bc_pm64", nbc);
-    {   // nearest-Write index and the segmented executeAt maximum: two prefix maxima in one launch (read as low words)
+    if (cb.bc_side) {
+        // the build made the (segment, executeAt) order on its side lane: only the segmented executeAt maximum over
+        // the position-ordered list is left. The count pass reads the lane's bcs_exec / bcs_lastw: the join goes first,
+        // so the cross-stream wait is served while the stream is idle behind the build's sync and the count pass
+        // follows the scan without a bubble.
+        ctx->lane_join();
+        scan<uint64_t, OpMax<uint64_t>>(ctx, cols.bc_pm_in, bc_pm64, nbc, false);
+    } else {
+        ctx->lane_join();   // (no lane is open here: a build that forked one either kept bc_side or joined at its tie branch)
+        if (segbits + rbits > 64) fail(ACC_E_ARG, "batch too large for the (segment, executeAt) composite key");
+        if (!cols.bc_key) fail(ACC_E_STATE, "internal: no bumped committed sort keys");
+        Sorted bcs = radix_sort(ctx, "rs_bc", cols.bc_key, nullptr, nbc, segbits + rbits);
+        ctx->stat("keydeps.bc_sort_passes", nbc ? (uint64_t)((segbits + rbits + 7) / 8) : 0);
+        bcs_exec = ctx->get<uint32_t>("v2_bcs_exec", nbc);
+        uint64_t *bcs_lw_in = ctx->get<uint64_t>("v2_bcs_lw_in64", nbc);
+        bcs_lw64 = ctx->get<uint64_t>("v2_bcs_lastw64", nbc);
+        launch(ctx, "v2_bcs_cols", k_v2_bcs_cols, dim3(grid_for(nbc, BLOCK)), dim3(BLOCK), 0, nbc, (const uint64_t *)bcs.keys,
+               (const uint32_t *)bcs.vals, (const uint8_t *)cols.bc_kind, (uint64_t)((1ull << rbits) - 1), bcs_exec, bcs_lw_in);
+        // nearest-Write index and the segmented executeAt maximum: two prefix maxima in one launch (read as low words)
         const uint64_t *si[2] = { bcs_lw_in, cols.bc_pm_in };
         uint64_t *so[2] = { bcs_lw64, bc_pm64 };
         const size_t sn[2] = { nbc, nbc };
@@ -2993,6 +3135,7 @@ void keydeps_of(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     if (!cb.cfk) {
         *view = ctx->kd_view;   // the empty result build_cfk left
     } else if (cb.ties || (ctx->flags & ACC_OPT_FORCE_REPLAY)) {
+        ctx->lane_join();   // the build's side lane (its list is not used here; its buffers are, by later stages)
         need_pair_pos(ctx, cb);
         keydeps_replay(ctx, cb, view);
     } else {
@@ -3021,6 +3164,7 @@ CfkBuild cfk_snapshot(acc_ctx *ctx, const acc_batch_in *in)
     CfkOpts opts;
     opts.seg_keys = true;
     CfkBuild cb = build_cfk(ctx, in, opts);
+    ctx->lane_join();   // the build's side lane: the snapshot's readers use the context stream only
     ctx->kd_valid = false;
     if (cb.cfk) cb.nseg = cfk_nseg(ctx, cb);
     return cb;

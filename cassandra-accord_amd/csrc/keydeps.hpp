@@ -25,7 +25,8 @@ struct V2Cols {
     uint32_t *bc_rank, *bc_exec;  // bumped committed, position order
     uint8_t *bc_kind;
     uint64_t *bc_pm_in;   // (seg << 32) | exec+1, for the segmented prefix max
-    uint64_t *bc_key;     // (seg << rbits) | exec, for the (seg, executeAt) sort
+    uint64_t *bc_key;     // (seg << rbits) | exec, for the (seg, executeAt) sort; null when the build made that order
+                          // from the txn side (CfkBuild::bc_side)
 };
 
 __device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t v)
@@ -212,6 +213,11 @@ struct CfkBuild {
     uint4 *tinfo = nullptr;           // [n] the per-txn records (k_txn_info)
     uint32_t *bigflag = nullptr;      // [n] zeroed by the column kernels, set by the count pass
     uint32_t htot[16] = {};           // the tile counts' totals as read at the build's sync ([6] = bumped committed)
+    // the bumped committed entries in (segment, executeAt) order, made by the build on the side lane from the txn side
+    // (bc_side; else keydeps_runs sorts cols.bc_key): executeAt ranks, nearest-Write index + 1 (inclusive prefix max)
+    bool bc_side = false;
+    uint32_t *bcs_exec = nullptr;
+    uint64_t *bcs_lastw64 = nullptr;
     V2Cols cols{};                    // the run-based scan's columns
     uint32_t *bases = nullptr;        // the class lists' bases in cols.list_rank
     uint64_t *tot = nullptr;          // count / mark accumulators, zeroed by the column kernels

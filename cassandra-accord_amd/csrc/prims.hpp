@@ -352,7 +352,7 @@ void scan_multi(acc_ctx *ctx, int k, const T *const *in, T *const *out, const si
     int m = 0;
     for (int i = 0; i < k; ++i) {
         if (n[i] == 0) {   // nothing to scan: the total is the identity of the sum (0)
-            if (total_out && total_out[i]) ACC_HIP(hipMemsetAsync(total_out[i], 0, sizeof(T), ctx->stream));
+            if (total_out && total_out[i]) ACC_HIP(hipMemsetAsync(total_out[i], 0, sizeof(T), ctx->cur()));
             continue;
         }
         a.in[m] = in[i]; a.out[m] = out[i]; a.total[m] = total_out ? total_out[i] : nullptr; a.n[m] = n[i];
@@ -364,28 +364,33 @@ void scan_multi(acc_ctx *ctx, int k, const T *const *in, T *const *out, const si
     if (m == 0) return;
     a.k = m;
     for (int i = m; i <= SCAN_MAXA; ++i) a.cum[i] = (uint32_t)nb;
-    // stream order is what makes the double-buffered status safe: every scan runs on the context stream
-    if (ctx->launch_stream) fail(ACC_E_STATE, "internal: scan launched on a side stream");
+    // stream order is what makes the double-buffered status safe: the scans of one lane (the context stream, or the
+    // side lane aux[0]) follow one another on one stream and use that lane's own status buffers and parity. The host
+    // state moves only after the launch is enqueued, so a failure before it leaves buffers and parity in step.
+    const int lane = ctx->scan_lane();
+    if (lane < 0) fail(ACC_E_STATE, "internal: scan launched on a side stream other than the side lane");
+    acc_ctx::ScanState &ss = ctx->scan_st[lane];
+    const char *const bn[2] = { lane ? "scan_lane_status0" : "scan_status0", lane ? "scan_lane_status1" : "scan_status1" };
     const size_t need = nb + 1;
     uint64_t *buf[2];
-    if (need > ctx->scan_cap) {
+    if (need > ss.cap) {
         for (int i = 0; i < 2; ++i) {
-            buf[i] = ctx->get_raw<uint64_t>(i ? "scan_status1" : "scan_status0", need);
-            ACC_HIP(hipMemsetAsync(buf[i], 0, need * sizeof(uint64_t), ctx->stream));
+            buf[i] = ctx->get_raw<uint64_t>(bn[i], need);
+            ACC_HIP(hipMemsetAsync(buf[i], 0, need * sizeof(uint64_t), ctx->cur()));
         }
-        ctx->scan_cap = need;
-        ctx->scan_dirty[0] = ctx->scan_dirty[1] = 0;
+        ss.cap = need;
+        ss.dirty[0] = ss.dirty[1] = 0;
     } else {
-        for (int i = 0; i < 2; ++i) buf[i] = ctx->get_raw<uint64_t>(i ? "scan_status1" : "scan_status0", need);
+        for (int i = 0; i < 2; ++i) buf[i] = ctx->get_raw<uint64_t>(bn[i], need);
     }
-    const int p = ctx->scan_par;
+    const int p = ss.par;
     uint64_t *status = buf[p];
     uint32_t *ticket = reinterpret_cast<uint32_t *>(status + nb);
     launch(ctx, "scan", k_scan_1p<T, Op, ITEMS>, dim3((unsigned)nb), dim3(BLOCK), 0, a, (int)exclusive, ticket, status,
-           buf[p ^ 1], (uint32_t)ctx->scan_dirty[p ^ 1]);
-    ctx->scan_dirty[p] = need;
-    ctx->scan_dirty[p ^ 1] = 0;
-    ctx->scan_par = p ^ 1;
+           buf[p ^ 1], (uint32_t)ss.dirty[p ^ 1]);
+    ss.dirty[p] = need;
+    ss.dirty[p ^ 1] = 0;
+    ss.par = p ^ 1;
 }
 
 template <class T, class Op>
@@ -409,7 +414,7 @@ static __global__ __launch_bounds__(BLOCK) void k_sum_u32(const uint32_t *__rest
 // enqueues the u64 total of in[0, n) into *out (zeroed first); the caller reads it at its next sync
 inline void sum_u32(acc_ctx *ctx, const uint32_t *in, size_t n, uint64_t *out)
 {
-    ACC_HIP(hipMemsetAsync(out, 0, 8, ctx->stream));
+    ACC_HIP(hipMemsetAsync(out, 0, 8, ctx->cur()));
     if (n) launch(ctx, "sum_u32", k_sum_u32, dim3((unsigned)std::min<size_t>(1024, (n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0,
                   in, n, out);
 }
@@ -804,7 +809,10 @@ struct Sorted {
 
 // The one-sweep words of a sort tag: [passes x 256 digit totals][passes tickets][passes x ntiles x 256 status words].
 // Two buffers per tag alternate: the histogram kernel of a sort zeroes the words the previous sort dirtied in the other
-// buffer, so no memset precedes a sort (both are zeroed once when they grow). Sorts run on the context stream only.
+// buffer, so no memset precedes a sort (both are zeroed once when they grow). A sort runs on the context stream or on
+// the side lane (aux[0]); the sorts of one tag must be ordered among themselves, which holds when, between a fork and
+// its join, the tag is used on one of the two only (fork and join order the lane against the main stream's earlier
+// and later sorts).
 struct OsWords {
     uint32_t *cur, *other;
     uint32_t other_n;
@@ -819,7 +827,7 @@ struct OsWords {
 };
 static inline OsWords os_words(acc_ctx *ctx, const char *tag, size_t words)
 {
-    if (ctx->launch_stream) fail(ACC_E_STATE, "internal: radix sort launched on a side stream");
+    if (ctx->scan_lane() < 0) fail(ACC_E_STATE, "internal: radix sort launched on a side stream other than the side lane");
     if (words >= 0xFFFFFFFFull) fail(ACC_E_CAP, "internal: radix sort status beyond 2^32 words");
     acc_ctx::OsState &s = ctx->os_state[ctx->ns + tag];
     char n0[56], n1[56];
@@ -827,7 +835,7 @@ static inline OsWords os_words(acc_ctx *ctx, const char *tag, size_t words)
     snprintf(n1, sizeof n1, "%s_os1", tag);
     uint32_t *b[2] = { ctx->get<uint32_t>(n0, std::max(words, s.cap)), ctx->get<uint32_t>(n1, std::max(words, s.cap)) };
     if (words > s.cap) {
-        for (int i = 0; i < 2; ++i) ACC_HIP(hipMemsetAsync(b[i], 0, words * sizeof(uint32_t), ctx->stream));
+        for (int i = 0; i < 2; ++i) ACC_HIP(hipMemsetAsync(b[i], 0, words * sizeof(uint32_t), ctx->cur()));
         s.cap = words;
         s.dirty[0] = s.dirty[1] = 0;
     }
@@ -850,8 +858,8 @@ static inline Sorted radix_sort(acc_ctx *ctx, const char *tag, const uint64_t *k
     int passes = (bits + 7) / 8;
     if (n == 0) return { k[0], v[0] };
     if (passes == 0) {
-        ACC_HIP(hipMemcpyAsync(k[0], keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-        if (vals) ACC_HIP(hipMemcpyAsync(v[0], vals, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+        ACC_HIP(hipMemcpyAsync(k[0], keys, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->cur()));
+        if (vals) ACC_HIP(hipMemcpyAsync(v[0], vals, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->cur()));
         else launch(ctx, "iota", k_iota, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, v[0], n);
         return { k[0], v[0] };
     }

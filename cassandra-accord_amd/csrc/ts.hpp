@@ -37,4 +37,18 @@ __device__ __forceinline__ uint32_t witnesses(uint32_t kind)
     }
 }
 
+// Kind class for the Kinds predicates (Txn.java:140-152): Read 0, Write 1, SyncPoint/ExclusiveSyncPoint 2;
+// EphemeralRead and LocalOnly are witnessed by no predicate (3 = none).
+__device__ __forceinline__ uint32_t kind_class(uint32_t kind)
+{
+    return kind == 0 ? 0u : kind == 1 ? 1u : (kind == 3 || kind == 4) ? 2u : 3u;
+}
+
+// "Bumped committed" as the run-based KeyDeps scan lists it, a per-txn property: committed (InternalStatus 4..6), of a
+// kind some predicate witnesses, executeAt != TxnId (v2_code, keydeps.hip, decides the same per CFK position).
+__device__ __forceinline__ bool bumped_committed(uint32_t status, uint32_t kind, bool bumped)
+{
+    return bumped && status >= 4 && status <= 6 && kind_class(kind) < 3;
+}
+
 }  // namespace acc

@@ -17,7 +17,7 @@ starts = [i for i, r in enumerate(rows) if r["kind"] == "K" and first in r["Kern
 i0 = starts[occ]
 i1 = next((i for i in range(i0 + 1, len(rows)) if rows[i]["kind"] == "K" and stop in rows[i]["Kernel_Name"]), len(rows))
 t0 = int(rows[i0]["Start_Timestamp"])
-last_end = t0
+last_end = 0   # offsets from t0, as s and e below
 busy = 0
 for r in rows[i0:i1]:
     s, e = int(r["Start_Timestamp"]) - t0, int(r["End_Timestamp"]) - t0
