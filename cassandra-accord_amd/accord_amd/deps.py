@@ -1082,11 +1082,54 @@ class CfkStore:
         self.ctx.check(self.ctx._lib.acc_cfk_keydeps(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
         return self.ctx.copy_out(view, None)
 
+    def keydeps_mixed(self, queries: dict, end_inclusive: int = 1, lane_seg: int = 0) -> "BatchKeyDeps":
+        """keydeps for queries of both domains (acc_cfk_keydeps_mixed; impl/InMemoryCommandStore.java:274-289): queries =
+        the keydeps dict plus rng_off, rng_start, rng_end. A key-domain TxnId lists keys and no ranges; a range-domain
+        TxnId (domain bit set) lists ranges (sorted, non-overlapping, start < end) and no keys, and is answered on every
+        CFK key its ranges cover, (s, e] when end_inclusive else [s, e): key_idx indexes those covered keys in range
+        order, kd_key holds their codes. lane_seg: the lane tier's segment threshold (0: the library default,
+        L.ACC_CFQ_LANE_NONE: off); results do not depend on it."""
+        q = queries
+        a = dict(qm=np.ascontiguousarray(q["msb"], dtype=np.uint64), ql=np.ascontiguousarray(q["lsb"], dtype=np.uint64),
+                 qn=np.ascontiguousarray(q["node"], dtype=np.int32), ko=np.ascontiguousarray(q["key_off"], dtype=np.uint32),
+                 kc=np.ascontiguousarray(q["key_code"], dtype=np.uint64), ro=np.ascontiguousarray(q["rng_off"], dtype=np.uint32),
+                 rs=np.ascontiguousarray(q["rng_start"], dtype=np.uint64), re=np.ascontiguousarray(q["rng_end"], dtype=np.uint64))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ex = L.TsCols(None, None, None)
+        if q.get("xmsb") is not None:
+            a.update(xm=np.ascontiguousarray(q["xmsb"], dtype=np.uint64), xl=np.ascontiguousarray(q["xlsb"], dtype=np.uint64),
+                     xn=np.ascontiguousarray(q["xnode"], dtype=np.int32))
+            ex = L.TsCols(p("xm"), p("xl"), p("xn"))
+        n = len(a["qm"])
+        qi = L.CfkMixedQueries(n, L.ACC_MEM_HOST, len(a["kc"]), len(a["rs"]), L.TsCols(p("qm"), p("ql"), p("qn")), ex, p("ko"),
+                               p("kc"), p("ro"), p("rs"), p("re"), int(end_inclusive), int(lane_seg))
+        view = L.KeydepsView()
+        self.ctx.check(self.ctx._lib.acc_cfk_keydeps_mixed(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
+        return self.ctx.copy_out(view, None)
+
     def missing_view(self) -> "L.CfkBatchView":
         """The store's txn-major view with each pair's missing[] as txn indices (device), for cfk_map_reduce_full."""
         bv = L.CfkBatchView()
         self.ctx.check(self.ctx._lib.acc_cfk_missing(self.ctx.handle, self._h, C.byref(bv)))
         return bv
+
+
+def mixed_queries_from_preaccept(q: dict) -> dict:
+    """The acc_preaccept_in-layout queries (msb, lsb, node, is_range, part_off, part_start, part_end; optional xmsb,
+    xlsb, xnode) as the CfkStore.keydeps_mixed dict: the parts of an is_range == 0 query become its keys (part_start),
+    those of an is_range == 1 query its ranges (part_start, part_end)."""
+    is_range = np.asarray(q["is_range"]).astype(bool)
+    off = np.asarray(q["part_off"], dtype=np.int64)
+    per = np.diff(off)
+    rpart = np.repeat(is_range, per)
+    start = np.asarray(q["part_start"], dtype=np.uint64)
+    csum = lambda cnt: np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32)  # noqa: E731
+    out = dict(msb=q["msb"], lsb=q["lsb"], node=q["node"], key_off=csum(np.where(is_range, 0, per)), key_code=start[~rpart],
+               rng_off=csum(np.where(is_range, per, 0)), rng_start=start[rpart],
+               rng_end=np.asarray(q["part_end"], dtype=np.uint64)[rpart])
+    if q.get("xmsb") is not None:
+        out.update(xmsb=q["xmsb"], xlsb=q["xlsb"], xnode=q["xnode"])
+    return out
 
 
 def _execute_at_after(part: dict, q: dict):
@@ -1124,8 +1167,9 @@ class ReplicaStore:
         """part: the batch's updates (cfk_update_stream layout); queries: its PreAccept queries (default: one per
         command first seen in part). Returns dict(propose = MaxConflicts.get + fast path per query, keydeps = the
         KeyDeps of every txn of the store after the batch, when scan). scan="new": instead keydeps_new = the KeyDeps of
-        the queries alone, scanned against the updated store in place (acc_cfk_keydeps): the rows the whole-store scan
-        would give for them, nothing recomputed for stored txns. A query without executeAt columns (xmsb, xlsb, xnode)
+        the queries alone, scanned against the updated store in place (acc_cfk_keydeps; acc_cfk_keydeps_mixed with the
+        store's bound type when a query has is_range set): the rows the whole-store scan would give for them, nothing
+        recomputed for stored txns. A query without executeAt columns (xmsb, xlsb, xnode)
         takes the executeAt the batch leaves its txn with."""
         from . import workload as W
         q = W.preaccept_queries(part) if queries is None else queries
@@ -1135,12 +1179,16 @@ class ReplicaStore:
         if isinstance(scan, str):
             if scan != "new":
                 raise ValueError(f"scan must be True, False or 'new', not {scan!r}")
-            nq = dict(msb=q["msb"], lsb=q["lsb"], node=q["node"], key_off=q["part_off"], key_code=q["part_start"])
-            if q.get("xmsb") is not None:
-                nq.update(xmsb=q["xmsb"], xlsb=q["xlsb"], xnode=q["xnode"])
+            mixed = q.get("is_range") is not None and bool(np.any(q["is_range"]))
+            if mixed:
+                nq = mixed_queries_from_preaccept(q)
             else:
+                nq = dict(msb=q["msb"], lsb=q["lsb"], node=q["node"], key_off=q["part_off"], key_code=q["part_start"])
+                if q.get("xmsb") is not None:
+                    nq.update(xmsb=q["xmsb"], xlsb=q["xlsb"], xnode=q["xnode"])
+            if q.get("xmsb") is None:
                 nq.update(zip(("xmsb", "xlsb", "xnode"), _execute_at_after(part, q)))
-            out["keydeps_new"] = self.cfk.keydeps(nq)
+            out["keydeps_new"] = self.cfk.keydeps_mixed(nq, self.end_inclusive) if mixed else self.cfk.keydeps(nq)
         elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
         return out

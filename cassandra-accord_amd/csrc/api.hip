@@ -39,6 +39,7 @@ void cfk_state(acc_cfk *cfk, acc_cfk_snap *out);
 void cfk_missing(acc_cfk *cfk, acc_cfk_batch_view *out);
 void cfk_free(acc_cfk *cfk);
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
+void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *view);
 acc_cfk *cfk_new(int device);
 }  // namespace acc
 
@@ -310,6 +311,15 @@ int acc_cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_ke
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_keydeps(ctx, cfk, q, out_view);
+    });
+}
+
+int acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *out_view)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_keydeps_mixed(ctx, cfk, q, out_view);
     });
 }
 

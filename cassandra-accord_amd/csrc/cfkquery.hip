@@ -22,6 +22,26 @@
 //                 (query, txn index), a unique flag scan and a binary search per hit. Both leave the sorted unique
 //                 txn indices in the hit slots, which one scan compacts into dep_txn.
 //
+//
+// acc_cfk_keydeps_mixed: the same for queries of both domains (impl/InMemoryCommandStore.java:274-289, the Range case of
+// mapReduceForKey: mapReduceActive on every CFK of commandsForKey.subMap(start, startInclusive, end, endInclusive) per
+// range). A range query's row is the row of a key query over the CFK keys its ranges cover, and km.key is sorted, so
+// the keys a range covers are one run of km.key and their entries one span of the entry columns. A front end turns
+// the call into the (query, key) pairs of step 2 and everything from the offsets on runs as above:
+//   r1. rvalidate  per query: kind, both offset arrays, keys only on key-domain and ranges only on range-domain queries,
+//                  keys sorted unique, ranges start < end, sorted, not overlapping
+//   r2. rbounds    per range: the run of km.key it covers (two binary searches with the store's bound type); per query
+//                  its pairs (own keys or covered keys); one scan: the expanded pair offsets (the total goes to the host)
+//   r3. rexpand    per expanded pair: its query, its range (a search of the per-range offsets: no thread walks a wide
+//                  range) and its store key; a key-domain pair is located as in step 2, a covered pair knows its segment
+//   lane tier      a covered pair whose whole segment holds at most lane_seg entries is answered by one lane: consecutive
+//                  lanes take consecutive covered keys, so a wave reads one contiguous span of the entry columns
+//                  instead of one wave per pair using a few of its 256 entry slots. The lane walks its segment to the
+//                  first TxnId >= S gathering M and the tie count, then counts (cq_lane_max) and, after the offsets,
+//                  writes (cq_lane_emit) the emitted entries. Such a pair keeps one chunk slot; the chunk kernels see
+//                  it with an empty prefix and the lane kernels fill the slot after them, so neither the chunk kernels
+//                  nor the offset machinery know about the tier.
+//
 // Results live in cq_* buffers only: acc_cfk_apply_deps trades the context's cd_* / cb_* buffers with the store.
 #include "keydeps.hpp"
 #include "cfkquery.hpp"
@@ -32,8 +52,11 @@ namespace cq {
 
 constexpr uint32_t CH = 256;          // segment entries per work chunk: one wave, four per lane
 constexpr uint32_t CAP_MAX = 1024;    // hits of a query the one-wave build tier holds in LDS (u64 each, per wave)
+constexpr uint64_t MAX_GRID = 1u << 23;     // blocks of one launch (x BLOCK = 2^31 work-items; a dispatch holds < 2^32)
+constexpr uint32_t LANE_SEG_DEFAULT = 16;   // acc_cfk_mixed_queries::lane_seg == 0 (the measured table)
 
-enum : uint64_t { E_KIND_ARG = 1, E_KIND_STATE = 2, E_RANGE = 4, E_OFF = 8, E_KEYS = 16, E_TIE = 32 };
+enum : uint64_t { E_KIND_ARG = 1, E_KIND_STATE = 2, E_RANGE = 4, E_OFF = 8, E_KEYS = 16, E_TIE = 32,
+                  E_RKEYS = 64, E_KRANGES = 128, E_ROFF = 256, E_RBOUND = 512, E_RORDER = 1024 };
 
 struct Queries {
     const uint64_t *qm, *ql, *xm, *xl;   // TxnId, executeAt (= TxnId columns when the caller gave none)
@@ -48,6 +71,22 @@ struct Pairs {
     const uint64_t *chunk_off;           // [Qp + 1]
     const uint32_t *item;                // [chunks] the pair of every chunk
     uint32_t Qp;
+};
+
+// the lane tier's pairs: to the chunk kernels such a pair has an empty prefix (w = 0) and one chunk slot
+struct Lanes {
+    const uint8_t *is;                   // [Qp] the pair is answered by the lane tier
+    uint32_t *w;                         // [Qp] its segment's length, then (k_cq_lane_max) its prefix's
+};
+
+// acc_cfk_keydeps_mixed: the caller's keys and ranges, and per range the run of km.key it covers
+struct Ranges {
+    const uint32_t *key_off, *rng_off;   // [nq + 1]
+    const uint64_t *key_code;            // [n_pairs]
+    const uint64_t *start, *end;         // [nr]
+    uint32_t nr, end_inclusive;
+    const uint32_t *lo;                  // [nr] first covered store key
+    const uint64_t *cum;                 // [nr + 1] covered keys of the ranges before it
 };
 
 // a chunk's (and, in a pair's first chunk slot, the pair's) M and tie count: f = has M << 31 | min(ties, 3)
@@ -109,6 +148,20 @@ __global__ __launch_bounds__(BLOCK) void k_cq_validate(Queries Q, uint64_t *__re
     if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
 }
 
+// the prefix of segment [s0, s1) below S (its length), and whether the entry at its end counts towards the tie rule
+__device__ __forceinline__ uint32_t prefix_of(const CfkResident &s, uint32_t s0, uint32_t s1, uint64_t Sm, uint64_t Sl, int32_t Sn,
+                                              uint32_t &t0)
+{
+    uint32_t x = s0, y = s1;
+    while (x < y) {
+        const uint32_t m = (x + y) >> 1;
+        if (ts_cmp(s.em[m], s.el[m], s.en[m], Sm, Sl, Sn) < 0) x = m + 1; else y = m;
+    }
+    // entries past it have TxnId > S, and executeAt >= TxnId
+    t0 = x < s1 && committed(s.st[x]) && ts_cmp(s.xm[x], s.xl[x], s.xn[x], Sm, Sl, Sn) == 0 ? 1u : 0u;
+    return x - s0;
+}
+
 // per pair: the prefix [a, a + w) of its key's segment the scan visits, whether the entry at its end is a committed
 // entry executing at S (it counts towards the tie rule), and its chunks
 __global__ __launch_bounds__(BLOCK) void k_cq_locate(Queries Q, CfkResident s, uint32_t *__restrict__ pair_q,
@@ -123,18 +176,8 @@ __global__ __launch_bounds__(BLOCK) void k_cq_locate(Queries Q, CfkResident s, u
     uint32_t lo = 0, hi = s.nk;
     while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
     if (lo < s.nk && s.key[lo] == k) {
-        const uint32_t s0 = s.ent_off[lo], s1 = s.ent_off[lo + 1];
-        const uint64_t Sm = Q.xm[q], Sl = Q.xl[q];
-        const int32_t Sn = Q.xn[q];
-        uint32_t x = s0, y = s1;
-        while (x < y) {
-            const uint32_t m = (x + y) >> 1;
-            if (ts_cmp(s.em[m], s.el[m], s.en[m], Sm, Sl, Sn) < 0) x = m + 1; else y = m;
-        }
-        a = s0;
-        w = x - s0;
-        // entries past it have TxnId > S, and executeAt >= TxnId
-        if (x < s1 && committed(s.st[x]) && ts_cmp(s.xm[x], s.xl[x], s.xn[x], Sm, Sl, Sn) == 0) t0 = 1;
+        a = s.ent_off[lo];
+        w = prefix_of(s, a, s.ent_off[lo + 1], Q.xm[q], Q.xl[q], Q.xn[q], t0);
     }
     pair_q[i] = q;
     pair_a[i] = a;
@@ -182,11 +225,11 @@ __device__ __forceinline__ uint32_t chunk_count(const CfkResident &s, const Chun
 
 // one wave per chunk: the chunk's part of maxCommittedBefore and of the tie count. A pair of one chunk (a short prefix:
 // the common case) has its M right here, so its wave counts the emitted entries as well (the entries are still in cache).
-__global__ __launch_bounds__(BLOCK) void k_cq_max(uint64_t nchunks, Queries Q, CfkResident s, Pairs P,
+__global__ __launch_bounds__(BLOCK) void k_cq_max(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P,
                                                   const uint8_t *__restrict__ pair_t0, Part part, uint64_t *__restrict__ chunk_cnt,
                                                   uint64_t *__restrict__ errs)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const uint32_t item = P.item[cw];
     const uint32_t q = P.q[item];
@@ -227,9 +270,9 @@ __global__ __launch_bounds__(BLOCK) void k_cq_max(uint64_t nchunks, Queries Q, C
 }
 
 // one wave per pair of several chunks: the chunks' parts folded into the pair's first chunk slot
-__global__ __launch_bounds__(BLOCK) void k_cq_fold(Pairs P, Part part, uint64_t *__restrict__ errs)
+__global__ __launch_bounds__(BLOCK) void k_cq_fold(uint64_t first, Pairs P, Part part, uint64_t *__restrict__ errs)
 {
-    const uint32_t i = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t i = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (i >= P.Qp) return;
     const uint64_t c0 = P.chunk_off[i], c1 = P.chunk_off[i + 1];
     if (c1 - c0 <= 1) return;
@@ -267,10 +310,10 @@ __device__ __forceinline__ ChunkCtx chunk_ctx(uint64_t cw, const Queries &Q, con
 }
 
 // one wave per chunk of a pair of several chunks (k_cq_max counted the others)
-__global__ __launch_bounds__(BLOCK) void k_cq_count(uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
+__global__ __launch_bounds__(BLOCK) void k_cq_count(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
                                                     uint64_t *__restrict__ chunk_cnt)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const uint32_t item = P.item[cw];
     if (P.chunk_off[item + 1] - P.chunk_off[item] == 1) return;
@@ -307,13 +350,26 @@ __global__ __launch_bounds__(BLOCK) void k_cq_qoff(uint32_t nq, const uint32_t *
     }
 }
 
+// entry e as its index in the store's txn-major view: the lower bound of its TxnId in the view's sorted TxnId columns
+__device__ __forceinline__ uint32_t view_index(const CfkResident &s, uint32_t e)
+{
+    const uint64_t xm = s.em[e], xl = s.el[e];
+    const int32_t xn = s.en[e];
+    uint32_t lo = 0, hi = s.n_txn;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 // the count pass's walk, compacting in position order: every emitted entry as its index in the store's txn-major view
-__global__ __launch_bounds__(BLOCK) void k_cq_emit(uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
+__global__ __launch_bounds__(BLOCK) void k_cq_emit(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Part part,
                                                    const uint64_t *__restrict__ chunk_eoff, const uint64_t *__restrict__ epos,
                                                    const uint64_t *__restrict__ gcnt, const uint64_t *__restrict__ goff, int tb,
                                                    uint32_t *__restrict__ hit, uint64_t *__restrict__ gkey)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const ChunkCtx c = chunk_ctx(cw, Q, P, part);
     const uint64_t lt = (1ull << lane_id()) - 1;
@@ -326,13 +382,7 @@ __global__ __launch_bounds__(BLOCK) void k_cq_emit(uint64_t nchunks, Queries Q, 
         const bool m = e < c.end && emitted(s, c, e);
         const uint64_t bal = __ballot(m);
         if (m) {
-            const uint64_t xm = s.em[e], xl = s.el[e];
-            const int32_t xn = s.en[e];
-            uint32_t lo = 0, hi = s.n_txn;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
-            }
+            const uint32_t lo = view_index(s, e);
             const uint64_t p = out + (uint64_t)__popcll(bal & lt);
             hit[p] = lo;
             if (big) gkey[gbase + p] = ((uint64_t)c.q << tb) | lo;
@@ -453,12 +503,188 @@ __global__ __launch_bounds__(BLOCK) void k_cq_uoff(uint32_t nq, const uint32_t *
     if (q <= nq) u_off[q] = upos[epos[qoff[q]]];
 }
 
+// ---------------------------------------------------------------- acc_cfk_keydeps_mixed: the front end and the lane tier
+
+// Q.off / Q.key: the caller's key_off / key_code
+__global__ __launch_bounds__(BLOCK) void k_cq_rvalidate(Queries Q, Ranges R, uint64_t *__restrict__ errs)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= Q.nq) return;
+    uint64_t e = 0;
+    const uint64_t l = Q.ql[q];
+    const uint32_t kind = (uint32_t)(l >> 1) & 7u;
+    if (kind > ACC_KIND_LOCAL_ONLY) e |= E_KIND_ARG;          // Kind.ofOrdinal
+    else if (witnesses(kind) == 0) e |= E_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+    const bool range = l & 1u;
+    const uint32_t k0 = Q.off[q], k1 = Q.off[q + 1];
+    if (k1 < k0 || k1 > Q.Qp || (q == 0 && k0 != 0) || (q == Q.nq - 1 && k1 != Q.Qp)) e |= E_OFF;
+    else if (range) { if (k1 != k0) e |= E_RKEYS; }
+    else
+        for (uint32_t j = k0 + 1; j < k1; ++j)
+            if (Q.key[j - 1] >= Q.key[j]) { e |= E_KEYS; break; }
+    const uint32_t r0 = R.rng_off[q], r1 = R.rng_off[q + 1];
+    if (r1 < r0 || r1 > R.nr || (q == 0 && r0 != 0) || (q == Q.nq - 1 && r1 != R.nr)) e |= E_ROFF;
+    else if (!range) { if (r1 != r0) e |= E_KRANGES; }
+    else
+        for (uint32_t j = r0; j < r1; ++j) {
+            if (R.start[j] >= R.end[j]) e |= E_RBOUND;
+            if (j > r0 && R.end[j - 1] > R.start[j]) e |= E_RORDER;     // touching ranges are allowed
+        }
+    if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
+}
+
+// per range: the run of store keys it covers, (start, end] or [start, end)
+__global__ __launch_bounds__(BLOCK) void k_cq_rbounds(Ranges R, CfkResident s, uint32_t *__restrict__ rlo, uint64_t *__restrict__ rcnt)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= R.nr) return;
+    const uint64_t a = R.start[r], b = R.end[r];
+    uint32_t lo, hi;
+    if (R.end_inclusive) {
+        lo = upper<uint64_t>(s.key, s.nk, a);
+        hi = upper<uint64_t>(s.key, s.nk, b);
+    } else {
+        lo = a ? upper<uint64_t>(s.key, s.nk, a - 1) : 0u;
+        hi = upper<uint64_t>(s.key, s.nk, b - 1);                      // start < end: b >= 1
+    }
+    rlo[r] = lo;
+    rcnt[r] = hi - lo;
+}
+
+// per query: its pairs, own keys or covered keys
+__global__ __launch_bounds__(BLOCK) void k_cq_rcount(Queries Q, Ranges R, uint64_t *__restrict__ qcnt)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= Q.nq) return;
+    qcnt[q] = (Q.ql[q] & 1u) ? R.cum[R.rng_off[q + 1]] - R.cum[R.rng_off[q]] : (uint64_t)(Q.off[q + 1] - Q.off[q]);
+}
+
+// the expanded pair offsets as the u32 the scan reads (the host has checked the total)
+__global__ __launch_bounds__(BLOCK) void k_cq_roff(uint32_t n, const uint64_t *__restrict__ in, uint32_t *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) out[i] = (uint32_t)in[i];
+}
+
+// k_cq_locate over the expanded pairs (Q.off: their offsets): a key-domain pair searches its key; a covered pair finds
+// its range by the per-range offsets and knows its segment; a covered pair with a short segment goes to the lane tier,
+// which finds the prefix itself (lane_w: the segment's length until then). Writes every pair's key code.
+__global__ __launch_bounds__(BLOCK) void k_cq_rexpand(Queries Q, Ranges R, CfkResident s, uint32_t lane_seg, uint64_t *__restrict__ x_key,
+                                                      uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_a,
+                                                      uint32_t *__restrict__ pair_w, uint8_t *__restrict__ pair_t0,
+                                                      uint64_t *__restrict__ chunks, uint8_t *__restrict__ lane,
+                                                      uint32_t *__restrict__ lane_w, uint64_t *__restrict__ nlane)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q.Qp) return;
+    const uint32_t q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
+    const uint32_t j = i - Q.off[q];
+    uint32_t a = 0, w = 0, t0 = 0, ln = 0, seg = s.nk;
+    uint64_t k;
+    const bool range = Q.ql[q] & 1u;
+    if (range) {
+        const uint32_t r0 = R.rng_off[q], r1 = R.rng_off[q + 1];
+        const uint64_t at = R.cum[r0] + j;
+        const uint32_t r = r0 + upper<uint64_t>(R.cum + r0, r1 - r0, at) - 1;     // the last range starting at or below at
+        seg = R.lo[r] + (uint32_t)(at - R.cum[r]);
+        k = s.key[seg];
+    } else {
+        k = R.key_code[R.key_off[q] + j];
+        uint32_t lo = 0, hi = s.nk;
+        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
+        if (lo < s.nk && s.key[lo] == k) seg = lo;
+    }
+    if (seg < s.nk) {
+        const uint32_t s0 = s.ent_off[seg], s1 = s.ent_off[seg + 1];
+        a = s0;
+        if (range && lane && s1 - s0 <= lane_seg) { ln = 1; lane_w[i] = s1 - s0; }
+        else w = prefix_of(s, s0, s1, Q.xm[q], Q.xl[q], Q.xn[q], t0);
+    }
+    x_key[i] = k;
+    pair_q[i] = q;
+    pair_a[i] = a;
+    pair_w[i] = w;
+    pair_t0[i] = (uint8_t)t0;
+    if (lane) lane[i] = (uint8_t)ln;
+    chunks[i] = ln ? 1u : (w + CH - 1) / CH;
+    const uint64_t bal = __ballot(ln != 0);
+    if (ln && lane_id() == (uint32_t)__ffsll((long long)bal) - 1)
+        atomicAdd((unsigned long long *)nlane, (unsigned long long)__popcll(bal));
+}
+
+// lane tier, one lane per pair: walks the segment to the first TxnId >= S (the prefix's end), gathering M and the tie
+// count (the entry at the end included), then counts the emitted entries of the prefix; fills the pair's chunk slot
+__global__ __launch_bounds__(BLOCK) void k_cq_lane_max(Queries Q, CfkResident s, Pairs P, Lanes ln, Part part,
+                                                       uint64_t *__restrict__ chunk_cnt, uint64_t *__restrict__ errs)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= P.Qp || !ln.is[i]) return;
+    const uint32_t q = P.q[i], a = P.a[i], s1 = a + ln.w[i];
+    const uint64_t Sm = Q.xm[q], Sl = Q.xl[q];
+    const int32_t Sn = Q.xn[q];
+    Best b{ 0, 0, 0, 0 };
+    uint32_t ties = 0, e = a;
+    for (; e < s1; ++e) {
+        if (ts_cmp(s.em[e], s.el[e], s.en[e], Sm, Sl, Sn) >= 0) break;
+        if (committed(s.st[e])) {
+            const uint64_t xm = s.xm[e], xl = s.xl[e];
+            const int32_t xn = s.xn[e];
+            const int c = ts_cmp(xm, xl, xn, Sm, Sl, Sn);
+            if (c == 0) ++ties;
+            else if (c < 0 && ((uint32_t)(s.el[e] >> 1) & 7u) == ACC_KIND_WRITE) best_take(b, xm, xl, xn, 1u);
+        }
+    }
+    if (e < s1 && committed(s.st[e]) && ts_cmp(s.xm[e], s.xl[e], s.xn[e], Sm, Sl, Sn) == 0) ++ties;
+    ChunkCtx c;
+    c.item = i; c.q = q; c.base = a; c.end = e;
+    c.qm = Q.qm[q]; c.ql = Q.ql[q]; c.qn = Q.qn[q];
+    c.wk = witnesses((uint32_t)(c.ql >> 1) & 7u);
+    c.has_m = b.has; c.Mm = b.m; c.Ml = b.l; c.Mn = b.n;
+    uint32_t cnt = 0;
+    for (uint32_t x = a; x < e; ++x) cnt += emitted(s, c, x) ? 1u : 0u;
+    const uint64_t cw = P.chunk_off[i];
+    part.m[cw] = b.m; part.l[cw] = b.l; part.n[cw] = b.n;
+    part.f[cw] = (b.has << 31) | min(ties, 3u);
+    chunk_cnt[cw] = cnt;
+    ln.w[i] = e - a;
+    if (ties >= 2) atomicOr((unsigned long long *)errs, (unsigned long long)E_TIE);
+}
+
+// lane tier: the same walk over the prefix, every emitted entry as its view index, in TxnId order
+__global__ __launch_bounds__(BLOCK) void k_cq_lane_emit(Queries Q, CfkResident s, Pairs P, Lanes ln, Part part, const uint64_t *__restrict__ chunk_eoff,
+                                                        const uint64_t *__restrict__ epos, const uint64_t *__restrict__ gcnt,
+                                                        const uint64_t *__restrict__ goff, int tb, uint32_t *__restrict__ hit,
+                                                        uint64_t *__restrict__ gkey)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= P.Qp || !ln.is[i]) return;
+    const uint64_t cw = P.chunk_off[i];
+    uint64_t out = chunk_eoff[cw];
+    if (chunk_eoff[cw + 1] == out) return;
+    ChunkCtx c = chunk_ctx(cw, Q, P, part);
+    c.end = c.base + ln.w[i];
+    const bool big = gcnt[c.q] != 0;
+    const uint64_t gbase = big ? goff[c.q] - epos[Q.off[c.q]] : 0;
+    for (uint32_t e = c.base; e < c.end; ++e) {
+        if (!emitted(s, c, e)) continue;
+        const uint32_t lo = view_index(s, e);
+        hit[out] = lo;
+        if (big) gkey[gbase + out] = ((uint64_t)c.q << tb) | lo;
+        ++out;
+    }
+}
+
 static void check_cq_errors(uint64_t e)
 {
     if (e & E_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in a query TxnId");
     if (e & E_RANGE) fail(ACC_E_ARG, "range-domain queries against the resident store are not supported");
     if (e & E_OFF) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
     if (e & E_KEYS) fail(ACC_E_ARG, "keys of a query must be sorted and unique (Keys.ofSortedUnique)");
+    if (e & E_ROFF) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+    if (e & E_RKEYS) fail(ACC_E_ARG, "a range-domain query lists keys");
+    if (e & E_KRANGES) fail(ACC_E_ARG, "a key-domain query lists ranges");
+    if (e & E_RBOUND) fail(ACC_E_ARG, "a range needs start < end");
+    if (e & E_RORDER) fail(ACC_E_ARG, "ranges of a query must be sorted and must not overlap (Ranges.ofSortedAndDeoverlapped)");
     if (e & E_KIND_STATE) fail(ACC_E_STATE, "Kind.witnesses(): unhandled kind LocalOnly (AssertionError)");
     if (e & E_TIE)
         fail(ACC_E_STATE, "two or more committed entries of one key execute at a query's executeAt: the FAST bisection "
@@ -469,34 +695,86 @@ static void check_cq_errors(uint64_t e)
 
 using namespace cq;
 
-void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keydeps_view *view)
+// what an entry's front end (k_cq_locate / k_cq_rexpand) leaves per pair for the scan both entries share
+struct Located {
+    uint32_t *pair_q, *pair_a, *pair_w;
+    uint8_t *pair_t0;
+    uint64_t *chunks;
+    uint8_t *lane;          // null: no lane tier (acc_cfk_keydeps, ACC_CFQ_LANE_NONE)
+    uint32_t *lane_w;
+};
+
+static Located located_bufs(acc_ctx *ctx, uint32_t Qp, bool lanes)
 {
-    if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
-    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    return Located{ ctx->get<uint32_t>("cq_pair_q", Qp), ctx->get<uint32_t>("cq_pair_a", Qp), ctx->get<uint32_t>("cq_pair_w", Qp),
+                    ctx->get<uint8_t>("cq_pair_t0", Qp), ctx->get<uint64_t>("cq_chunks", Qp),
+                    lanes ? ctx->get<uint8_t>("cq_pair_lane", Qp) : nullptr, lanes ? ctx->get<uint32_t>("cq_lane_w", Qp) : nullptr };
+}
+
+static CfkResident resident_checked(acc_cfk *cfk, uint32_t mem)
+{
+    if (mem != ACC_MEM_HOST && mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
     const CfkResident s = cfk_resident(cfk);
     if (!s.deps && s.n_txn)
         fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): it has no key-major CommandsForKey to scan");
+    return s;
+}
+
+// n_query == 0
+static void empty_result(acc_ctx *ctx, acc_keydeps_view *view)
+{
+    hipStream_t st = ctx->stream;
+    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", 1);
+    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", 1);
+    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", 1);
+    ACC_HIP(hipMemsetAsync(arena_off, 0, 8, st));
+    ACC_HIP(hipMemsetAsync(kd_off, 0, 8, st));
+    ACC_HIP(hipMemsetAsync(u_off, 0, 8, st));
+    ctx->sync();
+    *view = acc_keydeps_view{ 0, 0, 0, 0, 0, arena_off, ctx->get<int32_t>("cq_arena", 1), kd_off,
+                              ctx->get<uint32_t>("cq_key_idx", 1), u_off, ctx->get<uint32_t>("cq_dep_txn", 1),
+                              ctx->get<uint64_t>("cq_kd_key", 1) };
+    ctx->kd_view = *view;
+    ctx->kd_valid = true;
+}
+
+static void stage_ids(acc_ctx *ctx, Queries &Q, const acc_ts_cols &txn_id, const acc_ts_cols &execute_at, uint32_t nq, uint32_t mem)
+{
+    Q.qm = stage_in(ctx, "cq_in_qm", txn_id.msb, nq, mem);
+    Q.ql = stage_in(ctx, "cq_in_ql", txn_id.lsb, nq, mem);
+    Q.qn = stage_in(ctx, "cq_in_qn", txn_id.node, nq, mem);
+    if (execute_at.msb) {
+        Q.xm = stage_in(ctx, "cq_in_xm", execute_at.msb, nq, mem);
+        Q.xl = stage_in(ctx, "cq_in_xl", execute_at.lsb, nq, mem);
+        Q.xn = stage_in(ctx, "cq_in_xn", execute_at.node, nq, mem);
+    } else {
+        Q.xm = Q.qm; Q.xl = Q.ql; Q.xn = Q.qn;
+    }
+}
+
+static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view);
+
+// one wave per item (chunk or pair), in launches of at most MAX_GRID blocks: the zipf shape reads > 2^26 chunks in a call,
+// and 2^26 waves are 2^32 work-items, more than one dispatch holds. The kernel's first argument is its first item.
+template <class K, class... Args>
+static void launch_waves(acc_ctx *ctx, const char *name, K kernel, uint64_t n, Args... args)
+{
+    for (uint64_t first = 0; first < n; first += MAX_GRID * WAVES)
+        launch(ctx, name, kernel, dim3((unsigned)std::min<uint64_t>((n - first + WAVES - 1) / WAVES, MAX_GRID)), dim3(BLOCK), 0, first,
+               args...);
+}
+
+void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keydeps_view *view)
+{
+    if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
+    const CfkResident s = resident_checked(cfk, in->mem);
     if (in->n_pairs >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs in one call (>= 2^32 - 1)");
     hipStream_t st = ctx->stream;
     ctx->kd_valid = false;
     const uint32_t nq = in->n_query, Qp = (uint32_t)in->n_pairs, mem = in->mem;
-    uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
-    cap = std::min(cap, CAP_MAX);
-
-    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", (size_t)nq + 1);
-    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", (size_t)nq + 1);
-    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", (size_t)nq + 1);
     if (nq == 0) {
         if (Qp) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
-        ACC_HIP(hipMemsetAsync(arena_off, 0, 8, st));
-        ACC_HIP(hipMemsetAsync(kd_off, 0, 8, st));
-        ACC_HIP(hipMemsetAsync(u_off, 0, 8, st));
-        ctx->sync();
-        *view = acc_keydeps_view{ 0, 0, 0, 0, 0, arena_off, ctx->get<int32_t>("cq_arena", 1), kd_off,
-                                  ctx->get<uint32_t>("cq_key_idx", 1), u_off, ctx->get<uint32_t>("cq_dep_txn", 1),
-                                  ctx->get<uint64_t>("cq_kd_key", 1) };
-        ctx->kd_view = *view;
-        ctx->kd_valid = true;
+        empty_result(ctx, view);
         return;
     }
 
@@ -505,16 +783,7 @@ void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keyd
     Q.Qp = Qp;
     Q.off = stage_in(ctx, "cq_in_off", in->key_off, (size_t)nq + 1, mem);
     Q.key = stage_in(ctx, "cq_in_key", in->key_code, Qp, mem);
-    Q.qm = stage_in(ctx, "cq_in_qm", in->txn_id.msb, nq, mem);
-    Q.ql = stage_in(ctx, "cq_in_ql", in->txn_id.lsb, nq, mem);
-    Q.qn = stage_in(ctx, "cq_in_qn", in->txn_id.node, nq, mem);
-    if (in->execute_at.msb) {
-        Q.xm = stage_in(ctx, "cq_in_xm", in->execute_at.msb, nq, mem);
-        Q.xl = stage_in(ctx, "cq_in_xl", in->execute_at.lsb, nq, mem);
-        Q.xn = stage_in(ctx, "cq_in_xn", in->execute_at.node, nq, mem);
-    } else {
-        Q.xm = Q.qm; Q.xl = Q.ql; Q.xn = Q.qn;
-    }
+    stage_ids(ctx, Q, in->txn_id, in->execute_at, nq, mem);
 
     // ---- validate: nothing below indexes by an offset or trusts key order before this has passed
     uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
@@ -525,36 +794,133 @@ void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keyd
     check_cq_errors(ctx->pinned[0]);
 
     // ---- locate: prefixes and chunks
-    uint32_t *pair_q = ctx->get<uint32_t>("cq_pair_q", Qp);
-    uint32_t *pair_a = ctx->get<uint32_t>("cq_pair_a", Qp);
-    uint32_t *pair_w = ctx->get<uint32_t>("cq_pair_w", Qp);
-    uint8_t *pair_t0 = ctx->get<uint8_t>("cq_pair_t0", Qp);
-    uint64_t *chunks = ctx->get<uint64_t>("cq_chunks", Qp);
-    uint64_t *chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
-    if (Qp) {
-        launch(ctx, "cq_locate", k_cq_locate, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, pair_q, pair_a, pair_w, pair_t0, chunks);
-        scan<uint64_t, OpAdd<uint64_t>>(ctx, chunks, chunk_off, Qp, true, chunk_off + Qp);
-    } else {
-        ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
+    const Located L = located_bufs(ctx, Qp, false);
+    if (Qp)
+        launch(ctx, "cq_locate", k_cq_locate, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, L.pair_q, L.pair_a, L.pair_w, L.pair_t0,
+               L.chunks);
+    scan_located(ctx, s, Q, L, errs, view);
+}
+
+void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *in, acc_keydeps_view *view)
+{
+    if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
+    const CfkResident s = resident_checked(cfk, in->mem);
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
+    if (in->lane_seg > CH && in->lane_seg != ACC_CFQ_LANE_NONE) fail(ACC_E_ARG, "lane_seg must be 0..256 or ACC_CFQ_LANE_NONE");
+    if (in->n_pairs >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs in one call (>= 2^32 - 1)");
+    if (in->n_ranges >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many ranges in one call (>= 2^32 - 1)");
+    hipStream_t st = ctx->stream;
+    ctx->kd_valid = false;
+    const uint32_t nq = in->n_query, Kp = (uint32_t)in->n_pairs, NR = (uint32_t)in->n_ranges, mem = in->mem;
+    const uint32_t lane_seg = in->lane_seg == ACC_CFQ_LANE_NONE ? 0u : in->lane_seg ? in->lane_seg : LANE_SEG_DEFAULT;
+    if (nq == 0) {
+        if (Kp) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+        if (NR) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+        empty_result(ctx, view);
+        return;
     }
+
+    Queries Q{};       // over the caller's keys until the expansion
+    Q.nq = nq;
+    Q.Qp = Kp;
+    Q.off = stage_in(ctx, "cq_in_off", in->key_off, (size_t)nq + 1, mem);
+    Q.key = stage_in(ctx, "cq_in_key", in->key_code, Kp, mem);
+    stage_ids(ctx, Q, in->txn_id, in->execute_at, nq, mem);
+    Ranges R{};
+    R.key_off = Q.off;
+    R.key_code = Q.key;
+    R.rng_off = stage_in(ctx, "cq_in_roff", in->rng_off, (size_t)nq + 1, mem);
+    R.start = stage_in(ctx, "cq_in_rs", in->rng_start, NR, mem);
+    R.end = stage_in(ctx, "cq_in_re", in->rng_end, NR, mem);
+    R.nr = NR;
+    R.end_inclusive = in->end_inclusive;
+
+    // ---- validate: nothing below indexes by an offset or trusts key or range order before this has passed
+    uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
+    ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
+    launch(ctx, "cq_rvalidate", k_cq_rvalidate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, errs);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    check_cq_errors(ctx->pinned[0]);
+
+    // ---- bounds: the store keys every range covers, the expanded pair offsets
+    uint32_t *rlo = ctx->get<uint32_t>("cq_rlo", NR);
+    uint64_t *rcnt = ctx->get<uint64_t>("cq_rcnt", NR);
+    uint64_t *rcum = ctx->get<uint64_t>("cq_rcum", (size_t)NR + 1);
+    if (NR) {
+        launch(ctx, "cq_rbounds", k_cq_rbounds, dim3(grid_for(NR, BLOCK)), dim3(BLOCK), 0, R, s, rlo, rcnt);
+        scan<uint64_t, OpAdd<uint64_t>>(ctx, rcnt, rcum, NR, true, rcum + NR);
+    } else {
+        ACC_HIP(hipMemsetAsync(rcum, 0, 8, st));
+    }
+    R.lo = rlo;
+    R.cum = rcum;
+    uint64_t *qcnt = ctx->get<uint64_t>("cq_qcnt", nq);
+    uint64_t *xoff64 = ctx->get<uint64_t>("cq_xoff64", (size_t)nq + 1);
+    launch(ctx, "cq_rcount", k_cq_rcount, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, qcnt);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, qcnt, xoff64, nq, true, xoff64 + nq);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, xoff64 + nq, 8, hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, rcum + NR, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    const uint64_t X = ctx->pinned[0], covered = ctx->pinned[1];
+    if (X >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs after expanding the ranges (>= 2^32 - 1)");
+    const uint32_t Xp = (uint32_t)X;
+
+    // ---- expand: every pair's query, key and segment; the lane tier's pairs
+    uint32_t *xoff = ctx->get<uint32_t>("cq_xoff", (size_t)nq + 1);
+    uint64_t *xkey = ctx->get<uint64_t>("cq_xkey", Xp);
+    uint64_t *nlane = ctx->get<uint64_t>("cq_nlane", 1);
+    launch(ctx, "cq_roff", k_cq_roff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq + 1, (const uint64_t *)xoff64, xoff);
+    ACC_HIP(hipMemsetAsync(nlane, 0, 8, st));
+    Q.off = xoff;
+    Q.key = xkey;
+    Q.Qp = Xp;
+    const Located L = located_bufs(ctx, Xp, lane_seg != 0);   // ACC_CFQ_LANE_NONE: every pair takes the chunk path
+    if (Xp)
+        launch(ctx, "cq_rexpand", k_cq_rexpand, dim3(grid_for(Xp, BLOCK)), dim3(BLOCK), 0, Q, R, s, lane_seg, xkey, L.pair_q, L.pair_a,
+               L.pair_w, L.pair_t0, L.chunks, L.lane, L.lane_w, nlane);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 8, nlane, 8, hipMemcpyDeviceToHost, st));   // read at the scan's first sync
+    scan_located(ctx, s, Q, L, errs, view);
+    ctx->stat("cfq.range_pairs", covered);
+    ctx->stat("cfq.lane_pairs", ctx->pinned[8]);
+}
+
+// From the located pairs on: chunk offsets, M and the tie count, the count pass, every offset, emit, KeyDeps.Builder
+static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = Q.nq, Qp = Q.Qp;
+    uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
+    cap = std::min(cap, CAP_MAX);
+    uint32_t *const pair_q = L.pair_q, *const pair_a = L.pair_a, *const pair_w = L.pair_w;
+    uint8_t *const pair_t0 = L.pair_t0;
+    uint64_t *const chunks = L.chunks;
+    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", (size_t)nq + 1);
+    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", (size_t)nq + 1);
+    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", (size_t)nq + 1);
+    uint64_t *chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
+    if (Qp) scan<uint64_t, OpAdd<uint64_t>>(ctx, chunks, chunk_off, Qp, true, chunk_off + Qp);
+    else ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
     ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_off + Qp, 8, hipMemcpyDeviceToHost, st));
     ctx->sync();
     const uint64_t NC = ctx->pinned[0];
     if (NC >= (1ull << 33)) fail(ACC_E_CAP, "the queries read too many segment entries in one call (>= 2^41)");
     uint32_t *chunk_item = ctx->get<uint32_t>("cq_chunk_item", NC);
     const Pairs P{ pair_q, pair_a, pair_w, chunk_off, chunk_item, Qp };
+    const Lanes lanes{ L.lane, L.lane_w };
 
     // ---- M and the tie count, the count pass, every offset
     Part part{ ctx->get<uint64_t>("cq_part_m", NC), ctx->get<uint64_t>("cq_part_l", NC), ctx->get<int32_t>("cq_part_n", NC),
                ctx->get<uint32_t>("cq_part_f", NC) };
     uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
     uint64_t *chunk_eoff = ctx->get<uint64_t>("cq_chunk_eoff", NC + 1);
-    const unsigned gW = (unsigned)((NC + WAVES - 1) / WAVES);
     if (NC) {
         launch(ctx, "cq_items", k_cq_items, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off, chunk_item);
-        launch(ctx, "cq_max", k_cq_max, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, (const uint8_t *)pair_t0, part, chunk_cnt, errs);
-        launch(ctx, "cq_fold", k_cq_fold, dim3(grid_for(Qp, WAVES)), dim3(BLOCK), 0, P, part, errs);
-        launch(ctx, "cq_count", k_cq_count, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, part, chunk_cnt);
+        launch_waves(ctx, "cq_max", k_cq_max, NC, NC, Q, s, P, (const uint8_t *)pair_t0, part, chunk_cnt, errs);
+        launch_waves(ctx, "cq_fold", k_cq_fold, Qp, P, part, errs);
+        launch_waves(ctx, "cq_count", k_cq_count, NC, NC, Q, s, P, part, chunk_cnt);
+        if (L.lane)
+            launch(ctx, "cq_lane_max", k_cq_lane_max, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part, chunk_cnt, errs);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
         ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
@@ -586,8 +952,11 @@ void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keyd
     uint32_t *hit = ctx->get<uint32_t>("cq_hit", E);
     uint64_t *gkey = ctx->get<uint64_t>("cq_gkey", G);
     if (E)
-        launch(ctx, "cq_emit", k_cq_emit, dim3(gW), dim3(BLOCK), 0, NC, Q, s, P, part, (const uint64_t *)chunk_eoff,
+        launch_waves(ctx, "cq_emit", k_cq_emit, NC, NC, Q, s, P, part, (const uint64_t *)chunk_eoff,
                (const uint64_t *)epos, (const uint64_t *)gcnt, (const uint64_t *)goff, tb, hit, gkey);
+    if (E && L.lane)
+        launch(ctx, "cq_lane_emit", k_cq_lane_emit, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part,
+               (const uint64_t *)chunk_eoff, (const uint64_t *)epos, (const uint64_t *)gcnt, (const uint64_t *)goff, tb, hit, gkey);
 
     // ---- KeyDeps.Builder layout
     int32_t *arena = ctx->get<int32_t>("cq_arena", TK + E);

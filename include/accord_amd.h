@@ -923,6 +923,40 @@ typedef struct acc_cfk_queries {
 } acc_cfk_queries;
 int  acc_cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *out_view);
 
+/* acc_cfk_keydeps for queries of both domains: the Range case of InMemoryCommandStore.mapReduceForKey
+ * (impl/InMemoryCommandStore.java:274-289) next to its Key case. A key-domain query (TxnId domain bit 0) lists keys
+ * and is answered exactly as by acc_cfk_keydeps. A range-domain query (domain bit 1: sync points, range reads) lists
+ * ranges and runs the same per-(query, key) scan — prefix below S = executeAt, M, the emit switch, the Timestamp.equals
+ * self-exclusion, the tie rule — on every CFK of commandsForKey.subMap(start, startInclusive, end, endInclusive) of each
+ * of its ranges: the store keys k with s < k <= e (end_inclusive = 1) or s <= k < e (0), range by range in order; the
+ * ranges of a query do not overlap, so its covered keys ascend strictly. A range txn is no CFK member, and a range that
+ * covers no store key contributes nothing. The store's keys are sorted, so the keys a range covers are one run of them
+ * and their entries one span of the entry columns: only those are read, the store is not re-sorted or modified.
+ * Result as acc_cfk_keydeps; for a range-domain query key_idx indexes the list of its covered CFK keys in range order
+ * (the acc_keydeps_mixed convention) and kd_key holds their codes.
+ * lane_seg: covered keys whose whole segment holds at most lane_seg entries (1..256) are scanned one lane per key,
+ * consecutive lanes on consecutive keys, instead of one wave per (query, key); ACC_CFQ_LANE_NONE: never; 0: the library
+ * default. Results do not depend on it.
+ * Errors on top of acc_cfk_keydeps': a range-domain query that lists keys, a key-domain query that lists ranges, a
+ * range with start >= end, ranges of a query out of order or overlapping (rng_end[j-1] > rng_start[j]; touching ranges
+ * are allowed), rng_off not starting at 0 / decreasing / ending off n_ranges, end_inclusive > 1, lane_seg above 256 and
+ * not ACC_CFQ_LANE_NONE: ACC_E_ARG; more than 2^32 - 2 (query, key) pairs after expansion: ACC_E_CAP. */
+#define ACC_CFQ_LANE_NONE 0xFFFFFFFFu
+typedef struct acc_cfk_mixed_queries {
+    uint32_t    n_query, mem;          /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t    n_pairs;               /* key_off[n_query] */
+    uint64_t    n_ranges;              /* rng_off[n_query] */
+    acc_ts_cols txn_id;                /* [n_query]; domain bit (lsb & 1) picks keys or ranges */
+    acc_ts_cols execute_at;            /* msb == NULL: executeAt = txnId for every query */
+    const uint32_t *key_off;           /* [n_query+1] */
+    const uint64_t *key_code;          /* [n_pairs] sorted unique per key-domain query */
+    const uint32_t *rng_off;           /* [n_query+1] */
+    const uint64_t *rng_start, *rng_end; /* [n_ranges] per range-domain query: sorted, non-overlapping, start < end */
+    uint32_t    end_inclusive;         /* 1: (s, e]; 0: [s, e) — the store's Range bound type */
+    uint32_t    lane_seg;              /* see above; 0: the library default */
+} acc_cfk_mixed_queries;
+int  acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *out_view);
+
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
  * A CommandStore's MaxConflicts is the pointwise max of every (keysOrRanges, executeAt) update it received
