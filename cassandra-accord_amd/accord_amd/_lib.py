@@ -57,7 +57,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
 
 
 class Opts(C.Structure):
-    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("cfk_hot", C.c_uint32), ("lv_tier", C.c_uint32),
+    _fields_ = [("flags", C.c_uint32), ("wave_grid_max", C.c_uint32), ("cfk_hot", C.c_uint32), ("lv_tier", C.c_uint32),
                 ("lv_chunk", C.c_uint32), ("cfq_wave_cap", C.c_uint32)]
 
 

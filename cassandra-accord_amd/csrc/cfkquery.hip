@@ -52,7 +52,6 @@ namespace cq {
 
 constexpr uint32_t CH = 256;          // segment entries per work chunk: one wave, four per lane
 constexpr uint32_t CAP_MAX = 1024;    // hits of a query the one-wave build tier holds in LDS (u64 each, per wave)
-constexpr uint64_t MAX_GRID = 1u << 23;     // blocks of one launch (x BLOCK = 2^31 work-items; a dispatch holds < 2^32)
 constexpr uint32_t LANE_SEG_DEFAULT = 16;   // acc_cfk_mixed_queries::lane_seg == 0 (the measured table)
 
 enum : uint64_t { E_KIND_ARG = 1, E_KIND_STATE = 2, E_RANGE = 4, E_OFF = 8, E_KEYS = 16, E_TIE = 32,
@@ -409,14 +408,15 @@ __global__ __launch_bounds__(BLOCK) void k_cq_header(Queries Q, const uint32_t *
 
 // build tier 1, one wave per query with 1..cap hits: sort in LDS, unique in place, every hit's position by binary search.
 // Leaves the sorted unique txn indices in the query's first hit slots (uflag 1), the rest flagged 0.
-__global__ __launch_bounds__(BLOCK) void k_cq_build_wave(uint32_t nq, const uint32_t *__restrict__ qoff, const uint64_t *__restrict__ epos,
+__global__ __launch_bounds__(BLOCK) void k_cq_build_wave(uint64_t first, uint32_t nq, const uint32_t *__restrict__ qoff, const uint64_t *__restrict__ epos,
                                                          const uint64_t *__restrict__ arena_off, const uint64_t *__restrict__ kd_off,
                                                          uint32_t cap, const uint32_t *__restrict__ hit, int32_t *__restrict__ arena,
                                                          uint32_t *__restrict__ uflag, uint32_t *__restrict__ uval)
 {
     __shared__ uint64_t lds[WAVES][CAP_MAX];
-    const uint32_t q = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (q >= nq) return;
+    const uint64_t qi = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (qi >= nq) return;
+    const uint32_t q = (uint32_t)qi;
     const uint64_t h0 = epos[qoff[q]];
     const uint64_t h64 = epos[qoff[q + 1]] - h0;
     if (h64 == 0 || h64 > cap) return;
@@ -754,16 +754,6 @@ static void stage_ids(acc_ctx *ctx, Queries &Q, const acc_ts_cols &txn_id, const
 
 static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view);
 
-// one wave per item (chunk or pair), in launches of at most MAX_GRID blocks: the zipf shape reads > 2^26 chunks in a call,
-// and 2^26 waves are 2^32 work-items, more than one dispatch holds. The kernel's first argument is its first item.
-template <class K, class... Args>
-static void launch_waves(acc_ctx *ctx, const char *name, K kernel, uint64_t n, Args... args)
-{
-    for (uint64_t first = 0; first < n; first += MAX_GRID * WAVES)
-        launch(ctx, name, kernel, dim3((unsigned)std::min<uint64_t>((n - first + WAVES - 1) / WAVES, MAX_GRID)), dim3(BLOCK), 0, first,
-               args...);
-}
-
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keydeps_view *view)
 {
     if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
@@ -889,6 +879,7 @@ void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *
 static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
 {
     hipStream_t st = ctx->stream;
+    const uint64_t wl0 = ctx->wave_launches;
     const uint32_t nq = Q.nq, Qp = Q.Qp;
     uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
     cap = std::min(cap, CAP_MAX);
@@ -971,8 +962,8 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
         uint32_t *uval = ctx->get<uint32_t>("cq_uval", E);
         uint32_t *upos = ctx->get<uint32_t>("cq_upos", E + 1);
         if (E > G)
-            launch(ctx, "cq_build_wave", k_cq_build_wave, dim3(grid_for(nq, WAVES)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)epos,
-                   (const uint64_t *)arena_off, (const uint64_t *)kd_off, cap, (const uint32_t *)hit, arena, uflag, uval);
+            launch_waves(ctx, "cq_build_wave", k_cq_build_wave, nq, nq, Q.off, (const uint64_t *)epos, (const uint64_t *)arena_off,
+                         (const uint64_t *)kd_off, cap, (const uint32_t *)hit, arena, uflag, uval);
         if (G) {
             const uint64_t *sk = radix_sort_keys(ctx, "cq_rs", gkey, G, 0, tb + qbits);
             uint32_t *gflag = ctx->get<uint32_t>("cq_gflag", G);
@@ -1000,6 +991,7 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
     ctx->stat("cfq.chunks", NC);
     ctx->stat("cfq.hits", E);
     ctx->stat("cfq.sorted_hits", G);
+    ctx->stat("cfq.wave_launches", ctx->wave_launches - wl0);
     *view = acc_keydeps_view{ nq, TK + E, TK, TU, E, arena_off, arena, kd_off, key_idx, u_off, dep_txn, kd_key };
     ctx->kd_view = *view;
     ctx->kd_valid = true;

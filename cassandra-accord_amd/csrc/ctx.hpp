@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +23,11 @@ struct Error {
 };
 
 [[noreturn]] inline void fail(int code, const std::string &msg) { throw Error{code, msg}; }
+
+constexpr int BLOCK = 256;
+constexpr int WAVES = BLOCK / 64;
+// blocks of one sliced launch (launch_waves): x BLOCK = 2^31 work-items, and a dispatch holds < 2^32
+constexpr uint64_t MAX_GRID = 1u << 23;
 
 #define ACC_HIP(expr)                                                                          \
     do {                                                                                       \
@@ -78,6 +84,12 @@ struct acc_ctx {
     std::unordered_map<std::string, OsState> os_state;
     uint32_t flags = 0;
     acc_opts opts{};   // as given to acc_create (flags == opts.flags)
+    // blocks one sliced launch may hold (acc::launch_waves): opts.wave_grid_max, 0 or anything above MAX_GRID = MAX_GRID
+    uint64_t wave_grid() const
+    {
+        return opts.wave_grid_max ? std::min<uint64_t>(opts.wave_grid_max, acc::MAX_GRID) : acc::MAX_GRID;
+    }
+    uint64_t wave_launches = 0;   // launches launch_waves has issued on this context (an entry point publishes its increase)
     std::string last_error;
     // a second context on the same device (own stream, buffers, pinned staging), created on first use: the RangeDeps
     // half of acc_partial_deps_batch runs on it from a second host thread, concurrently with the KeyDeps half
@@ -278,10 +290,19 @@ struct NsScope {
 
 // Launch a kernel on the context stream (or the side stream selected by launch_stream); with ACC_OPT_TIMING, bracket it with HIP events recorded on
 // that same stream (so the interval is the kernel's own device time).
+// One dispatch holds fewer than 2^32 work-items along x; a larger grid.x * block.x wraps without an error from the runtime.
+constexpr bool fits_dispatch(uint64_t grid_x, uint64_t block_x) { return grid_x * block_x < (1ull << 32); }
+static_assert(!fits_dispatch(1ull << 24, BLOCK), "2^24 blocks of 256 are 2^32 work-items: one too many");
+static_assert(fits_dispatch((1ull << 24) - 1, BLOCK), "2^24 - 1 blocks of 256 fit");
+static_assert(fits_dispatch(MAX_GRID, BLOCK), "a full slice of launch_waves fits");
+
 template <class K, class... Args>
 inline void launch(acc_ctx *ctx, const char *name, K kernel, dim3 grid, dim3 block, size_t shmem, Args... args)
 {
     if (grid.x == 0 || grid.y == 0 || grid.z == 0) return;
+    if (!fits_dispatch(grid.x, block.x))
+        fail(ACC_E_CAP, std::string(name) + ": " + std::to_string(grid.x) + " blocks of " + std::to_string(block.x) +
+                            " threads are 2^32 work-items or more, which one dispatch does not hold");
     PendingEvent pe{};
     const bool timed = ctx->timed(name);
     if (timed) {
@@ -302,6 +323,29 @@ inline unsigned grid_for(size_t n, unsigned per_block)
 {
     size_t g = (n + per_block - 1) / per_block;
     return (unsigned)(g ? g : 1);
+}
+
+// n items, per_block of them to a block, in launches (slices) of at most ctx->wave_grid() blocks, and never more blocks
+// than fit one dispatch at this block size. The kernel's first argument is the index of its launch's first item; the
+// last slice's grid is the rounded-up remainder. Nothing is launched for n == 0.
+template <class K, class... Args>
+inline void launch_sliced(acc_ctx *ctx, const char *name, K kernel, uint64_t n, unsigned per_block, dim3 block, size_t shmem,
+                          Args... args)
+{
+    const uint64_t lim = std::min<uint64_t>(ctx->wave_grid(), ((1ull << 32) - 1) / block.x);
+    for (uint64_t first = 0; first < n; first += lim * per_block) {
+        launch(ctx, name, kernel, dim3((unsigned)std::min<uint64_t>((n - first + per_block - 1) / per_block, lim)), block, shmem,
+               first, args...);
+        ctx->wave_launches += 1;
+    }
+}
+
+// One wave per item: 2^26 waves are 2^32 work-items, more than one dispatch holds, and item counts read back from the
+// device (chunks of hot keys) have no cap of their own.
+template <class K, class... Args>
+inline void launch_waves(acc_ctx *ctx, const char *name, K kernel, uint64_t n, Args... args)
+{
+    launch_sliced(ctx, name, kernel, n, WAVES, dim3(BLOCK), 0, args...);
 }
 
 // Copy caller input (host or device) into a device buffer owned by the context.

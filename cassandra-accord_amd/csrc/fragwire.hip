@@ -57,14 +57,14 @@ __device__ __forceinline__ uint64_t val_code(const uint32_t *v, uint64_t j, uint
 
 // ---------------------------------------------------------------- sender
 // per fragment (one wave): the varint bytes of its TxnIds, its key-bit bytes, its key span and largest count
-__global__ __launch_bounds__(BLOCK) void k_fe_meas(uint64_t F, const uint32_t *__restrict__ hdr,
+__global__ __launch_bounds__(BLOCK) void k_fe_meas(uint64_t first, uint64_t F, const uint32_t *__restrict__ hdr,
                                                    const uint64_t *__restrict__ ko, const uint64_t *__restrict__ vo,
                                                    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                    uint64_t *__restrict__ vb, uint64_t *__restrict__ kb,
                                                    uint64_t *__restrict__ fmin, uint64_t *__restrict__ fmax,
                                                    uint32_t *__restrict__ fcm)
 {
-    const uint64_t f = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t f = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (f >= F) return;
     const uint32_t t = hdr[4 * f], nk = hdr[4 * f + 1], nv = hdr[4 * f + 2];
@@ -121,14 +121,14 @@ __device__ __forceinline__ void put_bit(uint8_t *buf, uint64_t byte0, uint64_t b
 }
 
 // per fragment (one wave): slot bit, counts, keys, TxnId varints, key bits into its destination's message (zeroed)
-__global__ __launch_bounds__(BLOCK) void k_fe_write(uint64_t F, uint32_t W, const Msg *__restrict__ msg,
+__global__ __launch_bounds__(BLOCK) void k_fe_write(uint64_t first, uint64_t F, uint32_t W, const Msg *__restrict__ msg,
                                                     const uint32_t *__restrict__ hdr, const uint64_t *__restrict__ ko,
                                                     const uint64_t *__restrict__ vo, const uint64_t *__restrict__ oo,
                                                     const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                     const int32_t *__restrict__ k2v, const uint64_t *__restrict__ vbo,
                                                     const uint64_t *__restrict__ kbo, uint8_t *__restrict__ buf)
 {
-    const uint64_t f = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t f = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (f >= F) return;
     const uint32_t t = hdr[4 * f], nk = hdr[4 * f + 1], nv = hdr[4 * f + 2];
@@ -262,11 +262,11 @@ __global__ __launch_bounds__(BLOCK) void k_fd_counts(uint64_t F, uint32_t W, uin
 }
 
 // per fragment (one wave): entries = set key bits (every TxnId for one key) -> no = nk + entries
-__global__ __launch_bounds__(BLOCK) void k_fd_no(uint64_t F, uint32_t W, const Msg *__restrict__ msg,
+__global__ __launch_bounds__(BLOCK) void k_fd_no(uint64_t first, uint64_t F, uint32_t W, const Msg *__restrict__ msg,
                                                  const uint8_t *__restrict__ buf, uint32_t *__restrict__ hdr,
                                                  const uint64_t *__restrict__ kbo, uint64_t *__restrict__ a_no)
 {
-    const uint64_t f = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t f = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (f >= F) return;
     const uint32_t nk = hdr[4 * f + 1], nv = hdr[4 * f + 2];
@@ -287,7 +287,7 @@ __global__ __launch_bounds__(BLOCK) void k_fd_no(uint64_t F, uint32_t W, const M
 __device__ __forceinline__ bool kbit(const uint8_t *kp, uint64_t b) { return (kp[b >> 3] >> (b & 7)) & 1u; }
 
 // per fragment (one wave): keys, TxnIds (varints decoded 64 bytes at a time), keysToTxnIds from the key bits
-__global__ __launch_bounds__(BLOCK) void k_fd_unpack(uint64_t F, uint32_t W, const Msg *__restrict__ msg,
+__global__ __launch_bounds__(BLOCK) void k_fd_unpack(uint64_t first, uint64_t F, uint32_t W, const Msg *__restrict__ msg,
                                                      const uint8_t *__restrict__ buf, const uint32_t *__restrict__ hdr,
                                                      const uint64_t *__restrict__ sk, const uint64_t *__restrict__ sv,
                                                      const uint64_t *__restrict__ svb, const uint64_t *__restrict__ skb,
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(BLOCK) void k_fd_unpack(uint64_t F, uint32_t W, con
                                                      uint32_t *__restrict__ vals, int32_t *__restrict__ k2v,
                                                      uint64_t *__restrict__ err)
 {
-    const uint64_t f = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t f = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (f >= F) return;
     const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
@@ -390,8 +390,8 @@ uint8_t *frag_encode(acc_ctx *ctx, uint32_t W, const uint64_t *fo, const uint64_
         scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 3, si, so, sn, true, stot);
         uint64_t *fmin = ctx->get<uint64_t>("fe_fmin", F), *fmax = ctx->get<uint64_t>("fe_fmax", F);
         uint32_t *fcm = ctx->get<uint32_t>("fe_fcm", F);
-        launch(ctx, "fe_meas", k_fe_meas, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F, hdr,
-               (const uint64_t *)ko, (const uint64_t *)vo, keys, vals, vb, kb, fmin, fmax, fcm);
+        launch_waves(ctx, "fe_meas", k_fe_meas, F, F, hdr,
+                     (const uint64_t *)ko, (const uint64_t *)vo, keys, vals, vb, kb, fmin, fmax, fcm);
         uint64_t *fo_d = ctx->get<uint64_t>("fe_fo", (size_t)W + 1);
         ACC_HIP(hipMemcpyAsync(fo_d, fo, 8 * ((size_t)W + 1), hipMemcpyHostToDevice, st));
         launch(ctx, "fe_dest", k_fe_dest, dim3(W * FE_DB), dim3(BLOCK), 0, (const uint64_t *)fo_d, (const uint64_t *)fmin,
@@ -453,9 +453,9 @@ uint8_t *frag_encode(acc_ctx *ctx, uint32_t W, const uint64_t *fo, const uint64_
     for (uint32_t d = 0; d < W; ++d)
         ACC_HIP(hipMemcpyAsync(buf + boff[d], head.data() + (size_t)d * HDR_WORDS, HDR_WORDS * 4, hipMemcpyHostToDevice, st));
     if (F)
-        launch(ctx, "fe_write", k_fe_write, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F, W,
-               (const Msg *)dm, hdr, (const uint64_t *)ko, (const uint64_t *)vo, (const uint64_t *)oo, keys, vals, k2v,
-               (const uint64_t *)vbo, (const uint64_t *)kbo, buf);
+        launch_waves(ctx, "fe_write", k_fe_write, F, F, W,
+                     (const Msg *)dm, hdr, (const uint64_t *)ko, (const uint64_t *)vo, (const uint64_t *)oo, keys, vals, k2v,
+                     (const uint64_t *)vbo, (const uint64_t *)kbo, buf);
     // (the host vectors the copies read stay alive until the stream drains)
     ctx->sync();
     uint64_t raw = 16 * F + 8 * ko_h[W] + 4 * vo_h[W] + 4 * oo_h[W];
@@ -524,8 +524,8 @@ void frag_decode(acc_ctx *ctx, uint32_t W, uint32_t rank, uint32_t n_global, con
         uint64_t *so[4] = { o[0], o[1], o[2], o[3] }, *stot[4] = { o[0] + F, o[1] + F, o[2] + F, o[3] + F };
         const size_t sn[4] = { F, F, F, F };
         scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 4, si, so, sn, true, stot);
-        launch(ctx, "fd_no", k_fd_no, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F, W, (const Msg *)dm,
-               recv, hdr, (const uint64_t *)o[3], a[4]);
+        launch_waves(ctx, "fd_no", k_fd_no, F, F, W, (const Msg *)dm,
+                     recv, hdr, (const uint64_t *)o[3], a[4]);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, a[4], o[4], F, true, o[4] + F);
     } else {
         for (int q = 0; q < 5; ++q) ACC_HIP(hipMemsetAsync(o[q], 0, 8, st));
@@ -551,9 +551,9 @@ void frag_decode(acc_ctx *ctx, uint32_t W, uint32_t rank, uint32_t n_global, con
     uint32_t *vals = ctx->get<uint32_t>("fd_vals", NV);
     int32_t *k2v = ctx->get<int32_t>("fd_k2v", NO);
     if (F)
-        launch(ctx, "fd_unpack", k_fd_unpack, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F, W,
-               (const Msg *)dm, recv, (const uint32_t *)hdr, (const uint64_t *)o[0], (const uint64_t *)o[1],
-               (const uint64_t *)o[2], (const uint64_t *)o[3], (const uint64_t *)o[4], keys, vals, k2v, err);
+        launch_waves(ctx, "fd_unpack", k_fd_unpack, F, F, W,
+                     (const Msg *)dm, recv, (const uint32_t *)hdr, (const uint64_t *)o[0], (const uint64_t *)o[1],
+                     (const uint64_t *)o[2], (const uint64_t *)o[3], (const uint64_t *)o[4], keys, vals, k2v, err);
     ACC_HIP(hipMemcpyAsync(ctx->pinned, err, 8, hipMemcpyDeviceToHost, st));
     ctx->sync();
     if (ctx->pinned[0]) fail(ACC_E_STATE, "malformed fragment message");

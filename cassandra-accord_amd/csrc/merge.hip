@@ -409,7 +409,7 @@ __device__ unsigned long long *g_ml_prof;
 #define ML_PH(k) ((void)0)
 #endif
 
-__global__ __launch_bounds__(ML_NT) void k_m_lds(uint32_t ng, const uint64_t *__restrict__ grp_off, const uint64_t *__restrict__ key_off,
+__global__ __launch_bounds__(ML_NT) void k_m_lds(uint64_t first, uint32_t ng, const uint64_t *__restrict__ grp_off, const uint64_t *__restrict__ key_off,
                                                  const uint64_t *__restrict__ key_code, const uint64_t *__restrict__ val_off,
                                                  const uint32_t *__restrict__ txn_rank, const uint64_t *__restrict__ k2v_off,
                                                  const int32_t *__restrict__ k2v, MlPlan pl, MlOut o)
@@ -428,7 +428,7 @@ __global__ __launch_bounds__(ML_NT) void k_m_lds(uint32_t ng, const uint64_t *__
     __shared__ uint32_t scan_lds[ML_NT / 64];
     __shared__ uint32_t rsm[ML_REP + 1];   // run starts of the merge tree
     __shared__ uint32_t wpre[ML_WB];       // TxnId bitmap: set bits before each word
-    const uint32_t gi = blockIdx.x;
+    const uint32_t gi = (uint32_t)first + blockIdx.x;   // one block per group, the launch's grid ends at ng
     const uint32_t tid = threadIdx.x;
 #ifdef ACC_ML_PROF
     unsigned long long ml_t = clock64();
@@ -765,7 +765,7 @@ void keydeps_merge(acc_ctx *ctx, const acc_merge_in *in, acc_merge_view *view)
             ACC_HIP(hipMemsetAsync(mlp, 0, 64, st));
             ACC_HIP(hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ml_prof), &mlp, sizeof mlp, 0, hipMemcpyHostToDevice, st));
 #endif
-            launch(ctx, "m_lds", k_m_lds, dim3(ng), dim3(ML_NT), pl.bytes, ng, grp_off, key_off, key_code, val_off, txn_rank,
+            launch_sliced(ctx, "m_lds", k_m_lds, ng, 1, dim3(ML_NT), pl.bytes, ng, grp_off, key_off, key_code, val_off, txn_rank,
                    k2v_off, k2v, pl, mo);
 #ifdef ACC_ML_PROF
             {

@@ -10,9 +10,6 @@
 
 namespace acc {
 
-constexpr int BLOCK = 256;
-constexpr int WAVES = BLOCK / 64;
-
 // ---------------------------------------------------------------- wave helpers
 
 __device__ __forceinline__ uint32_t lane_id() { return threadIdx.x & 63u; }

@@ -218,10 +218,10 @@ struct RcChunks {
 };
 
 // one wave per chunk: match count (and its item's running total)
-__global__ __launch_bounds__(BLOCK) void k_rc_count(uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
+__global__ __launch_bounds__(BLOCK) void k_rc_count(uint64_t first, uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
                                                     uint32_t *__restrict__ chunk_cnt, unsigned long long *__restrict__ item_cnt)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const uint32_t item = rc_upper64(ch.chunk_off, ch.Qp + 1, cw) - 1;
     const uint32_t q = ch.item_q[item];
@@ -242,10 +242,10 @@ __global__ __launch_bounds__(BLOCK) void k_rc_count(uint64_t nchunks, RcCfk c, R
 }
 
 // the same walk, compacting matches in position order: (query << rbits | TxnId rank) per emitted entry
-__global__ __launch_bounds__(BLOCK) void k_rc_emit(uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
+__global__ __launch_bounds__(BLOCK) void k_rc_emit(uint64_t first, uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
                                                    const uint64_t *__restrict__ chunk_eoff, int rbits, uint64_t *__restrict__ ent)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const uint32_t item = rc_upper64(ch.chunk_off, ch.Qp + 1, cw) - 1;
     const uint32_t q = ch.item_q[item];
@@ -350,6 +350,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     if (rq->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
     if (rq->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
     hipStream_t st = ctx->stream;
+    const uint64_t wl0 = ctx->wave_launches;
     ctx->kd_valid = false;
     const CfkBuild s = cfk_snapshot(ctx, in);
     const uint32_t nq = rq->n_query, n = s.n;
@@ -414,9 +415,8 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     uint64_t *chunk_eoff = ctx->get<uint64_t>("rc_chunk_eoff", NC + 1);
     ACC_HIP(hipMemsetAsync(item_cnt, 0, (size_t)Qp * 8, st));
     RcChunks chs{ chunk_off, item_q, item_a, item_w, qlo, qeq, qmask, Qp };
-    const unsigned gW = (unsigned)((NC + WAVES - 1) / WAVES);
     if (NC) {
-        launch(ctx, "rc_count", k_rc_count, dim3(gW), dim3(BLOCK), 0, NC, c, prm, chs, chunk_cnt, item_cnt);
+        launch_waves(ctx, "rc_count", k_rc_count, NC, NC, c, prm, chs, chunk_cnt, item_cnt);
         launch(ctx, "rc_widen", k_widen_u32, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, (size_t)NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt64, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
@@ -442,7 +442,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     const int qbits = bits_for(nq ? nq - 1 : 0);
     if (E && qbits + rbits > 64) fail(ACC_E_CAP, "too many queries for the (query, TxnId rank) composite key");
     uint64_t *ent = ctx->get<uint64_t>("rc_ent", E);
-    if (E) launch(ctx, "rc_emit", k_rc_emit, dim3(gW), dim3(BLOCK), 0, NC, c, prm, chs, (const uint64_t *)chunk_eoff, rbits, ent);
+    if (E) launch_waves(ctx, "rc_emit", k_rc_emit, NC, NC, c, prm, chs, (const uint64_t *)chunk_eoff, rbits, ent);
 
     // ---- Deps.Builder layout
     uint64_t *arena_off = ctx->get<uint64_t>("rc_arena_off", (size_t)nq + 1);
@@ -478,6 +478,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     ctx->stat("recovery.items", Qp);
     ctx->stat("recovery.chunks", NC);
     ctx->stat("recovery.entries", E);
+    ctx->stat("recovery.wave_launches", ctx->wave_launches - wl0);
     *view = acc_keydeps_view{ nq, TK + E, TK, TU, E, arena_off, arena, kd_off, key_idx, u_off, dep_txn, nullptr };
     ctx->kd_view = *view;
     ctx->kd_valid = true;
@@ -701,11 +702,11 @@ struct RrChunks {
 };
 
 template <bool EMIT>
-__global__ __launch_bounds__(BLOCK) void k_rr_scan(uint64_t nchunks, RrCmds c, RrQueries Q, RcParams p, RrChunks ch,
+__global__ __launch_bounds__(BLOCK) void k_rr_scan(uint64_t first, uint64_t nchunks, RrCmds c, RrQueries Q, RcParams p, RrChunks ch,
                                                    uint32_t *__restrict__ chunk_cnt, const uint64_t *__restrict__ chunk_eoff,
                                                    uint64_t *__restrict__ ent)
 {
-    const uint64_t cw = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const uint32_t q = rc_upper64(ch.chunk_off, ch.nq + 1, cw) - 1;
     const uint32_t i = ch.qa[q] + (uint32_t)(cw - ch.chunk_off[q]) * 64u + lane_id();
@@ -839,6 +840,7 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     if (ri->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
     if (ci->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
     hipStream_t st = ctx->stream;
+    const uint64_t wl0 = ctx->wave_launches;
     ctx->rd_valid = false;
     const uint32_t n = ci->n_cmd, nq = ri->n_query;
     const uint32_t cm = ci->mem, qmem = ri->mem;
@@ -951,10 +953,9 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     uint32_t *chunk_cnt = ctx->get<uint32_t>("rr_chunk_cnt", NC);
     uint64_t *chunk_cnt64 = ctx->get<uint64_t>("rr_chunk_cnt64", NC);
     uint64_t *chunk_eoff = ctx->get<uint64_t>("rr_chunk_eoff", NC + 1);
-    const unsigned gW = (unsigned)((NC + WAVES - 1) / WAVES);
     if (NC) {
-        launch(ctx, "rr_count", k_rr_scan<false>, dim3(gW), dim3(BLOCK), 0, NC, c, Q, prm, ch, chunk_cnt,
-               (const uint64_t *)nullptr, (uint64_t *)nullptr);
+        launch_waves(ctx, "rr_count", k_rr_scan<false>, NC, NC, c, Q, prm, ch, chunk_cnt, (const uint64_t *)nullptr,
+                     (uint64_t *)nullptr);
         launch(ctx, "rr_widen", k_widen_u32, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, (size_t)NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt64, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
@@ -965,8 +966,8 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     const uint64_t E = ctx->pinned[0];
     if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 range recovery-scan entries in one call");
     uint64_t *ent = ctx->get<uint64_t>("rr_ent", E);
-    if (E) launch(ctx, "rr_emit", k_rr_scan<true>, dim3(gW), dim3(BLOCK), 0, NC, c, Q, prm, ch, (uint32_t *)nullptr,
-                  (const uint64_t *)chunk_eoff, ent);
+    if (E) launch_waves(ctx, "rr_emit", k_rr_scan<true>, NC, NC, c, Q, prm, ch, (uint32_t *)nullptr,
+                        (const uint64_t *)chunk_eoff, ent);
 
     // ---- 4. TreeMap<Range, List> + Deps.Builder: sorted unique (query, range, TxnId)
     uint64_t U = 0;
@@ -1030,6 +1031,7 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     }
     ctx->stat("recovery.range_chunks", NC);
     ctx->stat("recovery.range_entries", U);
+    ctx->stat("recovery.range_wave_launches", ctx->wave_launches - wl0);
     *view = acc_rangedeps_view{ nq, ND, G + U, G, TU, U, dict_s, dict_e, arena_off, arena, rd_off, range_id, u_off, dep_txn };
     ctx->rd_view = *view;
     ctx->rd_valid = true;

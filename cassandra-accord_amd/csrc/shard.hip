@@ -107,7 +107,7 @@ __global__ __launch_bounds__(BLOCK) void k_sh_reply_sizes(uint64_t F, const uint
 }
 
 // one wave per reply: copy its three segments from the received streams into the merge layout
-__global__ __launch_bounds__(BLOCK) void k_sh_gather(uint64_t F, const uint32_t *__restrict__ perm,
+__global__ __launch_bounds__(BLOCK) void k_sh_gather(uint64_t first, uint64_t F, const uint32_t *__restrict__ perm,
                                                      const uint64_t *__restrict__ sk, const uint64_t *__restrict__ sv,
                                                      const uint64_t *__restrict__ so, const uint64_t *__restrict__ rk,
                                                      const uint64_t *__restrict__ rv, const uint64_t *__restrict__ ro,
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(BLOCK) void k_sh_gather(uint64_t F, const uint32_t 
                                                      const int32_t *__restrict__ k2v, uint64_t *__restrict__ m_keys,
                                                      uint32_t *__restrict__ m_vals, int32_t *__restrict__ m_k2v)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t r = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (r >= F) return;
     const uint32_t f = perm[r];
@@ -398,7 +398,7 @@ __global__ __launch_bounds__(BLOCK) void k_shr_pack(uint32_t n, uint32_t world, 
 }
 
 // one wave per reply: its ranges, raw TxnIds and ints from the received streams into the Deps.merge input layout
-__global__ __launch_bounds__(BLOCK) void k_shr_gather(uint64_t F, const uint32_t *__restrict__ perm,
+__global__ __launch_bounds__(BLOCK) void k_shr_gather(uint64_t first, uint64_t F, const uint32_t *__restrict__ perm,
                                                       const uint64_t *__restrict__ sk, const uint64_t *__restrict__ sv,
                                                       const uint64_t *__restrict__ so, const uint64_t *__restrict__ rk,
                                                       const uint64_t *__restrict__ rv, const uint64_t *__restrict__ ro,
@@ -408,7 +408,7 @@ __global__ __launch_bounds__(BLOCK) void k_shr_gather(uint64_t F, const uint32_t
                                                       uint64_t *__restrict__ lsb, int32_t *__restrict__ node,
                                                       int32_t *__restrict__ m_k2v)
 {
-    const uint64_t r = (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const uint64_t r = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     const uint32_t lane = lane_id();
     if (r >= F) return;
     const uint32_t f = perm[r];
@@ -560,9 +560,9 @@ void shard_merge(acc_ctx *ctx, const acc_frag_recv *in, acc_merge_view *view)
     uint64_t *m_keys = ctx->get<uint64_t>("shr_m_keys", NK);
     uint32_t *m_vals = ctx->get<uint32_t>("shr_m_vals", NV);
     int32_t *m_k2v = ctx->get<int32_t>("shr_m_k2v", NO);
-    launch(ctx, "shr_gather", k_sh_gather, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F, (const uint32_t *)fs.vals,
-           (const uint64_t *)sk, (const uint64_t *)sv, (const uint64_t *)so, (const uint64_t *)rk, (const uint64_t *)rv,
-           (const uint64_t *)ro, keys, vals, k2v, m_keys, m_vals, m_k2v);
+    launch_waves(ctx, "shr_gather", k_sh_gather, F, F, (const uint32_t *)fs.vals,
+                 (const uint64_t *)sk, (const uint64_t *)sv, (const uint64_t *)so, (const uint64_t *)rk, (const uint64_t *)rv,
+                 (const uint64_t *)ro, keys, vals, k2v, m_keys, m_vals, m_k2v);
     // ---- fused reduce: sizes (and the key-order check), offsets, writes
     Fuse fz{};
     fz.ng = n_groups; fz.grp_off = grp_off; fz.rk = rk; fz.rv = rv; fz.ro = ro; fz.keys = m_keys; fz.vals = m_vals;
@@ -716,10 +716,10 @@ void range_merge(acc_ctx *ctx, uint32_t world, uint32_t rank, uint32_t n_global,
     uint64_t *ka = ctx->get<uint64_t>("ka", NR + 1), *kb = ctx->get<uint64_t>("kb", NR + 1);
     uint64_t *msb = ctx->get<uint64_t>("msb", NV + 1), *lsb = ctx->get<uint64_t>("lsb", NV + 1);
     int32_t *node = ctx->get<int32_t>("node", NV + 1), *mk2v = ctx->get<int32_t>("k2v", NO + 1);
-    launch(ctx, "shr_gather", k_shr_gather, dim3((unsigned)((F + WAVES - 1) / WAVES)), dim3(BLOCK), 0, F,
-           (const uint32_t *)fs.vals, (const uint64_t *)sk, (const uint64_t *)sv, (const uint64_t *)so, (const uint64_t *)rk,
-           (const uint64_t *)rv, (const uint64_t *)ro, static_cast<const uint64_t *>(recv[1]),
-           static_cast<const uint64_t *>(recv[2]), static_cast<const int32_t *>(recv[3]), ka, kb, msb, lsb, node, mk2v);
+    launch_waves(ctx, "shr_gather", k_shr_gather, F, F,
+                 (const uint32_t *)fs.vals, (const uint64_t *)sk, (const uint64_t *)sv, (const uint64_t *)so, (const uint64_t *)rk,
+                 (const uint64_t *)rv, (const uint64_t *)ro, static_cast<const uint64_t *>(recv[1]),
+                 static_cast<const uint64_t *>(recv[2]), static_cast<const int32_t *>(recv[3]), ka, kb, msb, lsb, node, mk2v);
     ACC_HIP(hipMemcpyAsync(ctx->pinned, err, 8, hipMemcpyDeviceToHost, st));
     ctx->sync();
     if (ctx->pinned[0]) fail(ACC_E_ARG, "received a RangeDeps fragment for a txn that is not homed on this rank");

@@ -123,7 +123,8 @@ typedef struct acc_ctx acc_ctx;
  * a code path; zero everywhere = the defaults. */
 typedef struct acc_opts {
     uint32_t flags;           /* ACC_OPT_* */
-    uint32_t reserved;
+    uint32_t wave_grid_max;   /* wave-per-item launches (chunk scans of acc_cfk_keydeps and of the recovery scans) are
+                                 issued in slices of at most this many blocks (0: 2^23; clamped to 1..2^23) */
     uint32_t cfk_hot;         /* acc_cfk_apply: keys with more than this many sorted elements take the closed form
                                  of the replay (0: 64) */
     uint32_t lv_tier;         /* ACC_LV_* */

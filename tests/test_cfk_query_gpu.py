@@ -232,11 +232,9 @@ WIDTHS = [(63, 10), (64, 10), (65, 10), (128, 10), (129, 10), (CHUNK - 1, 10), (
           (2 * CHUNK + 1, 10), (2 * CHUNK + 1, 300)]
 
 
-@pytest.mark.parametrize("L,tail", WIDTHS)
-def test_segment_widths(ctx, ctx_small_cap, L, tail):
-    from accord_amd.deps import CfkStore
-    upd = width_stream(L, tail)
-    ob = CC.snap_as_batch(oracle.cfk_apply(CC.empty_snapshot(), upd))[0]
+def width_items(L, tail):
+    """the queries of test_segment_widths over width_stream(L, tail), and how many of them come before the three that
+    read key 901 as well"""
     top = 4 * (L + 1) + 4
     inside = sorted({1, 63, 64, 65, CHUNK - 1, CHUNK, CHUNK + 1, L - tail - 1, L - tail, L - tail + 1, L - 1} & set(range(1, L)))
     items = [(ts(top + 5), None, [900])]                                   # above: the whole segment
@@ -245,6 +243,15 @@ def test_segment_widths(ctx, ctx_small_cap, L, tail):
     items += [(ts(1), None, [900])]                                        # below: nothing
     both = len(items)
     items += [(ts(top + 5), None, [900, 901]), (ts(top + 7), None, [901]), (ts(top + 9), None, [899, 900, 901, 902])]
+    return items, both
+
+
+@pytest.mark.parametrize("L,tail", WIDTHS)
+def test_segment_widths(ctx, ctx_small_cap, L, tail):
+    from accord_amd.deps import CfkStore
+    upd = width_stream(L, tail)
+    ob = CC.snap_as_batch(oracle.cfk_apply(CC.empty_snapshot(), upd))[0]
+    items, both = width_items(L, tail)
     want = expect_foreign(ob, items)
     if tail == SMALL_CAP - 1:
         # above on 900: the last committed + the tail = SMALL_CAP hits (one-wave tier at the cap);

@@ -1,6 +1,7 @@
 """Host side of acc_cfk_keydeps (no GPU): the ctypes mirror of acc_cfk_queries and of the acc_opts knob against the
 header's layout, and the executeAt ReplicaStore.preaccept_batch(scan="new") gives a query that carries none."""
 import ctypes as C
+import inspect
 import re
 from pathlib import Path
 
@@ -9,7 +10,7 @@ import numpy as np
 import cfk_cases as CC
 from accord_amd import _lib as L
 from accord_amd import workload as W
-from accord_amd.deps import _execute_at_after
+from accord_amd.deps import Context, _execute_at_after
 
 HEADER = (Path(__file__).resolve().parent.parent / "include" / "accord_amd.h").read_text()
 
@@ -19,6 +20,12 @@ def test_opts_keeps_its_size_and_names_the_knob():
     assert [f[0] for f in L.Opts._fields_][-1] == "cfq_wave_cap"
     body = re.search(r"typedef struct acc_opts \{(.*?)\} acc_opts;", HEADER, re.S).group(1)
     assert re.findall(r"uint32_t\s+(\w+);", body) == [f[0] for f in L.Opts._fields_]
+    # the slice limit of the wave-per-item launches took the reserved second word: flags stays first, the rest in place
+    assert [f[0] for f in L.Opts._fields_][:3] == ["flags", "wave_grid_max", "cfk_hot"]
+    assert L.Opts.wave_grid_max.offset == 4 and L.Opts.cfq_wave_cap.offset == 20
+    for knob in ("wave_grid_max", "cfq_wave_cap"):
+        p = inspect.signature(Context.__init__).parameters[knob]
+        assert p.kind is inspect.Parameter.KEYWORD_ONLY and p.default == 0
 
 
 def test_cfk_queries_layout_matches_the_header():

@@ -277,9 +277,8 @@ def segment_stream(codes, lens, accepted_tail):
 LADDER = [1, 2, 3, 31, 32, 33, 63, 64, 65, 255, 256, 257, 513]
 
 
-@pytest.mark.parametrize("end_inclusive", [1, 0], ids=["end_inclusive", "start_inclusive"])
-def test_segment_ladder(ctx, ctx_small_cap, end_inclusive):
-    from accord_amd.deps import CfkStore
+def ladder_case():
+    """the store of test_segment_ladder (one key per LADDER length), its txn-major view and the test's queries"""
     K = len(LADDER)
     codes = [1000 + 10 * j for j in range(K)]
     upd = segment_stream(codes, LADDER, lambda Ln: min(10, Ln // 2))
@@ -296,6 +295,14 @@ def test_segment_ladder(ctx, ctx_small_cap, end_inclusive):
         (ts(cut(70) + 2), None, [1090], []),
         (ts(top + 7), None, [1090, 1120], []),
     ]
+    return upd, ob, items
+
+
+@pytest.mark.parametrize("end_inclusive", [1, 0], ids=["end_inclusive", "start_inclusive"])
+def test_segment_ladder(ctx, ctx_small_cap, end_inclusive):
+    from accord_amd.deps import CfkStore
+    K = len(LADDER)
+    upd, ob, items = ladder_case()
     want = expect_mixed(ob, items, end_inclusive)
     assert int(want["u_off"][1]) == 115                 # per key its last committed Write and its accepted tail
     assert int(want["kd_off"][1]) == K
