@@ -51,6 +51,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
+           "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
            "acc_ranges_of", "acc_ranges_with", "acc_ranges_subtract", "acc_ranges_merge_touching", "acc_ranges_select",
            "acc_ranges_index_of", "acc_ranges_contains_all_keys", "acc_ranges_contains_all", "acc_rangedeps_is_covered_by",
            "acc_partial_deps_covering", "acc_rmm_without", "acc_recovery_deps_reduce"]
@@ -303,6 +304,20 @@ class CfkMixedQueries(C.Structure):
                 ("end_inclusive", C.c_uint32), ("lane_seg", C.c_uint32)]
 
 
+ACC_RCMD_ERASED = 1
+
+
+class RcmdUpdates(C.Structure):
+    _fields_ = [("n_upd", C.c_uint32), ("mem", C.c_uint32), ("n_ranges", C.c_uint64), ("txn_id", TsCols),
+                ("flags", C.c_void_p), ("rng_off", C.c_void_p), ("rng_start", C.c_void_p), ("rng_end", C.c_void_p)]
+
+
+class RcmdTable(C.Structure):
+    _fields_ = [("n_cmd", C.c_uint32), ("end_inclusive", C.c_uint32), ("n_ranges", C.c_uint64), ("n_dict", C.c_uint32),
+                ("reserved", C.c_uint32), ("txn_id", TsCols), ("flags", C.c_void_p), ("rng_off", C.c_void_p),
+                ("rng_start", C.c_void_p), ("rng_end", C.c_void_p), ("dict_start", C.c_void_p), ("dict_end", C.c_void_p)]
+
+
 class ConflictsIn(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("n_upd", C.c_uint32), ("end_inclusive", C.c_uint32), ("n_keys", C.c_uint64),
                 ("n_ranges", C.c_uint64), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
@@ -519,6 +534,16 @@ def load():
         L.acc_maxconflicts_get.restype = C.c_int
         L.acc_maxconflicts_size.argtypes = [C.c_void_p]
         L.acc_maxconflicts_size.restype = C.c_uint64
+        L.acc_rcmd_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
+        L.acc_rcmd_create.restype = C.c_int
+        L.acc_rcmd_destroy.argtypes = [C.c_void_p]
+        L.acc_rcmd_destroy.restype = None
+        L.acc_rcmd_update.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RcmdUpdates)]
+        L.acc_rcmd_update.restype = C.c_int
+        L.acc_rcmd_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RcmdTable)]
+        L.acc_rcmd_view.restype = C.c_int
+        L.acc_rcmd_rangedeps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkMixedQueries), C.POINTER(RangedepsView)]
+        L.acc_rcmd_rangedeps.restype = C.c_int
     except AttributeError:
         if not os.environ.get("ACC_LIB_PATH"):   # an older tuning build (A/B runs) may lack them; the product may not
             raise

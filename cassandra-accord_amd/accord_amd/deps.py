@@ -1115,6 +1115,89 @@ class CfkStore:
         return bv
 
 
+def _mixed_queries_in(q: dict, end_inclusive: int, lane_seg: int, keep: list) -> "L.CfkMixedQueries":
+    """The CfkStore.keydeps_mixed dict as an acc_cfk_mixed_queries of host arrays (kept alive in keep)."""
+    a = dict(qm=np.ascontiguousarray(q["msb"], dtype=np.uint64), ql=np.ascontiguousarray(q["lsb"], dtype=np.uint64),
+             qn=np.ascontiguousarray(q["node"], dtype=np.int32), ko=np.ascontiguousarray(q["key_off"], dtype=np.uint32),
+             kc=np.ascontiguousarray(q["key_code"], dtype=np.uint64), ro=np.ascontiguousarray(q["rng_off"], dtype=np.uint32),
+             rs=np.ascontiguousarray(q["rng_start"], dtype=np.uint64), re=np.ascontiguousarray(q["rng_end"], dtype=np.uint64))
+    p = lambda k: a[k].ctypes.data  # noqa: E731
+    ex = L.TsCols(None, None, None)
+    if q.get("xmsb") is not None:
+        a.update(xm=np.ascontiguousarray(q["xmsb"], dtype=np.uint64), xl=np.ascontiguousarray(q["xlsb"], dtype=np.uint64),
+                 xn=np.ascontiguousarray(q["xnode"], dtype=np.int32))
+        ex = L.TsCols(p("xm"), p("xl"), p("xn"))
+    keep.append(a)
+    return L.CfkMixedQueries(len(a["qm"]), L.ACC_MEM_HOST, len(a["kc"]), len(a["rs"]), L.TsCols(p("qm"), p("ql"), p("qn")), ex,
+                             p("ko"), p("kc"), p("ro"), p("rs"), p("re"), int(end_inclusive), int(lane_seg))
+
+
+class RangeCmdStore:
+    """A CommandStore's range commands kept in HBM (acc_rcmd_*): the rangeCommands map that InMemorySafeStore.update
+    adds to (impl/InMemoryCommandStore.java:739-762, RangeCommand.update = ranges.with(add)) with its stabbing index,
+    and the RangeDeps of new txns read from it (mapReduceRangesInternal, :883-960). One Range bound type per store."""
+
+    def __init__(self, ctx: Context, end_inclusive: int = 1):
+        self.ctx = ctx
+        self.end_inclusive = int(end_inclusive)
+        h = C.c_void_p()
+        ctx.check(ctx._lib.acc_rcmd_create(ctx.handle, self.end_inclusive, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.acc_rcmd_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def update(self, upd: dict):
+        """Apply updates in array order: upd = dict(msb, lsb, node: the TxnIds (may repeat); flags: 0 or
+        L.ACC_RCMD_ERASED per update, default 0; rng_off, rng_start, rng_end: each update's ranges, sorted and
+        non-overlapping). Key-domain TxnIds are ignored."""
+        n = len(upd["msb"])
+        fl = upd.get("flags")
+        a = dict(tm=np.ascontiguousarray(upd["msb"], dtype=np.uint64), tl=np.ascontiguousarray(upd["lsb"], dtype=np.uint64),
+                 tn=np.ascontiguousarray(upd["node"], dtype=np.int32),
+                 fl=np.zeros(n, np.uint8) if fl is None else np.ascontiguousarray(fl, dtype=np.uint8),
+                 ro=np.ascontiguousarray(upd["rng_off"], dtype=np.uint32), rs=np.ascontiguousarray(upd["rng_start"], dtype=np.uint64),
+                 re=np.ascontiguousarray(upd["rng_end"], dtype=np.uint64))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ui = L.RcmdUpdates(n, L.ACC_MEM_HOST, len(a["rs"]), L.TsCols(p("tm"), p("tl"), p("tn")), p("fl"), p("ro"), p("rs"), p("re"))
+        self.ctx.check(self.ctx._lib.acc_rcmd_update(self.ctx.handle, self._h, C.byref(ui)))
+
+    def view(self) -> "L.RcmdTable":
+        """The table as device pointers (acc_rcmd_view; valid until the next update)."""
+        v = L.RcmdTable()
+        self.ctx.check(self.ctx._lib.acc_rcmd_view(self.ctx.handle, self._h, C.byref(v)))
+        return v
+
+    def table(self) -> dict:
+        """Host copy of the table and the dictionary: msb, lsb, node, flags [n_cmd] in TxnId order, rng_off [n_cmd + 1],
+        rng_start, rng_end; dict_start, dict_end [n_dict]."""
+        v = self.view()
+        n, R, nd = int(v.n_cmd), int(v.n_ranges), int(v.n_dict)
+        g = lambda ptr, cnt, dt: device_array(self.ctx, ptr, cnt, dt) if cnt else np.zeros(0, dt)  # noqa: E731
+        return dict(msb=g(v.txn_id.msb, n, np.uint64), lsb=g(v.txn_id.lsb, n, np.uint64), node=g(v.txn_id.node, n, np.int32),
+                    flags=g(v.flags, n, np.uint8), rng_off=g(v.rng_off, n + 1, np.uint32), rng_start=g(v.rng_start, R, np.uint64),
+                    rng_end=g(v.rng_end, R, np.uint64), dict_start=g(v.dict_start, nd, np.uint64),
+                    dict_end=g(v.dict_end, nd, np.uint64), end_inclusive=int(v.end_inclusive))
+
+    def rangedeps(self, queries: dict) -> "BatchRangeDeps":
+        """The RangeDeps of the queries alone against the resident store (acc_rcmd_rangedeps): queries = the
+        CfkStore.keydeps_mixed dict. Host arrays out: range_id into the store's dictionary (rng_start, rng_end),
+        dep_txn = indices into table() order. The store is read in place and not modified."""
+        keep = []
+        qi = _mixed_queries_in(queries, self.end_inclusive, 0, keep)
+        view = L.RangedepsView()
+        self.ctx.check(self.ctx._lib.acc_rcmd_rangedeps(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
+        return self.ctx.copy_out_range(view)
+
+
 def mixed_queries_from_preaccept(q: dict) -> dict:
     """The acc_preaccept_in-layout queries (msb, lsb, node, is_range, part_off, part_start, part_end; optional xmsb,
     xlsb, xnode) as the CfkStore.keydeps_mixed dict: the parts of an is_range == 0 query become its keys (part_start),
@@ -1163,20 +1246,40 @@ class ReplicaStore:
         self.end_inclusive = int(end_inclusive)
         self.cfk = CfkStore(ctx)
         self.mc = MaxConflictsMap(ctx, end_inclusive)
+        self.rcmd = RangeCmdStore(ctx, end_inclusive)
 
-    def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True) -> dict:
+    def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True,
+                        range_part: dict | None = None) -> dict:
         """part: the batch's updates (cfk_update_stream layout); queries: its PreAccept queries (default: one per
         command first seen in part). Returns dict(propose = MaxConflicts.get + fast path per query, keydeps = the
         KeyDeps of every txn of the store after the batch, when scan). scan="new": instead keydeps_new = the KeyDeps of
         the queries alone, scanned against the updated store in place (acc_cfk_keydeps; acc_cfk_keydeps_mixed with the
         store's bound type when a query has is_range set): the rows the whole-store scan would give for them, nothing
         recomputed for stored txns. A query without executeAt columns (xmsb, xlsb, xnode)
-        takes the executeAt the batch leaves its txn with."""
+        takes the executeAt the batch leaves its txn with.
+        range_part: the batch's range-command updates (RangeCmdStore.update layout plus optional xmsb, xlsb, xnode: their
+        executeAts, default the TxnIds), applied to the range-command store and merged into MaxConflicts with their
+        ranges. With scan="new" the result also holds rangedeps_new = the RangeDeps of the same queries from the
+        range-command store after the update (acc_rcmd_rangedeps): with keydeps_new, both halves of PartialDeps."""
         from . import workload as W
         q = W.preaccept_queries(part) if queries is None else queries
         out = dict(propose=self.mc.get(q))
         self.mc.update(W.conflicts_updates(part, self.end_inclusive))
         self.cfk.apply_deps(part)
+        if range_part is not None:
+            rp = range_part
+            dom = (np.asarray(rp["lsb"], dtype=np.uint64) & np.uint64(1)).astype(bool)   # key-domain TxnIds are no range commands
+            cnt = np.where(dom, np.diff(np.asarray(rp["rng_off"], dtype=np.int64)), 0)
+            sel = np.repeat(dom, np.diff(np.asarray(rp["rng_off"], dtype=np.int64)))
+            has_x = rp.get("xmsb") is not None
+            U = len(rp["msb"])
+            self.mc.update(dict(end_inclusive=self.end_inclusive, xmsb=rp["xmsb"] if has_x else rp["msb"],
+                                xlsb=rp["xlsb"] if has_x else rp["lsb"], xnode=rp["xnode"] if has_x else rp["node"],
+                                key_off=np.zeros(U + 1, np.uint32), key=np.zeros(0, np.uint64),
+                                rng_off=np.concatenate([[0], np.cumsum(cnt)]).astype(np.uint32),
+                                rng_start=np.asarray(rp["rng_start"], dtype=np.uint64)[sel],
+                                rng_end=np.asarray(rp["rng_end"], dtype=np.uint64)[sel]))
+            self.rcmd.update(rp)
         if isinstance(scan, str):
             if scan != "new":
                 raise ValueError(f"scan must be True, False or 'new', not {scan!r}")
@@ -1190,6 +1293,10 @@ class ReplicaStore:
             if q.get("xmsb") is None:
                 nq.update(zip(("xmsb", "xlsb", "xnode"), _execute_at_after(part, q)))
             out["keydeps_new"] = self.cfk.keydeps_mixed(nq, self.end_inclusive) if mixed else self.cfk.keydeps(nq)
+            if not mixed:
+                nq = dict(nq, rng_off=np.zeros(len(q["msb"]) + 1, np.uint32), rng_start=np.zeros(0, np.uint64),
+                          rng_end=np.zeros(0, np.uint64))
+            out["rangedeps_new"] = self.rcmd.rangedeps(nq)
         elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
         return out
@@ -1197,3 +1304,4 @@ class ReplicaStore:
     def close(self):
         self.cfk.close()
         self.mc.close()
+        self.rcmd.close()

@@ -41,6 +41,11 @@ void cfk_free(acc_cfk *cfk);
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
 void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *view);
 acc_cfk *cfk_new(int device);
+acc_rcmd *rcmd_new(int device, uint32_t end_inclusive);
+void rcmd_free(acc_rcmd *store);
+void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in);
+void rcmd_table(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_table *out);
+void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rangedeps_view *view);
 }  // namespace acc
 
 namespace {
@@ -320,6 +325,42 @@ int acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_querie
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_keydeps_mixed(ctx, cfk, q, out_view);
+    });
+}
+
+int acc_rcmd_create(acc_ctx *ctx, uint32_t end_inclusive, acc_rcmd **out)
+{
+    if (!ctx || !out) return ACC_E_ARG;
+    *out = nullptr;
+    return acc_guard(ctx, [&] { *out = acc::rcmd_new(ctx->device, end_inclusive); });
+}
+
+void acc_rcmd_destroy(acc_rcmd *store) { acc::rcmd_free(store); }
+
+int acc_rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *updates)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_update(ctx, store, updates);
+    });
+}
+
+int acc_rcmd_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_table *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_table(ctx, store, out);
+    });
+}
+
+int acc_rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rangedeps_view *out_view)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_rangedeps(ctx, store, q, out_view);
     });
 }
 

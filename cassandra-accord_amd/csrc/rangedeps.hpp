@@ -116,6 +116,7 @@ private:
 // parts before it. Device pointers are owned by the context and valid until its next compute call.
 struct RdBuild {
     uint32_t n = 0, Q = 0;            // txns; queries = P + R
+    uint32_t npos = 0;                // TxnId positions the entries name (0: n, the batch's own; rcmd.hip: the store's table)
     size_t P = 0, R = 0;              // key pairs, ranges
     int end_inclusive = 0;
     // ---- rd_prepare

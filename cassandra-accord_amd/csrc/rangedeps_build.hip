@@ -560,8 +560,9 @@ void rd_build_txns(acc_ctx *ctx, RdBuild &b)
     o.s_rid = ctx->get<uint32_t>("rd_s_rid", b.E);
     o.s_dep = ctx->get<uint32_t>("rd_s_dep", b.E);
     const uint32_t *tl_sorted = ts.vals;
-    // 32-bit sort keys in the lane-group tiers: range ids (< NE) and TxnId positions (< n) within 26 bits
-    const bool narrow = b.NE < (1u << 26) && n < (1u << 26) && !(ctx->flags & ACC_OPT_RD_WIDE_SORT);   // (testing: 64-bit sorts throughout)
+    // 32-bit sort keys in the lane-group tiers: range ids (< NE) and TxnId positions (< npos) within 26 bits
+    const uint32_t npos = b.npos ? b.npos : n;
+    const bool narrow = b.NE < (1u << 26) && npos < (1u << 26) && !(ctx->flags & ACC_OPT_RD_WIDE_SORT);   // (testing: 64-bit sorts throughout)
     ctx->stat("rangedeps.narrow_sorts", narrow ? 1 : 0);
     // tiers own disjoint txns (disjoint scratch): LDS workgroup tiers on side stream 1, 16- and 32-lane groups on side
     // stream 0, waves on the main stream, all concurrently

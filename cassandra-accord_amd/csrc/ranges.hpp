@@ -3,6 +3,7 @@
 // method step by step (file:line in each function).
 #pragma once
 #include "../../include/accord_amd.h"
+#include "ranges_with.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -12,23 +13,22 @@
 namespace acc {
 namespace rg {
 
-struct Rg {
-    uint64_t s, e;
-    bool operator==(const Rg &o) const { return s == o.s && e == o.e; }
-};
 using V = std::vector<Rg>;
 
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
 
-inline int cmpu(uint64_t a, uint64_t b) { return a < b ? -1 : a > b ? 1 : 0; }
-
-// Range.compareIntersecting (Range.java:296-305)
-inline int cmp_intersecting(const Rg &a, const Rg &b)
-{
-    if (a.s >= b.e) return 1;
-    if (a.e <= b.s) return -1;
-    return 0;
-}
+// a Ranges held in a vector, as ranges_with.hpp reads and writes one
+struct VecIn {
+    const Rg *p;
+    size_t n;
+    explicit VecIn(const V &v) : p(v.data()), n(v.size()) {}
+    size_t size() const { return n; }
+    Rg operator[](size_t i) const { return p[i]; }
+};
+struct VecSink {
+    V &v;
+    void push(const Rg &r) { v.push_back(r); }
+};
 
 // Range.compareTo(RoutableKey): EndInclusive (Range.java:48-55), StartInclusive (Range.java:98-105)
 inline int cmp_key(const Rg &r, uint64_t k, bool ei)
@@ -100,77 +100,24 @@ inline const V &check_sorted_deoverlapped(const V &in)
     return in;
 }
 
-// AbstractRanges.supersetLinearMerge (AbstractRanges.java:439-484): (ai, bi) = how far `as` covers a prefix of `bs`
+// AbstractRanges.supersetLinearMerge (AbstractRanges.java:439-484), restated in ranges_with.hpp
 inline void superset_linear_merge(const V &as, const V &bs, size_t &ai_out, size_t &bi_out)
 {
-    size_t ai = 0, bi = 0;
-    while (ai < as.size() && bi < bs.size()) {
-        Rg a = as[ai];
-        const Rg b = bs[bi];
-        int c = cmp_intersecting(a, b);
-        if (c < 0) { ai++; continue; }
-        if (c > 0) break;
-        if (b.s < a.s) break;
-        if ((c = cmpu(b.e, a.e)) <= 0) {
-            bi++;
-            if (c == 0) ai++;
-            continue;
-        }
-        // a run of touching `as` ranges must reach b's end, else stop at the start of the run
-        size_t t = ai;
-        bool broke = false;
-        do {
-            if (++t == as.size() || a.e != as[t].s) { broke = true; break; }
-            a = as[t];
-        } while (a.e < b.e);
-        if (broke) break;
-        bi++;
-        ai = t;
-    }
-    ai_out = ai;
-    bi_out = bi;
+    superset_linear_merge_of(VecIn(as), VecIn(bs), ai_out, bi_out);
 }
 
-// AbstractRanges.union(MERGE_OVERLAPPING, left, right) (AbstractRanges.java:496-585) = Ranges.with (Ranges.java:119-127)
+// AbstractRanges.union(MERGE_OVERLAPPING, left, right) (AbstractRanges.java:496-585) = Ranges.with (Ranges.java:119-127),
+// restated in ranges_with.hpp (the device folds range-command updates with the same code, rcmd.hip)
 inline V with(const V &left, const V &right)
 {
-    if (&left == &right || right.empty()) return left;
-    if (left.empty()) return right;
-    const V *pa = &left, *pb = &right;
-    {
-        const int c = cmpu((*pa)[0].s, (*pb)[0].s);
-        if (c > 0 || (c == 0 && pa->back().e < pb->back().e)) std::swap(pa, pb);
+    if (&left == &right) return left;
+    V result;
+    VecSink sink{ result };
+    switch (with_of(VecIn(left), VecIn(right), sink)) {
+    case WITH_LEFT: return left;
+    case WITH_RIGHT: return right;
+    default: return result;
     }
-    const V &as = *pa, &bs = *pb;
-    size_t ai, bi;
-    superset_linear_merge(as, bs, ai, bi);
-    if (bi == bs.size()) return as;
-    V result(as.begin(), as.begin() + (ptrdiff_t)ai);
-    while (ai < as.size() && bi < bs.size()) {
-        const Rg a = as[ai], b = bs[bi];
-        const int c = cmp_intersecting(a, b);
-        if (c < 0) { result.push_back(a); ai++; }
-        else if (c > 0) { result.push_back(b); bi++; }
-        else {
-            const uint64_t start = a.s <= b.s ? a.s : b.s;
-            uint64_t end = a.e >= b.e ? a.e : b.e;
-            ai++; bi++;
-            while (ai < as.size() || bi < bs.size()) {
-                bool from_a;
-                if (ai == as.size()) from_a = false;
-                else if (bi == bs.size()) from_a = true;
-                else from_a = as[ai].s < bs[bi].s;
-                const Rg &mn = from_a ? as[ai] : bs[bi];
-                if (mn.s > end) break;
-                if (mn.e > end) end = mn.e;
-                if (from_a) ai++; else bi++;
-            }
-            result.push_back({ start, end });
-        }
-    }
-    while (ai < as.size()) result.push_back(as[ai++]);
-    while (bi < bs.size()) result.push_back(bs[bi++]);
-    return result;
 }
 
 // AbstractRanges.subtract(AbstractRanges) (AbstractRanges.java:223-287); findNext = the CEIL search with

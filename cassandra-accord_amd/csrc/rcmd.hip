@@ -1,0 +1,722 @@
+// rcmd.hip — a device-resident range-command store and the RangeDeps of new txns read from it.
+//
+// The reference keeps a CommandStore's range commands as a live TreeMap<TxnId, RangeCommand>
+// (impl/InMemoryCommandStore.java: rangeCommands) that InMemorySafeStore.update adds to per command (:739-762:
+// key-domain TxnIds return early, computeIfAbsent, then RangeCommand.update: ranges = ranges == null ? add :
+// ranges.with(add), :524-539), and that mapReduceActive -> mapReduceRangesInternal (:863-870, :883-960) asks about the
+// incoming txn only. acc_rcmd is that map in HBM:
+//   the table   per TxnId in Timestamp.compareTo order: the raw TxnId of its first update, an erased flag
+//               (saveStatus >= Erased: never visited, :891-892) and its Ranges, sorted and non-overlapping;
+//   the index   the stabbing index over the ranges of the non-erased commands in the form rd_range_dict (rangedeps.hip)
+//               leaves it: the dictionary of distinct stored ranges in Range::compare order, the entries in (width
+//               class, start) order with (range id, table index) and kind, class_off.
+//
+// acc_rcmd_update (one stream, every column written once into fresh arrays, which the store then adopts):
+//   1. the delta validated; every later loop runs inside the offsets that passed;
+//   2. the delta's TxnIds dense-ranked by a stable sort: a TxnId listed several times is one group whose updates stay in
+//      array order (Ranges.with is not order-independent);
+//   3. each group searched among the stored TxnIds: stored row j moves to j + #inserted below it, an inserted TxnId
+//      lands at its insert position + its rank among the inserts;
+//   4. k_rc_fold, a lane per touched command: the exact replay of Ranges.with (ranges_with.hpp, the code the host's
+//      acc_ranges_with runs) over the command's updates in array order, in two scratch buffers of stored + added ranges
+//      that take turns as the sink; the result may also be the stored ranges or an update's ranges themselves (the
+//      superset short-cut returns the object it was given), so the lane ends with a pointer and a count;
+//   5. one scan of the row counts for rng_off, one write of every column;
+//   6. the index rebuilt from the new table by rd_range_dict as it is, and its arrays and the table moved into the
+//      store with acc_ctx::swap_buf (the context keeps the store's previous arrays for its next results).
+// acc_rcmd_rangedeps: the queries validated; per query two binary searches over the stored TxnId columns (lim = stored
+// TxnIds below executeAt, tpos = its own table index or none); then rd_stab_queries and rd_build_txns as they are, with
+// the entry columns, class offsets and dictionary pointing at the store.
+// Integer work only: HBM/latency bound, no MFMA.
+
+#include "rangedeps.hpp"
+#include "ranges_with.hpp"
+
+#include <type_traits>
+
+struct acc_rcmd {
+    int device = 0;
+    uint32_t end_inclusive = 0;
+    uint32_t n = 0;        // commands (table rows)
+    uint32_t R = 0;        // ranges of the table
+    uint32_t NE = 0;       // index entries = ranges of the non-erased commands
+    uint32_t n_dict = 0;   // distinct stored ranges
+    // the table
+    uint64_t *tm = nullptr, *tl = nullptr;
+    int32_t *tn = nullptr;
+    uint8_t *flags = nullptr;
+    uint32_t *rng_off = nullptr;
+    uint64_t *rs = nullptr, *re = nullptr;
+    // the index (rd_range_dict's arrays; class_off lies NCLS + 1 words into cls)
+    uint64_t *dict_s = nullptr, *dict_e = nullptr;
+    uint32_t *dincl = nullptr;
+    uint64_t *cs_s = nullptr, *cs_e = nullptr;
+    uint2 *cs_info = nullptr;
+    uint8_t *cs_kind = nullptr;
+    uint32_t *cls = nullptr;
+    // byte sizes of the arrays above in declaration order (adopted from the context: they differ from the counts)
+    size_t bytes[15] = {};
+};
+
+namespace acc {
+
+namespace rc {
+
+enum : uint64_t {
+    E_KIND = 1, E_FLAGS = 2, E_OFF = 4, E_BOUND = 8, E_ORDER = 16,
+    // queries
+    E_Q_KIND_ARG = 1 << 8, E_Q_KIND_STATE = 1 << 9, E_Q_KOFF = 1 << 10, E_Q_ROFF = 1 << 11, E_Q_RKEYS = 1 << 12,
+    E_Q_KRANGES = 1 << 13, E_Q_KEYS = 1 << 14,
+};
+
+constexpr uint32_t NONE = 0xFFFFFFFFu;
+
+struct Delta {
+    const uint64_t *tm, *tl;
+    const int32_t *tn;
+    const uint8_t *flags;
+    const uint32_t *rng_off;
+    const uint64_t *rs, *re;
+    uint32_t D, NR;
+};
+
+struct Table {
+    const uint64_t *tm, *tl;
+    const int32_t *tn;
+    const uint8_t *flags;
+    const uint32_t *rng_off;
+    const uint64_t *rs, *re;
+    uint32_t n;
+};
+
+struct TableOut {
+    uint64_t *tm, *tl;
+    int32_t *tn;
+    uint8_t *flags;
+    uint32_t *rng_off;
+    uint64_t *rs, *re;
+};
+
+// a Ranges in two columns, and the sink of one with(): what ranges_with.hpp reads and writes on the device
+struct Span {
+    const uint64_t *s, *e;
+    uint32_t n;
+    __device__ size_t size() const { return n; }
+    __device__ rg::Rg operator[](size_t i) const { return rg::Rg{ s[i], e[i] }; }
+};
+struct SpanSink {
+    uint64_t *s, *e;
+    uint32_t n, cap;
+    __device__ void push(const rg::Rg &r)
+    {
+        if (n < cap) { s[n] = r.s; e[n] = r.e; }   // with() stays within left + right <= cap; nothing is written past it
+        ++n;
+    }
+};
+
+// ---------------------------------------------------------------- update
+
+// Per update: Kind.ofOrdinal, the flag bits, offsets that start at 0, do not decrease and end at n_ranges, and
+// Ranges.ofSortedAndDeoverlapped with start < end inside them; the TxnId's compare words. A key-domain TxnId
+// (InMemorySafeStore.update: txnId.domain() != Range -> return) gets bit 0 of its second word set, which IDENTITY_LSB
+// leaves out: it never groups with a range-domain TxnId. g: [0] errors, [1] key-domain updates.
+__global__ __launch_bounds__(BLOCK) void k_rc_validate(Delta d, uint64_t *__restrict__ g, uint64_t *__restrict__ w0,
+                                                       uint64_t *__restrict__ w1, uint64_t *__restrict__ w2)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= d.D) return;
+    uint64_t e = 0;
+    const uint64_t l = d.tl[i];
+    if (((l >> 1) & 7u) > ACC_KIND_LOCAL_ONLY) e |= E_KIND;
+    if (d.flags[i] & ~(uint8_t)ACC_RCMD_ERASED) e |= E_FLAGS;
+    const uint32_t r0 = d.rng_off[i], r1 = d.rng_off[i + 1];
+    if (r1 < r0 || r1 > d.NR || (i == 0 && r0 != 0) || (i == d.D - 1 && r1 != d.NR)) e |= E_OFF;
+    else
+        for (uint32_t j = r0; j < r1; ++j) {
+            if (d.rs[j] >= d.re[j]) e |= E_BOUND;
+            if (j > r0 && d.re[j - 1] > d.rs[j]) e |= E_ORDER;
+        }
+    const bool keydom = !(l & 1u);
+    w0[i] = d.tm[i];
+    w1[i] = (l & IDENTITY_LSB) | (keydom ? 1u : 0u);
+    w2[i] = ts_w2(d.tn[i]);
+    if (e) atomicOr((unsigned long long *)&g[0], (unsigned long long)e);
+    if (keydom) atomicAdd((unsigned long long *)&g[1], 1ull);
+}
+
+// gstart[r] = the first position of group r in the sorted delta order; gstart[G] = D
+__global__ __launch_bounds__(BLOCK) void k_rc_gstart(uint32_t D, uint32_t G, const uint32_t *__restrict__ perm,
+                                                     const uint32_t *__restrict__ rank, uint32_t *__restrict__ gstart)
+{
+    const uint32_t p = blockIdx.x * BLOCK + threadIdx.x;
+    if (p >= D) return;
+    const uint32_t r = rank[perm[p]];
+    if (p == 0 || rank[perm[p - 1]] != r) gstart[r] = p;
+    if (p == 0) gstart[G] = D;
+}
+
+// group r (one TxnId of the delta): its lower bound among the stored TxnIds, member or not, and the bound of its
+// folded Ranges = the stored ranges + every range its updates list. Key-domain groups: pos = NONE.
+__global__ __launch_bounds__(BLOCK) void k_rc_locate(uint32_t G, Delta d, Table s, const uint32_t *__restrict__ first,
+                                                     const uint32_t *__restrict__ perm, const uint32_t *__restrict__ gstart,
+                                                     uint32_t *__restrict__ pos, uint32_t *__restrict__ isnew,
+                                                     uint64_t *__restrict__ bound)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= G) return;
+    const uint32_t i0 = first[r];
+    const uint64_t xm = d.tm[i0], xl = d.tl[i0];
+    const int32_t xn = d.tn[i0];
+    if (!(xl & 1u)) { pos[r] = NONE; isnew[r] = 0; bound[r] = 0; return; }
+    uint32_t lo = 0, hi = s.n;
+    while (lo < hi) {
+        const uint32_t m = (lo + hi) >> 1;
+        if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m;
+    }
+    const bool found = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], xm, xl, xn) == 0;
+    uint64_t b = found ? (uint64_t)(s.rng_off[lo + 1] - s.rng_off[lo]) : 0ull;
+    for (uint32_t p = gstart[r]; p < gstart[r + 1]; ++p) {
+        const uint32_t u = perm[p];
+        b += d.rng_off[u + 1] - d.rng_off[u];
+    }
+    pos[r] = lo;
+    isnew[r] = found ? 0u : 1u;
+    bound[r] = b;
+}
+
+// The fold, a lane per touched command: InMemorySafeStore.update per update of the group in array order.
+//   erased already (stored, or by an earlier update of the batch): the update changes nothing (st[0] counts it; st[1]
+//   counts the stored commands the batch names);
+//   an erased update: the command is erased, its ranges leave the table;
+//   else ranges = ranges == null ? add : ranges.with(add), replayed by with_of.
+// Scratch of group r: two buffers of bound[r] ranges from 2 * boff[r], taking turns as the sink. Leaves the group's
+// row, its Ranges as a pointer pair (stored columns, the delta's columns or scratch) and count, and its erased flag.
+struct Folded {
+    uint32_t *row, *cnt;
+    uint8_t *erased;
+    const uint64_t **ps, **pe;
+};
+__global__ __launch_bounds__(BLOCK) void k_rc_fold(uint32_t G, Delta d, Table s, const uint32_t *__restrict__ perm,
+                                                   const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ pos,
+                                                   const uint32_t *__restrict__ isnew, const uint32_t *__restrict__ newx,
+                                                   const uint64_t *__restrict__ boff, uint64_t *__restrict__ scr_s,
+                                                   uint64_t *__restrict__ scr_e, uint32_t *__restrict__ grow, Folded f,
+                                                   uint64_t *__restrict__ st)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= G) return;
+    const uint32_t lo = pos[r];
+    if (lo == NONE) { f.row[r] = NONE; return; }
+    const uint32_t row = lo + newx[r];
+    grow[row] = r;
+    f.row[r] = row;
+    bool erased = false;
+    Span cur{ nullptr, nullptr, 0 };
+    if (!isnew[r]) {
+        erased = (s.flags[lo] & ACC_RCMD_ERASED) != 0;
+        const uint32_t a = s.rng_off[lo];
+        if (!erased) cur = Span{ s.rs + a, s.re + a, s.rng_off[lo + 1] - a };
+    }
+    const uint64_t b0 = boff[r], cap64 = boff[r + 1] - b0;
+    const uint32_t cap = (uint32_t)cap64;
+    uint64_t *const bs[2] = { scr_s + 2 * b0, scr_s + 2 * b0 + cap64 };
+    uint64_t *const be[2] = { scr_e + 2 * b0, scr_e + 2 * b0 + cap64 };
+    uint32_t which = 0, ignored = 0;
+    for (uint32_t p = gstart[r]; p < gstart[r + 1]; ++p) {
+        const uint32_t u = perm[p];
+        if (erased) { ++ignored; continue; }
+        if (d.flags[u] & ACC_RCMD_ERASED) { erased = true; cur = Span{ nullptr, nullptr, 0 }; continue; }
+        const uint32_t a = d.rng_off[u];
+        const Span add{ d.rs + a, d.re + a, d.rng_off[u + 1] - a };
+        SpanSink sink{ bs[which], be[which], 0, cap };
+        const rg::WithResult w = rg::with_of(cur, add, sink);
+        if (w == rg::WITH_RIGHT) cur = add;
+        else if (w == rg::WITH_SINK) {
+            cur = Span{ sink.s, sink.e, sink.n < cap ? sink.n : cap };
+            which ^= 1u;   // the next sink is the buffer cur does not lie in
+        }
+    }
+    f.cnt[r] = cur.n;
+    f.erased[r] = erased ? 1 : 0;
+    f.ps[r] = cur.s;
+    f.pe[r] = cur.e;
+    if (ignored) atomicAdd((unsigned long long *)&st[0], (unsigned long long)ignored);
+    if (!isnew[r]) atomicAdd((unsigned long long *)&st[1], 1ull);
+}
+
+// insf[x] = 1: new row x holds an inserted TxnId
+__global__ __launch_bounds__(BLOCK) void k_rc_insflag(uint32_t n2, const uint32_t *__restrict__ grow, const uint32_t *__restrict__ isnew,
+                                                      uint32_t *__restrict__ insf)
+{
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
+    if (x >= n2) return;
+    const uint32_t g = grow[x];
+    insf[x] = g != NONE && isnew[g] ? 1u : 0u;
+}
+
+// ranges of new row x: its group's fold, or the stored row x - #inserted below it
+__global__ __launch_bounds__(BLOCK) void k_rc_counts(uint32_t n2, Table s, const uint32_t *__restrict__ grow,
+                                                     const uint32_t *__restrict__ insx, const uint32_t *__restrict__ gcnt,
+                                                     uint64_t *__restrict__ cnt)
+{
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
+    if (x >= n2) return;
+    const uint32_t g = grow[x];
+    if (g != NONE) { cnt[x] = gcnt[g]; return; }
+    const uint32_t j = x - insx[x];
+    cnt[x] = s.rng_off[j + 1] - s.rng_off[j];
+}
+
+// every column of new row x, once; the index's per-row inputs with it (rd_range_dict reads tinfo.y = table index,
+// rowner, eflag) and the OR of the range starts and of the ends (g[2], g[3]: the bit compaction plans; a bit set in
+// every bound rides along, which keeps the order)
+__global__ __launch_bounds__(BLOCK) void k_rc_write(uint32_t n2, Delta d, Table s, const uint32_t *__restrict__ first,
+                                                    const uint32_t *__restrict__ grow, const uint32_t *__restrict__ insx,
+                                                    const uint32_t *__restrict__ isnew, Folded f,
+                                                    const uint64_t *__restrict__ off, TableOut o, uint4 *__restrict__ tinfo,
+                                                    uint32_t *__restrict__ rowner, uint32_t *__restrict__ eflag,
+                                                    uint64_t *__restrict__ g)
+{
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
+    uint64_t ms = 0, me = 0;
+    if (x < n2) {
+        const uint32_t gr = grow[x];
+        const uint32_t j = x - insx[x];   // the stored row (unless inserted)
+        const uint64_t *ps, *pe;
+        uint8_t fl;
+        if (gr != NONE && isnew[gr]) {
+            const uint32_t i0 = first[gr];   // the raw bits of the first update
+            o.tm[x] = d.tm[i0]; o.tl[x] = d.tl[i0]; o.tn[x] = d.tn[i0];
+        } else {
+            o.tm[x] = s.tm[j]; o.tl[x] = s.tl[j]; o.tn[x] = s.tn[j];
+        }
+        if (gr != NONE) { ps = f.ps[gr]; pe = f.pe[gr]; fl = f.erased[gr] ? (uint8_t)ACC_RCMD_ERASED : (uint8_t)0; }
+        else { const uint32_t a = s.rng_off[j]; ps = s.rs + a; pe = s.re + a; fl = s.flags[j]; }
+        o.flags[x] = fl;
+        const uint64_t a0 = off[x], a1 = off[x + 1];
+        o.rng_off[x] = (uint32_t)a0;
+        if (x == n2 - 1) o.rng_off[n2] = (uint32_t)a1;
+        tinfo[x] = make_uint4(0u, x, 0u, 1u);
+        for (uint64_t k = a0; k < a1; ++k) {
+            const uint64_t sv = ps[k - a0], ev = pe[k - a0];
+            o.rs[k] = sv; o.re[k] = ev;
+            rowner[k] = x;
+            eflag[k] = fl & ACC_RCMD_ERASED ? 0u : 1u;
+            ms |= sv; me |= ev;
+        }
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) { ms |= shfl_xor(ms, dd); me |= shfl_xor(me, dd); }
+    if (lane_id() == 0) {
+        if (ms) atomicOr((unsigned long long *)&g[2], (unsigned long long)ms);
+        if (me) atomicOr((unsigned long long *)&g[3], (unsigned long long)me);
+    }
+}
+
+// ---------------------------------------------------------------- query
+
+struct Queries {
+    uint32_t nq, P, R;
+    const uint64_t *tm, *tl, *xm, *xl;
+    const int32_t *tn, *xn;
+    const uint32_t *key_off, *rng_off;
+    const uint64_t *key, *rs, *re;
+};
+
+// Per query: the checks of acc_cfk_keydeps_mixed (Kind.ofOrdinal, Kind.witnesses(), both offset arrays, the domain of
+// its participants, Keys sorted unique, Ranges sorted and deoverlapped with start < end); then, inside offsets that
+// passed, its row {lim, tpos, witnesses, domain}: lim = stored TxnIds below S = executeAt (STARTED_BEFORE, :901-902),
+// tpos = the table index of a stored TxnId Timestamp.equals to its own (never a dep of itself) or NONE; the owner of
+// each of its keys and ranges; the OR-mask of the query low bounds against the first one (g[1]).
+__global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, uint4 *__restrict__ tinfo, uint32_t *__restrict__ owner,
+                                                    uint32_t *__restrict__ rowner, uint64_t *__restrict__ g)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    uint64_t ml = 0;
+    if (q < Q.nq) {
+        uint64_t e = 0;
+        const uint64_t l = Q.tl[q];
+        const uint32_t kind = (uint32_t)(l >> 1) & 7u;
+        if (kind > ACC_KIND_LOCAL_ONLY) e |= E_Q_KIND_ARG;          // Kind.ofOrdinal
+        else if (witnesses(kind) == 0) e |= E_Q_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+        const bool range = l & 1u;
+        const uint64_t ref = Q.P ? Q.key[0] : Q.R ? Q.rs[0] : 0ull;
+        const uint32_t k0 = Q.key_off[q], k1 = Q.key_off[q + 1];
+        if (k1 < k0 || k1 > Q.P || (q == 0 && k0 != 0) || (q == Q.nq - 1 && k1 != Q.P)) e |= E_Q_KOFF;
+        else if (range) { if (k1 != k0) e |= E_Q_RKEYS; }
+        else
+            for (uint32_t j = k0; j < k1; ++j) {
+                if (j > k0 && Q.key[j - 1] >= Q.key[j]) e |= E_Q_KEYS;
+                owner[j] = q;
+                ml |= Q.key[j] ^ ref;
+            }
+        const uint32_t r0 = Q.rng_off[q], r1 = Q.rng_off[q + 1];
+        if (r1 < r0 || r1 > Q.R || (q == 0 && r0 != 0) || (q == Q.nq - 1 && r1 != Q.R)) e |= E_Q_ROFF;
+        else if (!range) { if (r1 != r0) e |= E_Q_KRANGES; }
+        else
+            for (uint32_t j = r0; j < r1; ++j) {
+                if (Q.rs[j] >= Q.re[j]) e |= E_BOUND;
+                if (j > r0 && Q.re[j - 1] > Q.rs[j]) e |= E_ORDER;     // touching ranges are allowed
+                rowner[j] = q;
+                ml |= Q.rs[j] ^ ref;
+            }
+        if (e) atomicOr((unsigned long long *)&g[0], (unsigned long long)e);
+        // lim: first stored TxnId >= S; tpos: first stored TxnId >= the query's own, when equal
+        const uint64_t sm = Q.xm[q], sl = Q.xl[q];
+        const int32_t sn = Q.xn[q];
+        uint32_t lo = 0, hi = s.n;
+        while (lo < hi) {
+            const uint32_t m = (lo + hi) >> 1;
+            if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], sm, sl, sn) < 0) lo = m + 1; else hi = m;
+        }
+        const uint32_t lim = lo;
+        const uint64_t qm = Q.tm[q];
+        const int32_t qn = Q.tn[q];
+        lo = 0; hi = s.n;
+        while (lo < hi) {
+            const uint32_t m = (lo + hi) >> 1;
+            if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], qm, l, qn) < 0) lo = m + 1; else hi = m;
+        }
+        const uint32_t tpos = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], qm, l, qn) == 0 ? lo : NONE;
+        tinfo[q] = make_uint4(lim, tpos, witnesses(kind), range ? 1u : 0u);
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) ml |= shfl_xor(ml, dd);
+    if (lane_id() == 0 && ml) atomicOr((unsigned long long *)&g[1], (unsigned long long)ml);
+}
+
+}  // namespace rc
+
+using namespace rc;
+
+acc_rcmd *rcmd_new(int device, uint32_t end_inclusive)
+{
+    if (end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
+    acc_rcmd *s = new acc_rcmd();
+    s->device = device;
+    s->end_inclusive = end_inclusive;
+    return s;
+}
+
+void rcmd_free(acc_rcmd *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    for (void *p : { (void *)s->tm, (void *)s->tl, (void *)s->tn, (void *)s->flags, (void *)s->rng_off, (void *)s->rs, (void *)s->re,
+                     (void *)s->dict_s, (void *)s->dict_e, (void *)s->dincl, (void *)s->cs_s, (void *)s->cs_e, (void *)s->cs_info,
+                     (void *)s->cs_kind, (void *)s->cls })
+        (void)hipFree(p);
+    delete s;
+}
+
+static Table table_of(const acc_rcmd *s) { return Table{ s->tm, s->tl, s->tn, s->flags, s->rng_off, s->rs, s->re, s->n }; }
+
+void rcmd_table(acc_ctx *ctx, acc_rcmd *s, acc_rcmd_table *out)
+{
+    if (!s || !out) fail(ACC_E_ARG, "null argument");
+    // an empty store has no arrays yet: placeholders (rng_off = one zero)
+    uint32_t *z = nullptr;
+    if (!s->rng_off) {
+        z = ctx->get<uint32_t>("rc_zero", 4);
+        ACC_HIP(hipMemsetAsync(z, 0, 16, ctx->stream));
+        ctx->sync();
+    }
+    *out = acc_rcmd_table{ s->n, s->end_inclusive, s->R, s->n_dict, 0u, acc_ts_cols{ s->tm, s->tl, s->tn }, s->flags,
+                           s->rng_off ? s->rng_off : z, s->rs, s->re, s->dict_s, s->dict_e };
+}
+
+void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
+{
+    if (!store || !in) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->n_ranges >= 0xFFFFFFFFull) fail(ACC_E_ARG, "n_ranges must be < 2^32 - 1");
+    hipStream_t st = ctx->stream;
+    const uint32_t D = in->n_upd, NR = (uint32_t)in->n_ranges, mem = in->mem;
+    ctx->stat("rcmd.inserted", 0);
+    ctx->stat("rcmd.updated", 0);
+    ctx->stat("rcmd.skipped_key_domain", 0);
+    ctx->stat("rcmd.erased_ignored", 0);
+    ctx->stat("rcmd.entries", store->NE);
+    ctx->stat("rcmd.stored_ranges", store->n_dict);
+    if (D == 0) {
+        if (NR) fail(ACC_E_ARG, "rng_off must start at 0, be non-decreasing and end at n_ranges");
+        return;
+    }
+    Delta d{};
+    d.D = D; d.NR = NR;
+    d.tm = stage_in(ctx, "rc_in_tm", in->txn_id.msb, D, mem);
+    d.tl = stage_in(ctx, "rc_in_tl", in->txn_id.lsb, D, mem);
+    d.tn = stage_in(ctx, "rc_in_tn", in->txn_id.node, D, mem);
+    d.flags = stage_in(ctx, "rc_in_flags", in->flags, D, mem);
+    d.rng_off = stage_in(ctx, "rc_in_roff", in->rng_off, (size_t)D + 1, mem);
+    d.rs = stage_in(ctx, "rc_in_rs", in->rng_start, NR, mem);
+    d.re = stage_in(ctx, "rc_in_re", in->rng_end, NR, mem);
+
+    // ---- 1, 2. validate; the TxnIds' dense ranks and stable sorted order
+    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
+    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
+    uint64_t *w[3] = { ctx->get<uint64_t>("rc_w0", D), ctx->get<uint64_t>("rc_w1", D), ctx->get<uint64_t>("rc_w2", D) };
+    launch(ctx, "rc_validate", k_rc_validate, dim3(grid_for(D, BLOCK)), dim3(BLOCK), 0, d, g, w[0], w[1], w[2]);
+    const uint64_t *words[3] = { w[0], w[1], w[2] };
+    const DenseRank dr = dense_rank(ctx, "rc_dr", D, 3, words, nullptr, nullptr, true);
+    uint32_t G, nkey;
+    {
+        ReadBack rb(ctx);
+        const auto hg = rb.words((const uint64_t *)g, 2);
+        const auto cnt = rb.u64(dr.count_dev);
+        rb.wait();
+        const uint64_t e = hg[0];
+        if (e & E_KIND) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in TxnId flags");
+        if (e & E_FLAGS) fail(ACC_E_ARG, "flags: only ACC_RCMD_ERASED may be set");
+        if (e & E_OFF) fail(ACC_E_ARG, "rng_off must start at 0, be non-decreasing and end at n_ranges");
+        if (e & E_BOUND) fail(ACC_E_ARG, "range start must be below its end (Range: start >= end)");
+        if (e & E_ORDER) fail(ACC_E_ARG, "ranges of an update must be sorted and deoverlapped (Ranges.ofSortedAndDeoverlapped)");
+        G = (uint32_t)(uint64_t)cnt;
+        nkey = (uint32_t)hg[1];
+    }
+
+    // ---- 3. groups against the stored TxnIds
+    const Table s = table_of(store);
+    const uint32_t n = store->n;
+    uint32_t *gstart = ctx->get<uint32_t>("rc_gstart", (size_t)G + 1);
+    uint32_t *pos = ctx->get<uint32_t>("rc_pos", G), *isnew = ctx->get<uint32_t>("rc_isnew", G);
+    uint32_t *newx = ctx->get<uint32_t>("rc_newx", (size_t)G + 1);
+    uint64_t *bound = ctx->get<uint64_t>("rc_bound", G), *boff = ctx->get<uint64_t>("rc_boff", (size_t)G + 1);
+    launch(ctx, "rc_gstart", k_rc_gstart, dim3(grid_for(D, BLOCK)), dim3(BLOCK), 0, D, G, dr.perm, (const uint32_t *)dr.rank, gstart);
+    launch(ctx, "rc_locate", k_rc_locate, dim3(grid_for(G, BLOCK)), dim3(BLOCK), 0, G, d, s, (const uint32_t *)dr.first, dr.perm,
+           (const uint32_t *)gstart, pos, isnew, bound);
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, isnew, newx, G, true, newx + G);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, bound, boff, G, true, boff + G);
+    uint32_t nnew;
+    uint64_t B;
+    {
+        ReadBack rb(ctx);
+        const auto a = rb.u32(newx + G);
+        const auto b = rb.u64(boff + G);
+        rb.wait();
+        nnew = a; B = b;
+    }
+    if ((uint64_t)n + nnew >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (commands >= 2^32 - 1)");
+    const uint32_t n2 = n + nnew;
+    if (n2 == 0) {   // an empty store and key-domain TxnIds only
+        ctx->stat("rcmd.skipped_key_domain", nkey);
+        return;
+    }
+
+    // ---- 4. the fold
+    uint64_t *scr_s = ctx->get<uint64_t>("rc_scr_s", 2 * B), *scr_e = ctx->get<uint64_t>("rc_scr_e", 2 * B);
+    uint32_t *grow = ctx->get<uint32_t>("rc_grow", n2);
+    ACC_HIP(hipMemsetAsync(grow, 0xFF, (size_t)n2 * sizeof(uint32_t), st));
+    Folded f{ ctx->get<uint32_t>("rc_f_row", G), ctx->get<uint32_t>("rc_f_cnt", G), ctx->get<uint8_t>("rc_f_erased", G),
+              ctx->get<const uint64_t *>("rc_f_ps", G), ctx->get<const uint64_t *>("rc_f_pe", G) };
+    launch(ctx, "rc_fold", k_rc_fold, dim3(grid_for(G, BLOCK)), dim3(BLOCK), 0, G, d, s, dr.perm, (const uint32_t *)gstart,
+           (const uint32_t *)pos, (const uint32_t *)isnew, (const uint32_t *)newx, (const uint64_t *)boff, scr_s, scr_e, grow, f, g + 4);
+
+    // ---- 5. row counts -> rng_off; every column once
+    uint32_t *insf = ctx->get<uint32_t>("rc_insf", n2), *insx = ctx->get<uint32_t>("rc_insx", (size_t)n2 + 1);
+    uint64_t *cnt = ctx->get<uint64_t>("rc_cnt", n2), *off = ctx->get<uint64_t>("rc_off", (size_t)n2 + 1);
+    launch(ctx, "rc_insflag", k_rc_insflag, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, (const uint32_t *)grow,
+           (const uint32_t *)isnew, insf);
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, insf, insx, n2, true, insx + n2);
+    launch(ctx, "rc_counts", k_rc_counts, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, s, (const uint32_t *)grow,
+           (const uint32_t *)insx, (const uint32_t *)f.cnt, cnt);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, cnt, off, n2, true, off + n2);
+    uint64_t R2;
+    {
+        ReadBack rb(ctx);
+        const auto a = rb.u64(off + n2);
+        rb.wait();
+        R2 = a;
+    }
+    if (R2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (ranges >= 2^32 - 1)");
+    TableOut o{ ctx->get<uint64_t>("rc_t_tm", n2), ctx->get<uint64_t>("rc_t_tl", n2), ctx->get<int32_t>("rc_t_tn", n2),
+                ctx->get<uint8_t>("rc_t_flags", n2), ctx->get<uint32_t>("rc_t_rng_off", (size_t)n2 + 1),
+                ctx->get<uint64_t>("rc_t_rs", R2), ctx->get<uint64_t>("rc_t_re", R2) };
+    RdBuild b;
+    b.n = n2;
+    b.R = (size_t)R2;
+    b.end_inclusive = (int)store->end_inclusive;
+    b.tinfo = ctx->get<uint4>("rd_tinfo", n2);
+    b.rowner = ctx->get<uint32_t>("rd_rowner", R2);
+    b.eflag = ctx->get<uint32_t>("rd_eflag", R2);
+    b.eidx = ctx->get<uint32_t>("rd_eidx", R2 + 1);
+    launch(ctx, "rc_write", k_rc_write, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, d, s, (const uint32_t *)dr.first,
+           (const uint32_t *)grow, (const uint32_t *)insx, (const uint32_t *)isnew, f, (const uint64_t *)off, o, b.tinfo, b.rowner,
+           b.eflag, g);
+
+    // ---- 6. the index from the new table (rd_range_dict as acc_rangedeps_batch runs it)
+    b.tl = o.tl;
+    b.rs = o.rs;
+    b.re = o.re;
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, b.eflag, b.eidx, (size_t)R2, true, b.eidx + R2);
+    uint64_t n_ign, n_upd;
+    {
+        ReadBack rb(ctx);
+        const auto hm = rb.words((const uint64_t *)(g + 2), 4);   // start mask, end mask, ignored updates, updated commands
+        ReadBack::Word<uint32_t> ne;
+        if (R2) ne = rb.u32(b.eidx + R2);
+        rb.wait();
+        b.mask_s = hm[0]; b.mask_e = hm[1];
+        n_ign = hm[2]; n_upd = hm[3];
+        b.NE = ne;
+    }
+    rd_range_dict(ctx, b);
+    uint32_t n_dict = 0;
+    {
+        ReadBack rb(ctx);
+        ReadBack::Word<uint32_t> nd;
+        if (b.NE) nd = rb.u32(b.dincl + b.NE);
+        rb.wait();   // everything of this update is complete: the store may take the arrays
+        n_dict = nd;
+    }
+
+    // ---- the store adopts the table and the index; the context keeps its previous arrays for the next results
+    int bi = 0;
+    auto adopt = [&](const char *name, auto *&p) {
+        void *v = p;
+        ctx->swap_buf(name, v, store->bytes[bi++]);
+        p = static_cast<std::remove_reference_t<decltype(p)>>(v);
+    };
+    adopt("rc_t_tm", store->tm); adopt("rc_t_tl", store->tl); adopt("rc_t_tn", store->tn); adopt("rc_t_flags", store->flags);
+    adopt("rc_t_rng_off", store->rng_off); adopt("rc_t_rs", store->rs); adopt("rc_t_re", store->re);
+    adopt("rd_dict_s", store->dict_s); adopt("rd_dict_e", store->dict_e); adopt("rd_dincl", store->dincl);
+    adopt("rd_cs_s", store->cs_s); adopt("rd_cs_e", store->cs_e); adopt("rd_cs_info", store->cs_info);
+    adopt("rd_cs_kind", store->cs_kind); adopt("rd_cls", store->cls);
+    store->n = n2;
+    store->R = (uint32_t)R2;
+    store->NE = b.NE;
+    store->n_dict = n_dict;
+    ctx->rd_valid = false;   // an earlier result may name arrays the store or the next call now owns
+    ctx->stat("rcmd.inserted", nnew);
+    ctx->stat("rcmd.updated", n_upd);
+    ctx->stat("rcmd.skipped_key_domain", nkey);
+    ctx->stat("rcmd.erased_ignored", n_ign);
+    ctx->stat("rcmd.entries", b.NE);
+    ctx->stat("rcmd.stored_ranges", n_dict);
+}
+
+static void rcmd_check_query_errors(uint64_t e)
+{
+    if (e & E_Q_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in TxnId flags");
+    if (e & E_Q_KIND_STATE) fail(ACC_E_STATE, "Kind.witnesses(): LocalOnly has no witnessed kinds");
+    if (e & E_Q_KOFF) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+    if (e & E_Q_ROFF) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+    if (e & E_Q_RKEYS) fail(ACC_E_ARG, "a range-domain query lists keys (TxnId.domain())");
+    if (e & E_Q_KRANGES) fail(ACC_E_ARG, "a key-domain query lists ranges (TxnId.domain())");
+    if (e & E_Q_KEYS) fail(ACC_E_ARG, "keys of a query must be sorted and unique (Keys.ofSortedUnique)");
+    if (e & E_BOUND) fail(ACC_E_ARG, "range start must be below its end (Range: start >= end)");
+    if (e & E_ORDER) fail(ACC_E_ARG, "ranges of a query must be sorted and deoverlapped (Ranges.ofSortedAndDeoverlapped)");
+}
+
+void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *in, acc_rangedeps_view *view)
+{
+    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
+    if (in->end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
+    if (in->n_pairs + in->n_ranges >= 0xFFFFFFFFull || in->n_pairs >= 0xFFFFFFFFull || in->n_ranges >= 0xFFFFFFFFull)
+        fail(ACC_E_ARG, "n_pairs + n_ranges must be < 2^32");
+    hipStream_t st = ctx->stream;
+    ctx->rd_valid = false;
+    const uint32_t nq = in->n_query, mem = in->mem;
+    RdBuild b;
+    b.n = nq;
+    b.npos = store->n;
+    b.P = (size_t)in->n_pairs;
+    b.R = (size_t)in->n_ranges;
+    b.Q = (uint32_t)(b.P + b.R);
+    b.end_inclusive = (int)store->end_inclusive;
+    b.arena_off = ctx->get<uint64_t>("rd_arena_off", (size_t)nq + 1);
+    b.rd_off = ctx->get<uint64_t>("rd_rd_off", (size_t)nq + 1);
+    b.u_off = ctx->get<uint64_t>("rd_u_off", (size_t)nq + 1);
+    // the dictionary of the view (placeholders while the store has none)
+    const uint64_t *dict_s = store->dict_s ? store->dict_s : ctx->get<uint64_t>("rc_dict0", 2);
+    const uint64_t *dict_e = store->dict_e ? store->dict_e : ctx->get<uint64_t>("rc_dict0", 2);
+    auto empty = [&] {
+        ACC_HIP(hipMemsetAsync(b.arena_off, 0, ((size_t)nq + 1) * 8, st));
+        ACC_HIP(hipMemsetAsync(b.rd_off, 0, ((size_t)nq + 1) * 8, st));
+        ACC_HIP(hipMemsetAsync(b.u_off, 0, ((size_t)nq + 1) * 8, st));
+        *view = acc_rangedeps_view{ nq, store->n_dict, 0, 0, 0, 0, dict_s, dict_e, b.arena_off, ctx->get<int32_t>("rd_arena", 1),
+                                    b.rd_off, ctx->get<uint32_t>("rd_range_id", 1), b.u_off, ctx->get<uint32_t>("rd_dep_txn", 1) };
+        ctx->rd_view = *view;
+        ctx->rd_valid = true;
+        ctx->stat("rangedeps.entries", store->NE);
+        ctx->stat("rangedeps.stored_ranges", store->n_dict);
+        ctx->stat("rangedeps.queries", b.Q);
+        ctx->stat("rangedeps.raw_entries", 0);
+        ctx->sync();
+    };
+    if (nq == 0) {
+        if (b.P) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+        if (b.R) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+        empty();
+        return;
+    }
+
+    // ---- stage and validate; the per-query rows
+    Queries Q{};
+    Q.nq = nq; Q.P = (uint32_t)b.P; Q.R = (uint32_t)b.R;
+    Q.tm = stage_in(ctx, "rc_q_tm", in->txn_id.msb, nq, mem);
+    Q.tl = stage_in(ctx, "rc_q_tl", in->txn_id.lsb, nq, mem);
+    Q.tn = stage_in(ctx, "rc_q_tn", in->txn_id.node, nq, mem);
+    if (in->execute_at.msb) {
+        Q.xm = stage_in(ctx, "rc_q_xm", in->execute_at.msb, nq, mem);
+        Q.xl = stage_in(ctx, "rc_q_xl", in->execute_at.lsb, nq, mem);
+        Q.xn = stage_in(ctx, "rc_q_xn", in->execute_at.node, nq, mem);
+    } else {
+        Q.xm = Q.tm; Q.xl = Q.tl; Q.xn = Q.tn;
+    }
+    Q.key_off = stage_in(ctx, "rc_q_koff", in->key_off, (size_t)nq + 1, mem);
+    Q.key = stage_in(ctx, "rc_q_key", in->key_code, b.P, mem);
+    Q.rng_off = stage_in(ctx, "rc_q_roff", in->rng_off, (size_t)nq + 1, mem);
+    Q.rs = stage_in(ctx, "rc_q_rs", in->rng_start, b.R, mem);
+    Q.re = stage_in(ctx, "rc_q_re", in->rng_end, b.R, mem);
+    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
+    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
+    b.tinfo = ctx->get<uint4>("rd_tinfo", nq);
+    uint32_t *owner = ctx->get<uint32_t>("owner", b.P);
+    b.rowner = ctx->get<uint32_t>("rd_rowner", b.R);
+    launch(ctx, "rc_qprep", k_rc_qprep, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), b.tinfo, owner, b.rowner, g);
+    {
+        ReadBack rb(ctx);
+        const auto hg = rb.words((const uint64_t *)g, 2);
+        rb.wait();
+        rcmd_check_query_errors(hg[0]);
+        b.mask_lo = hg[1];
+    }
+    if (store->NE == 0) {   // nothing to stab: no commands, or none with ranges that is not erased
+        empty();
+        return;
+    }
+
+    // ---- the reused stages over the store's index
+    b.key_off = Q.key_off; b.rng_off = Q.rng_off;
+    b.key_code = Q.key; b.rs = Q.rs; b.re = Q.re;
+    b.tl = Q.tl;
+    b.owner = owner;
+    b.dict.batch_sorted = true;   // tpos is the table index: no txn_of_tpos
+    b.NE = store->NE;
+    b.dict_s = store->dict_s; b.dict_e = store->dict_e; b.dincl = store->dincl;
+    b.cs_s = store->cs_s; b.cs_e = store->cs_e; b.cs_info = store->cs_info; b.cs_kind = store->cs_kind;
+    b.class_off = store->cls + (rd::NCLS + 1);
+    rd_stab_queries(ctx, b);
+    rd_build_txns(ctx, b);
+
+    ctx->stat("rangedeps.entries", b.NE);
+    ctx->stat("rangedeps.stored_ranges", b.n_dict);
+    ctx->stat("rangedeps.queries", b.Q);
+    ctx->stat("rangedeps.raw_entries", b.E);
+    ctx->stat("rangedeps.stab_passes", b.stab_passes);
+    ctx->stat("rangedeps.s16_txns", b.tier_txns[1]);
+    ctx->stat("rangedeps.s32_txns", b.tier_txns[11]);
+    ctx->stat("rangedeps.s64_txns", b.tier_txns[2]);
+    ctx->stat("rangedeps.block_txns", b.block_txns);
+    ctx->stat("rangedeps.global_txns", b.tier_txns[10]);
+    ctx->sync();
+    *view = acc_rangedeps_view{ nq, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
+                                b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
+    ctx->rd_view = *view;
+    ctx->rd_valid = true;
+}
+
+}  // namespace acc

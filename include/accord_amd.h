@@ -41,6 +41,10 @@
  *   acc_deps_to_json       (the in-tree Deps wire format) parsed / written on device, with the KeyDeps / RangeDeps Builder.
  *   acc_cfk_*              CommandsForKey.update for batches of commands   local/CommandsForKey.java:652-706
  *                          against a CFK store kept in HBM (SafeCommandStore.updateCommandsForKey :217-240).
+ *   acc_rcmd_*             the rangeCommands map of a CommandStore kept in HBM: InMemorySafeStore.update
+ *                          impl/InMemoryCommandStore.java:739-762 (RangeCommand.update = ranges.with(add), :524-539) for
+ *                          batches of commands, and the range-command half of mapReduceActive (:863-870, :883-960) for
+ *                          new txns only, read from the store's resident stabbing index.
  *   acc_levelise           execution-order restatement of Commands.updateWaitingOn local/Commands.java:776-830
  *                          (deterministic wavefront schedule).
  *
@@ -957,6 +961,76 @@ typedef struct acc_cfk_mixed_queries {
     uint32_t    lane_seg;              /* see above; 0: the library default */
 } acc_cfk_mixed_queries;
 int  acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *out_view);
+
+/* ---- A device-resident range-command store and the RangeDeps of new txns ----
+ * The other half of PreAccept.calculatePartialDeps beside acc_cfk_keydeps_mixed: the deps on the store's range commands
+ * (InMemorySafeStore.mapReduceActive -> mapReduceRangesInternal, impl/InMemoryCommandStore.java:863-870, 883-960). The
+ * reference keeps rangeCommands as a live TreeMap<TxnId, RangeCommand> that update() adds to (:739-762) and asks it about
+ * the incoming txn only; acc_rcmd is that map in HBM, one per CommandStore, one Range bound type fixed at creation
+ * (end_inclusive: 1 = (s, e], 0 = [s, e)). Per TxnId in Timestamp.compareTo order it holds the TxnId's raw bits (those of
+ * its first update), an erased flag (saveStatus >= Erased) and its Ranges (sorted, non-overlapping), and beside the table
+ * the stabbing index over the ranges of the non-erased commands: the dictionary of distinct stored ranges in
+ * Range::compare order and the entries in (width class, start) order, as acc_rangedeps_batch builds them per call.
+ *
+ * acc_rcmd_update applies the updates in array order, as InMemorySafeStore.update does per command: update u is a
+ * TxnId, flags[u] and the ranges [rng_off[u], rng_off[u+1]). A key-domain TxnId is ignored (txnId.domain() != Range ->
+ * return; stat rcmd.skipped_key_domain). A non-erased update inserts the TxnId when absent (computeIfAbsent) and sets
+ * ranges = ranges == null ? add : ranges.with(add) (RangeCommand.update :524-539; Ranges.with =
+ * AbstractRanges.union(MERGE_OVERLAPPING), primitives/AbstractRanges.java:439-585 — what acc_ranges_with computes, replayed
+ * step by step on the device: it has a superset short-cut and absorbs touching ranges only inside a group a strict overlap
+ * opened, so [1,3) with [3,5) with [2,4) = {[1,3),[3,5)} while [1,3) with [2,4) with [3,5) = {[1,5)}; a TxnId listed
+ * several times in one batch folds in array order). An update with ACC_RCMD_ERASED marks the TxnId erased, inserting a
+ * row without ranges when absent; its listed ranges are ignored. An erased command is never visited (:891-892): its
+ * ranges leave the table and the dictionary, and every later update of it changes nothing (stat rcmd.erased_ignored). A
+ * command may hold no ranges. Two TxnIds that are Timestamp.equals are one command. Errors (ACC_E_ARG): an invalid kind
+ * ordinal, a flags bit other than ACC_RCMD_ERASED, ranges of an update not sorted / overlapping / start >= end, rng_off
+ * not starting at 0 / decreasing / not ending at n_ranges. A rejected batch leaves the store unchanged; n_upd == 0 is a
+ * no-op. Each update rebuilds the index once from the resident table. One store is used by one context at a time.
+ *
+ * acc_rcmd_view describes the table: DEVICE pointers, valid until the next acc_rcmd_update of the store.
+ *
+ * acc_rcmd_rangedeps takes the query struct of acc_cfk_keydeps_mixed, so one query batch serves both halves
+ * (end_inclusive must equal the store's: ACC_E_ARG; lane_seg is ignored). For query q with S = its executeAt
+ * (execute_at.msb == NULL: S = TxnId) it visits every stored command C (:888-960 with ANY_STATUS / ANY_DEPS) that is not
+ * erased, has C.txnId < S strictly (STARTED_BEFORE, :901-902), whose kind q.kind().witnesses() holds, and whose TxnId is
+ * not Timestamp.equals to q's; each of C's ranges that contains one of q's keys (Range.contains with the bound type) or
+ * intersects one of q's ranges (compareIntersecting == 0) is collected per Range (a TreeMap by Range::compare, each list
+ * in TxnId order without consecutive duplicates) and built by RangeDeps.Builder. The result is an acc_rangedeps_view with
+ * n_txn = n_query in the acc_rangedeps_batch layout: range_id are ids into the store's dictionary (rng_start / rng_end),
+ * dep_txn indices into the acc_rcmd_view table order, ascending. It is the context's last RangeDeps result
+ * (acc_rangedeps_copy_out copies it), valid until the next RangeDeps compute call on the context or the next update of
+ * the store. The store is not modified. Errors as acc_cfk_keydeps_mixed: domain / participant mismatch, bad ranges or
+ * offsets, unsorted keys, n_pairs + n_ranges >= 2^32 - 1: ACC_E_ARG; a LocalOnly query: ACC_E_STATE. An empty store,
+ * n_query == 0 and queries without participants give empty results.
+ * Not modelled: historicalRangeCommands, which the reference's mapReduceActive also visits (:962-1004);
+ * acc_rangedeps_batch does not model them either. */
+typedef struct acc_rcmd acc_rcmd;
+
+typedef struct acc_rcmd_updates {
+    uint32_t    n_upd, mem;            /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t    n_ranges;              /* rng_off[n_upd] */
+    acc_ts_cols txn_id;                /* [n_upd]; may repeat */
+    const uint8_t  *flags;             /* [n_upd] 0 or ACC_RCMD_ERASED */
+    const uint32_t *rng_off;           /* [n_upd+1] */
+    const uint64_t *rng_start, *rng_end; /* [n_ranges] per update: sorted, non-overlapping, start < end */
+} acc_rcmd_updates;
+
+typedef struct acc_rcmd_table {
+    uint32_t    n_cmd, end_inclusive;
+    uint64_t    n_ranges;              /* rng_off[n_cmd] */
+    uint32_t    n_dict, reserved;
+    acc_ts_cols txn_id;                /* [n_cmd] TxnId order */
+    const uint8_t  *flags;             /* [n_cmd] 0 or ACC_RCMD_ERASED */
+    const uint32_t *rng_off;           /* [n_cmd+1] */
+    const uint64_t *rng_start, *rng_end; /* [n_ranges] */
+    const uint64_t *dict_start, *dict_end; /* [n_dict] distinct ranges of the non-erased commands, Range::compare order */
+} acc_rcmd_table;
+
+int  acc_rcmd_create(acc_ctx *ctx, uint32_t end_inclusive, acc_rcmd **out);
+void acc_rcmd_destroy(acc_rcmd *store);
+int  acc_rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *updates);
+int  acc_rcmd_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_table *out);
+int  acc_rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rangedeps_view *out_view);
 
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
