@@ -323,6 +323,8 @@ void rd_range_dict(acc_ctx *ctx, RdBuild &b)
     uint4 *erec = ctx->get<uint4>("rd_erec", 2 * (size_t)NE);
     uint64_t *dkey = ctx->get<uint64_t>("rd_dkey", NE), *ekey = ctx->get<uint64_t>("rd_ekey", NE);
     const bool split = rs_plan.bits + re_plan.bits > 64;
+    ctx->stat("rangedeps.dict_bits", (uint64_t)(rs_plan.bits + re_plan.bits));
+    ctx->stat("rangedeps.dict_split", split ? 1 : 0);
     launch(ctx, "rd_entries", k_rd_entries, dim3(grid_for(b.R, BLOCK)), dim3(BLOCK), 0, (uint32_t)b.R, b.n, (const uint32_t *)b.eflag,
            (const uint32_t *)b.eidx, (const uint32_t *)b.rowner, b.rs, b.re, (const uint4 *)b.tinfo, b.tl, rs_plan, re_plan,
            re_plan.bits, split ? 1 : 0, erec, dkey, ekey);

@@ -531,6 +531,7 @@ void rd_stab_queries(acc_ctx *ctx, RdBuild &b)
     const size_t P = b.P, R = b.R;
     const uint32_t Q = b.Q;
     const Runs q_plan = make_runs(b.mask_lo);
+    ctx->stat("rangedeps.query_bits", (uint64_t)q_plan.bits);
     QRec *rec = ctx->get<QRec>("rd_qrec", Q), *srec = nullptr;
     uint64_t *qkey = ctx->get<uint64_t>("rd_qkey", Q);
     const int qbits_full = q_plan.bits < 62 ? q_plan.bits + 3 : q_plan.bits < 64 ? q_plan.bits + 1 : 64;

@@ -2,8 +2,9 @@
 
 Bit-exact on every array: the stored-range dictionary, RangeDeps.ranges (dictionary ids), RangeDeps.txnIds (batch
 indices) and the Java rangesToTxnIds int[] of every txn; hand-made boundary cases, dense random batches for both
-Range bound types, u64 codes over the whole range (split sorts), every build tier, the config-4 golden fixture
-and error behaviour."""
+Range bound types, u64 codes over the whole range (split sorts), the bound families of rd_cases.py (every band of the
+query plan and the 64/65-bit edge of the dictionary key, with the plans taken read back from the stats), every build
+tier, the config-4 golden fixture and error behaviour."""
 import os
 
 import numpy as np
@@ -123,6 +124,30 @@ def test_wide_codes(ctx):
     import oracle
     rb = rd_cases.wide_codes(11, n=3000)
     assert_same(ctx.calculate_partial_range_deps(rb), oracle.rangedeps_batch(rb), "wide codes")
+
+
+@pytest.mark.parametrize("end_inclusive", [1, 0])
+@pytest.mark.parametrize("name", list(rd_cases.FAMILIES))
+def test_bound_families(ctx, name, end_inclusive):
+    """Every band of the query plan (61, 62, 63, 64 bits and the hull of a mask of 21 runs) and the 64/65-bit edge of
+    the dictionary key, against the oracle; the plans the library took (rangedeps.query_bits, dict_bits, dict_split)
+    against the arithmetic on the batch's own bounds: the masks are XOR-relative to the first bound of each column."""
+    import oracle
+    rb = rd_cases.family_batch(name, 0x5EED, end_inclusive)
+    g = ctx.calculate_partial_range_deps(rb)
+    st = ctx.stats()
+    o = oracle.rangedeps_batch(rb)
+    assert o.total_edges > 0
+    assert_same(g, o, f"family {name}")
+    want = rd_cases.batch_plan_bits(rb)
+    got = dict(query_bits=st["rangedeps.query_bits"], dict_bits=st["rangedeps.dict_bits"], dict_split=st["rangedeps.dict_split"])
+    assert got == want, (name, got, want)
+    if name in rd_cases.FAMILY_QUERY_BITS:
+        assert got["query_bits"] == rd_cases.FAMILY_QUERY_BITS[name]
+    if name in rd_cases.FAMILY_DICT:
+        assert (got["dict_bits"], got["dict_split"]) == rd_cases.FAMILY_DICT[name]
+    if name in ("top3", "top2", "top1", "full", "sparse"):
+        assert got["dict_split"] == 1
 
 
 def test_config4_golden(ctx):

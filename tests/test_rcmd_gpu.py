@@ -5,7 +5,8 @@ ranges.with(add)) and the range-command half of mapReduceActive for new txns (:8
 Expected values.
   The table: a Python fold of accord_amd.ranges.Ranges.with_ (the host acc_ranges_with) over the updates in array order
   per TxnId (Model below): raw bits of the first instance, flags, rng_off, ranges; the dictionary = the distinct ranges
-  of the non-erased commands in (start, end) order.
+  of the non-erased commands in (start, end) order. Every with() of that fold is also asserted equal to the independent
+  model (ranges_model.py); test_rcmd_fold_gpu.py checks the device fold against that model alone.
   The queries: the host copy of the table as range-domain rows in table order (PREACCEPTED, or INVALID_OR_TRUNCATED for
   erased rows, executeAt = TxnId), every query appended as a row with its TxnId and executeAt (a key-domain query with
   its keys and PREACCEPTED; a range-domain query with its ranges and INVALID_OR_TRUNCATED: evaluated as a query, no
@@ -16,6 +17,8 @@ import numpy as np
 import pytest
 
 import oracle
+import ranges_model
+import rd_cases
 from accord_amd import _lib as L
 from accord_amd import workload as W
 from accord_amd.deps import (IllegalArgumentException, IllegalStateException, RangeCmdStore, ReplicaStore,
@@ -74,7 +77,7 @@ def queries(items):
 
 class Model:
     """The host model of the store: InMemorySafeStore.update per update in array order, Ranges.with by the host
-    restatement. seen: what the stream exercised."""
+    restatement, each result asserted equal to ranges_model.with_. seen: what the stream exercised."""
 
     def __init__(self, end_inclusive):
         self.ei = end_inclusive
@@ -117,6 +120,8 @@ class Model:
             else:
                 left = c[2]
                 res = left.with_(add)
+                # the independent model (ranges_model.py) folds beside the host restatement, at every step
+                assert list(res) == ranges_model.with_(list(left), list(add)), (list(left), list(add))
                 same = len(res) == len(left) and np.array_equal(res.start, left.start) and np.array_equal(res.end, left.end)
                 if len(left) and len(add):
                     if same:
@@ -527,7 +532,63 @@ def test_empties_and_errors(ctx):
         s.close()
 
 
-# ---------------------------------------------------------------- 8. ReplicaStore
+# ---------------------------------------------------------------- 8. wide bounds through the reused stages
+
+@pytest.mark.parametrize("ei", [0, 1])
+@pytest.mark.parametrize("name", list(rd_cases.FAMILIES))
+def test_bound_families(ctx, name, ei):
+    """Every band of rd_stab_queries' query plan (61, 62, 63 and 64 bits, the hull of a mask of 21 runs) and both sides
+    of rd_range_dict's 64-bit key (64 bits unsplit, 65 split, a 64-bit end field, the wide families split) from the
+    store: about 400 commands of every width class, 300 key-domain and 300 range-domain queries, members with a bumped
+    executeAt among them. The plans taken (rangedeps.query_bits, dict_bits, dict_split) equal the arithmetic on the
+    bounds: the store's dictionary masks are the OR of the table's starts and of its ends, the query mask is the OR of
+    every query low bound XOR the first one."""
+    f = rd_cases.family(name, 0x5EED, ei)
+    cmds = f["cmds"]
+    kinds = [W.WRITE, W.READ, W.SYNC_POINT, W.EXCLUSIVE_SYNC_POINT]
+    tids = [ts(1000 + 3 * i, kinds[i % 4], node=1 + i % 3) for i in range(len(cmds))]
+    items = [(t, ERASED if i % 41 == 20 else 0, r) for i, (t, r) in enumerate(zip(tids, cmds))]   # (the last command stays: d33's end at 2^32)
+    m = Model(ei)
+    s = RangeCmdStore(ctx, ei)
+    try:
+        upd = updates(items)
+        s.update(upd)
+        st = ctx.stats()
+        m.apply(upd)
+        tab = s.table()
+        assert_table(tab, m.table(), f"family {name}")
+        sb, eb = rd_cases.plan_bits(rd_cases.or_mask(tab["rng_start"])), rd_cases.plan_bits(rd_cases.or_mask(tab["rng_end"]))
+        assert (st["rangedeps.dict_bits"], st["rangedeps.dict_split"]) == (sb + eb, int(sb + eb > 64)), (name, sb, eb)
+        if name in rd_cases.FAMILY_DICT:
+            assert (sb + eb, int(sb + eb > 64)) == rd_cases.FAMILY_DICT[name]
+            assert name != "e64" or (sb, eb) == (0, 64), "the start field is empty, the end field is shifted in by 64"
+        else:
+            assert sb + eb > 64
+        far = ts(1 << 40, W.WRITE, node=900)
+        qi = []
+        for i, k in enumerate(f["keyq"]):
+            t = ts(1000 + 3 * (i * 7 % len(cmds)) + 1, kinds[i % 4], rng=0, node=5)
+            qi.append((t, far if i % 3 == 0 else None, k, []))
+        for i, r in enumerate(f["rngq"]):
+            if i % 6 == 0:
+                qi.append((tids[i * 5 % len(cmds)], far, [], r))     # a member with a bumped executeAt
+            else:
+                qi.append((ts(1000 + 3 * (i * 11 % len(cmds)) + 2, kinds[i % 4], node=6), far if i % 3 == 1 else None, [], r))
+        q = queries(qi)
+        g = check_queries(s, q, ei, f"family {name}")
+        st = ctx.stats()
+        ref = int(q["key_code"][0])
+        qb = rd_cases.plan_bits(rd_cases.or_mask(q["key_code"], ref) | rd_cases.or_mask(q["rng_start"], ref))
+        assert st["rangedeps.query_bits"] == qb, (name, qb)
+        if name in rd_cases.FAMILY_QUERY_BITS:
+            assert qb == rd_cases.FAMILY_QUERY_BITS[name]
+        n = ndeps(g)
+        assert (n[:len(f["keyq"])] > 0).sum() >= 50 and (n[len(f["keyq"]):] > 0).sum() >= 50
+    finally:
+        s.close()
+
+
+# ---------------------------------------------------------------- 9. ReplicaStore
 
 def test_replica_store_both_halves(ctx):
     ei = 1
