@@ -17,6 +17,7 @@ ACC_MEM_HOST, ACC_MEM_DEVICE = 0, 1
 ACC_OPT_TIMING = 1
 ACC_OPT_FORCE_REPLAY = 2
 ACC_OPT_NO_WINDOW_TIER = 4
+ACC_OPT_TIER_GRID_SHIFT = 16
 ACC_OPT_RD_WIDE_SORT = 8
 ACC_OPT_PD_SERIAL = 16
 ACC_LV_AUTO, ACC_LV_LDS_WALK, ACC_LV_WINDOWED, ACC_LV_WAVES = 0, 1, 2, 3

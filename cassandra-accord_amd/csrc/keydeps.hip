@@ -960,10 +960,29 @@ __device__ __forceinline__ TxnCtx txn_ctx(const V2View &v, const V2Out &o, uint3
 
 // Key k's runs from its record (pair index jk); an inline record is one run of its own entries (m = INLINE_M,
 // start = the pair index). Returns the key's raw length.
-template <int MAXK>
-__device__ __forceinline__ uint32_t load_record(RunsT<MAXK> &R, const uint4 *rec, const uint32_t *irec32, uint32_t jk, uint32_t k)
+// A pair's count-pass record as loaded: its entry count, the inline record's word 7 and the four run-record words. The
+// loads are independent and issued together (one memory round trip, not three in a chain); an inline record's run words
+// are loaded and ignored.
+struct RecRaw {
+    uint64_t cnt;
+    uint32_t w;
+    uint4 r0, r1, r2, r3;
+};
+
+__device__ __forceinline__ RecRaw load_rec_raw(const uint4 *rec, const uint32_t *irec32, const uint64_t *cnt, uint32_t jk)
 {
-    const uint32_t w = irec32[IREC_W * (size_t)jk + 7];
+    RecRaw a;
+    a.cnt = cnt[jk];
+    a.w = irec32[IREC_W * (size_t)jk + 7];
+    const uint4 *r = rec + 4 * (size_t)jk;
+    a.r0 = r[0]; a.r1 = r[1]; a.r2 = r[2]; a.r3 = r[3];
+    return a;
+}
+
+template <int MAXK>
+__device__ __forceinline__ uint32_t load_record(RunsT<MAXK> &R, const RecRaw &a, uint32_t jk, uint32_t k)
+{
+    const uint32_t w = a.w;
     if (w & REC_INLINE_FLAG) {
         const uint32_t e = w & ~REC_INLINE_FLAG;
         R.start[k][0] = jk;
@@ -973,39 +992,48 @@ __device__ __forceinline__ uint32_t load_record(RunsT<MAXK> &R, const uint4 *rec
         R.m[k] = INLINE_M;
         return e;
     }
-    const uint4 *r = rec + 4 * (size_t)jk;
-    const uint4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-    const uint32_t a[6] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y };
+    const uint4 r0 = a.r0, r1 = a.r1, r2 = a.r2, r3 = a.r3;
+    const uint32_t s[6] = { r0.x, r0.y, r0.z, r0.w, r1.x, r1.y };
     const uint32_t l[6] = { r1.z, r1.w, r2.x, r2.y, r2.z, r2.w };
     uint32_t acc = 0;
 #pragma unroll
-    for (int q = 0; q < 6; ++q) { R.start[k][q] = a[q]; R.pre[k][q] = acc; acc += l[q]; }
+    for (int q = 0; q < 6; ++q) { R.start[k][q] = s[q]; R.pre[k][q] = acc; acc += l[q]; }
     R.start[k][6] = r3.x; R.pre[k][6] = acc; acc += r3.y;
     R.pre[k][7] = acc;
     R.m[k] = r3.z;
     return acc;
 }
 
-// Called by ONE wave: lane k < nk fills the runs of key k from its 64-B record. Returns the flattened raw length.
+// Called by ONE wave: lane k < nk fills the runs of key k (pair j0 + k) from its loaded record. Returns the flattened
+// raw length.
 template <int MAXK>
-__device__ uint32_t compute_runs(RunsT<MAXK> &R, const V2View &v, const V2Out &o, const uint64_t *cnt, const TxnCtx &c)
+__device__ uint32_t finish_runs(RunsT<MAXK> &R, const RecRaw &a, uint32_t j0, uint32_t nk)
 {
     const uint32_t lane = lane_id();
     uint32_t ktot = 0;
-    if (lane < c.nk && cnt[c.j0 + lane] != 0) {
-        ktot = load_record(R, o.rec, o.irec32, c.j0 + lane, lane);
-    } else if (lane < c.nk) {
+    if (lane < nk && a.cnt != 0) {
+        ktot = load_record(R, a, j0 + lane, lane);
+    } else if (lane < nk) {
         for (int q = 0; q <= NRUN; ++q) R.pre[lane][q] = 0;
         R.m[lane] = NO_M;
     }
     if (lane < (uint32_t)MAXK) R.kc[lane] = 0;
     uint32_t incl = wave_inclusive(ktot, OpAdd<uint32_t>());
-    if (lane < c.nk) R.kbase[lane] = incl - ktot;
+    if (lane < nk) R.kbase[lane] = incl - ktot;
     uint32_t total = shfl_idx(incl, 63);
-    if (lane == 0) { R.kbase[c.nk] = total; R.total = total; }
+    if (lane == 0) { R.kbase[nk] = total; R.total = total; }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     return total;
+}
+
+// Called by ONE wave: lane k < nk loads the 64-B record of key k and fills its runs.
+template <int MAXK>
+__device__ uint32_t compute_runs(RunsT<MAXK> &R, const V2View &v, const V2Out &o, const uint64_t *cnt, const TxnCtx &c)
+{
+    RecRaw a{};
+    if (lane_id() < c.nk) a = load_rec_raw(o.rec, o.irec32, cnt, c.j0 + lane_id());
+    return finish_runs(R, a, c.j0, c.nk);
 }
 
 // Element e of the flattened runs: value x, key k; returns whether it is an entry of the txn's deps.
@@ -1507,50 +1535,161 @@ __device__ __forceinline__ void wave_reg_sort_u32(uint32_t *buf, uint32_t n_vali
 constexpr uint32_t WIN_W = 512;      // bitmap words per key: 16384 ranks below S
 constexpr uint32_t WIN_OUT = 1024;   // entries below the span
 
+// A txn's metadata as the tier uses it: staged in LDS one list item ahead by the prefetch wave (below)
+template <int WK>
+struct WinTxn {
+    uint32_t t, j0, nk, E, S, trank, tz;
+    uint64_t e0, abase;
+    uint32_t koff[WK];   // dep_off[j0 + k] - e0: key k's first entry among the txn's
+};
+
 template <int WK>
 struct WinLds {
     uint32_t bm[WK][WIN_W];
     uint32_t un[WIN_W];
     uint16_t pre[WK + 1][WIN_W];   // exclusive prefix popcounts per series (series WK... = the union, index nk)
     uint32_t out[WIN_OUT];         // (rank << 6 | key) of the entries below the span
-    RunsT<WK> R;
+    uint32_t out2[WIN_OUT];        // ... sorted, when the waves' sorted quarters are merged
+    RunsT<WK> R[2];                // [list item of the block & 1]: the current txn's runs, the next one's
+    WinTxn<WK> T[2];
     uint32_t kc[WK], out_k[WK], ser_tot[WK + 1];
     uint32_t n_out, kept, d_out, bad, minr;
 };
 
+// The loads of the next list item, in flight in the prefetch wave's registers while the block works on the current txn.
+// They depend on the list item alone, a chain three levels deep (list -> txn -> pairs); one level is issued per phase of
+// the current iteration, so each has landed when the next level needs it.
+struct WinPre {
+    uint32_t t, j0, j1;
+    uint4 ti;
+    uint64_t ao, dk;   // dk: lane k <= nk: dep_off[j0 + k]
+    uint32_t cz0, cz1;
+    RecRaw rr;         // lane k < nk: key k's record
+};
+
+// x in a vector register: a load indexed by it is a vector load. The prefetch chain starts from a block-uniform list index;
+// as scalar loads its levels would be waited for at the next block barrier (scalar loads and LDS share a counter), as
+// vector loads they stay in flight across the barriers until their values are used.
+__device__ __forceinline__ uint32_t in_vgpr(uint32_t x)
+{
+    asm volatile("" : "+v"(x));
+    return x;
+}
+
+__device__ __forceinline__ void win_pre_txn(WinPre &p, const V2View &v, const V2Out &o, uint32_t t)
+{
+    p.t = t;
+    p.j0 = o.key_off[t]; p.j1 = o.key_off[t + 1];
+    p.ti = v.tinfo[t];
+    p.ao = o.arena_off[t];
+}
+
+__device__ __forceinline__ void win_pre_keys(WinPre &p, const V2Out &o, const uint64_t *cnt)
+{
+    const uint32_t lane = lane_id(), nk = p.j1 - p.j0;
+    p.dk = lane <= nk ? o.dep_off[p.j0 + lane] : 0ull;
+    p.cz0 = o.cnz[p.j0]; p.cz1 = o.cnz[p.j1];
+    p.rr = RecRaw{};
+    if (lane < nk) p.rr = load_rec_raw(o.rec, o.irec32, cnt, p.j0 + lane);
+}
+
+// (one wave) the landed loads into the LDS record and runs of the next iteration
+template <int WK>
+__device__ __forceinline__ void win_pre_land(WinTxn<WK> &T, RunsT<WK> &R, const WinPre &p)
+{
+    const uint32_t lane = lane_id(), nk = p.j1 - p.j0;
+    const uint64_t e0 = shfl_idx(p.dk, 0), e1 = shfl_idx(p.dk, (int)nk);
+    if (lane < nk) T.koff[lane] = (uint32_t)(p.dk - e0);
+    if (lane == 0) {
+        T.t = p.t; T.j0 = p.j0; T.nk = nk; T.E = (uint32_t)(e1 - e0);
+        T.S = p.ti.y; T.trank = p.ti.x; T.tz = p.ti.z;
+        T.e0 = e0; T.abase = p.ao + (p.cz1 - p.cz0);
+    }
+    finish_runs(R, p.rr, p.j0, nk);
+}
+
+// locate_elem with fixed trip counts (MAXK a power of two): the LDS reads of a thread's WIN_GU elements are independent and
+// interleave, where the data-dependent loops of locate_elem run one element after the other
+template <int MAXK>
+__device__ __forceinline__ void locate_elem_flat(const RunsT<MAXK> &R, uint32_t nk, uint32_t e, uint32_t &idx, uint32_t &k, bool &r3,
+                                                 bool &inl)
+{
+    static_assert((MAXK & (MAXK - 1)) == 0, "a power of two");
+    k = 0;
+#pragma unroll
+    for (uint32_t st = MAXK / 2; st > 0; st >>= 1) {
+        const uint32_t m = k + st, kb = R.kbase[m];
+        if (m < nk && kb <= e) k = m;
+    }
+    const uint32_t off = e - R.kbase[k];
+    inl = R.m[k] == INLINE_M;
+    uint32_t r = 0;   // the last run that starts at or before off (the run starts ascend)
+#pragma unroll
+    for (int q = 1; q < NRUN; ++q) r += R.pre[k][q] <= off ? 1u : 0u;
+    if (inl) { idx = 16 * R.start[k][0] + off; r3 = false; return; }
+    idx = R.start[k][r] + (off - R.pre[k][r]);
+    r3 = r == 6;
+}
+
 #ifdef ACC_PHASE_PROF
-// tuning build only: per workgroup of the window tier, summed over its txns: cycles in runs + span low end, bitmap gather,
-// below-span sort, prefix popcounts, the span's writes, rank -> TxnId; then txns, entries, span words, entries below
+// tuning build only: per workgroup of the window tier, summed over its txns: cycles in the span's low end, bitmap gather,
+// union words (+ the block sort of a long list below), below-span sort and writes beside the prefix popcounts, the span's
+// writes; then txns, entries, span words, entries below; [9] the wait between txns
 __device__ unsigned long long *g_win_prof;
 #define WN_PH(k) do { if (tid == 0) { const unsigned long long t_ = clock64(); wp[k] += t_ - wq; wq = t_; } } while (0)
 #else
 #define WN_PH(k) ((void)0)
 #endif
+constexpr int WIN_GU = 8;  // independent elements per thread and round of the gather (a round: 2,048 raw elements)
+constexpr int WIN_U = 4;   // TxnId loads in flight per union word of a thread in the span's writes
 template <int WK>
 __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restrict__ list, const uint64_t *__restrict__ cnt_dev,
                                                        V2View v, const uint64_t *__restrict__ cnt, V2Out o)
 {
     __shared__ WinLds<WK> L;
+    static_assert(sizeof(WinLds<WK>) <= 64 * 1024, "the window tier's LDS");
+    static_assert(WIN_W <= 2 * BLOCK, "a thread takes at most two union words");
+    static_assert(WIN_OUT <= 4 * BLOCK, "a thread maps at most four TxnIds below the span");
     const uint32_t tid = threadIdx.x, wave = tid >> 6, lane = lane_id();
     const uint32_t n_list = (uint32_t)*cnt_dev;
-    RunsT<WK> &R = L.R;
+    // The last wave prefetches: the next list item's txn record, offsets and count-pass records are loaded during the
+    // current txn's phases and land in L.T / L.R [cur ^ 1], so an iteration starts with its runs and offsets in LDS
+    // instead of walking the chain list -> key_off / tinfo -> dep_off -> cnt / records with the block waiting on each.
+    const bool pw = wave == WAVES - 1;
+    WinPre np{};
+    if (pw && blockIdx.x < n_list) {   // the block's first item: the chain in one go
+        win_pre_txn(np, v, o, list[blockIdx.x]);
+        win_pre_keys(np, o, cnt);
+        win_pre_land(L.T[0], L.R[0], np);
+    }
+    __syncthreads();
 #ifdef ACC_PHASE_PROF
     unsigned long long wp[10] = {}, wq = clock64();
 #endif
-    for (uint32_t b = blockIdx.x; b < n_list; b += gridDim.x) {
+    uint32_t cur = 0;
+    // (every path to the next iteration, the two `continue`s too, lands the prefetch before its barrier and flips cur here)
+    for (uint32_t b = blockIdx.x; b < n_list; b += gridDim.x, cur ^= 1u) {
         WN_PH(9);
-        const uint32_t t = list[b];
-        const TxnCtx c = txn_ctx(v, o, t);
-        const uint32_t S = v.tinfo[t].y;
-        if (tid < 64) compute_runs(R, v, o, cnt, c);
+        const bool pre = pw && b + gridDim.x < n_list;   // (never reads list[] at or past n_list)
+        const WinTxn<WK> &T = L.T[cur];
+        RunsT<WK> &R = L.R[cur];
+        TxnCtx c;
+        c.t = T.t; c.j0 = T.j0; c.nk = T.nk; c.j1 = c.j0 + c.nk; c.e0 = T.e0; c.E = T.E; c.trank = T.trank;
+        const uint32_t t = c.t, S = T.S;
+        c.bq = S != c.trank;
+        c.wk = witnesses(T.tz >> 3);
+        c.wc = wk_classes(c.wk);
+        const uint64_t abase = T.abase;
+        uint32_t tn = 0;
+        if (pre) tn = list[in_vgpr(b + gridDim.x)];   // level 1
         if (tid < (uint32_t)WK) { L.kc[tid] = 0; L.out_k[tid] = 0; }
         if (tid == 0) { L.n_out = 0; L.kept = 0; L.bad = 0; L.minr = 0xFFFFFFFFu; }
         __syncthreads();
         // the span's low end: the smallest rank an entry can have (a class run's first entry, an inline record's first
         // entry, any entry of a short R3 run), so the bitmaps cover only [min, S) instead of 16,384 ranks below S
+        uint32_t mn = 0xFFFFFFFFu;
         if (tid < c.nk) {
             const uint32_t k = tid;
-            uint32_t mn = 0xFFFFFFFFu;
             if (R.m[k] == INLINE_M) {
                 if (R.pre[k][1] > 0) mn = v.irec32[IREC_W * (size_t)R.start[k][0]];
             } else {
@@ -1559,16 +1698,24 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
                     if (R.pre[k][q + 1] > R.pre[k][q]) mn = min(mn, v.list_rank[R.start[k][q]]);
                 if (R.pre[k][7] - R.pre[k][6] > 256) mn = 0u;   // (a long R3 run: from 0; a short one: below)
             }
-            atomicMin(&L.minr, mn);
         }
-        // the short R3 runs' smallest ranks, the block's threads side by side (one thread walking a run serially waits on
-        // one load at a time)
-        for (uint32_t k = 0; k < c.nk; ++k) {
-            if (R.m[k] == INLINE_M) continue;
-            const uint32_t l3 = R.pre[k][7] - R.pre[k][6];
-            if (l3 > 256 || tid >= l3) continue;
-            atomicMin(&L.minr, v.bc_rank[R.start[k][6] + tid]);
+        // the short R3 runs' smallest ranks, the block's threads side by side, every key's load issued before the first is
+        // used (one thread walking a run, or one key after the other, waits on one load at a time)
+        uint32_t r3v[WK];
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)WK; ++k) {
+            r3v[k] = 0xFFFFFFFFu;
+            if (k < c.nk && R.m[k] != INLINE_M) {
+                const uint32_t l3 = R.pre[k][7] - R.pre[k][6];
+                if (l3 <= 256 && tid < l3) r3v[k] = v.bc_rank[R.start[k][6] + tid];
+            }
         }
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)WK; ++k) mn = min(mn, r3v[k]);
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) mn = min(mn, xor_lanes(mn, d));
+        if (lane == 0) atomicMin(&L.minr, mn);
+        if (pre) win_pre_txn(np, v, o, tn);   // level 2 (issued, not waited for)
         __syncthreads();
         const uint32_t lo_span = S > WIN_W * 32 ? S - WIN_W * 32 : 0u;
         uint32_t base = max(lo_span, min(L.minr, S));
@@ -1582,23 +1729,30 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
         const uint32_t total = R.total;
         // ---- gather: bits of the span, the entries below it to the list
         uint32_t kept = 0;
-        for (uint32_t e0 = tid; e0 < total; e0 += BIG_GU * BLOCK) {
-            uint32_t idx[BIG_GU], kk[BIG_GU], x[BIG_GU];
-            bool r3[BIG_GU], in[BIG_GU], il[BIG_GU];
+        for (uint32_t e0 = tid; e0 < total; e0 += WIN_GU * BLOCK) {
+            uint32_t idx[WIN_GU], kk[WIN_GU], x[WIN_GU];
+            bool r3[WIN_GU], in[WIN_GU], il[WIN_GU];
 #pragma unroll
-            for (int u = 0; u < BIG_GU; ++u) {
+            for (int u = 0; u < WIN_GU; ++u) {
                 const uint32_t e = e0 + u * BLOCK;
                 in[u] = e < total;
                 idx[u] = 0; kk[u] = 0; r3[u] = false; il[u] = false;
-                if (in[u]) locate_elem(R, c.nk, e, idx[u], kk[u], r3[u], il[u]);
+                if (in[u]) locate_elem_flat(R, c.nk, e, idx[u], kk[u], r3[u], il[u]);
             }
 #pragma unroll
-            for (int u = 0; u < BIG_GU; ++u)
+            for (int u = 0; u < WIN_GU; ++u)
                 x[u] = in[u] ? (il[u] ? inl_entry(v.irec32, v.rec, idx[u]) : r3[u] ? v.bc_rank[idx[u]] : v.list_rank[idx[u]]) : 0u;
+            // an R3 element's filter columns with its rank, not after it (r3 implies in)
+            uint32_t ex[WIN_GU], kd[WIN_GU];
 #pragma unroll
-            for (int u = 0; u < BIG_GU; ++u) {
+            for (int u = 0; u < WIN_GU; ++u) {
+                ex[u] = r3[u] ? v.bc_exec[idx[u]] : 0u;
+                kd[u] = r3[u] ? (uint32_t)v.bc_kind[idx[u]] : 0u;
+            }
+#pragma unroll
+            for (int u = 0; u < WIN_GU; ++u) {
                 bool keep = in[u] && (il[u] || !(c.bq && x[u] == c.trank));
-                if (keep && r3[u]) keep = v.bc_exec[idx[u]] >= R.m[kk[u]] && ((c.wk >> v.bc_kind[idx[u]]) & 1u);
+                if (keep && r3[u]) keep = ex[u] >= R.m[kk[u]] && ((c.wk >> kd[u]) & 1u);
                 if (!keep) continue;
                 ++kept;
                 if (x[u] >= base) {
@@ -1612,11 +1766,13 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
                 }
             }
         }
+        if (pre) win_pre_keys(np, o, cnt);   // level 3 (the pair range landed during the gather)
         kept = wave_inclusive(kept, OpAdd<uint32_t>());
         if (lane == 63) atomicAdd(&L.kept, kept);
         __syncthreads();
         if (L.kept != c.E || L.bad) {
             if (tid == 0) atomicAdd((unsigned long long *)&o.gstat[2], 1ull);
+            if (pre) win_pre_land(L.T[cur ^ 1u], L.R[cur ^ 1u], np);
             __syncthreads();
             continue;
         }
@@ -1630,6 +1786,7 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
                 const uint32_t f = (uint32_t)atomicAdd((unsigned long long *)&o.gstat[1], 1ull);
                 o.big_list[f] = t;
             }
+            if (pre) win_pre_land(L.T[cur ^ 1u], L.R[cur ^ 1u], np);
             __syncthreads();
             continue;
         }
@@ -1639,51 +1796,77 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
             for (uint32_t k = 0; k < c.nk; ++k) u |= L.bm[k][w];
             L.un[w] = u;
         }
-        // ---- the entries below the span, sorted (rank, key): one wave in registers up to 512 (no block barriers), the
-        // block's LDS bitonic beyond
-        if (n_out > 1) {
-            if (n_out <= 128) { if (wave == 0) wave_reg_sort_u32<2>(L.out, n_out); }
-            else if (n_out <= 512) { if (wave == 0) wave_reg_sort_u32<8>(L.out, n_out); }
-            else {
-                uint32_t n2 = 64;
-                while (n2 < n_out) n2 <<= 1;
-                for (uint32_t q = n_out + tid; q < n2; q += BLOCK) L.out[q] = 0xFFFFFFFFu;
-                __syncthreads();
-                block_bitonic<uint32_t, BLOCK>(L.out, n2);
+        // ---- the entries below the span, sorted (rank, key). Up to 512: one wave in registers (no block barriers) beside
+        // the other waves' prefix popcounts. Beyond: every wave sorts a quarter in registers, then each entry finds its
+        // place among the other quarters' by binary search (the entries are distinct) and goes there in out2
+        const bool blk_sort = n_out > 512;
+        const uint32_t *srt = L.out;
+        if (blk_sort) {
+            const uint32_t Q = (n_out + WAVES - 1) / WAVES;   // <= 256
+            const uint32_t q0 = min(wave * Q, n_out);
+            wave_reg_sort_u32<4>(L.out + q0, min(Q, n_out - q0));
+            __syncthreads();
+            for (uint32_t i = tid; i < n_out; i += BLOCK) {
+                const uint32_t x = L.out[i], own = i / Q;
+                uint32_t pos = i - own * Q;
+                for (uint32_t oq = 0; oq < (uint32_t)WAVES; ++oq) {
+                    if (oq == own) continue;
+                    const uint32_t s0 = min(oq * Q, n_out);
+                    uint32_t lo = s0, hi = min(s0 + Q, n_out);
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (L.out[mid] < x) lo = mid + 1; else hi = mid;
+                    }
+                    pos += lo - s0;
+                }
+                L.out2[pos] = x;
             }
+            srt = L.out2;
         }
         __syncthreads();
         WN_PH(2);
-        // ---- exclusive prefix popcounts of every series (keys 0..nk-1, union = nk): a wave per series, 8 words a lane
-        for (uint32_t s = wave; s <= c.nk; s += WAVES) {
-            const uint32_t *words = s < c.nk ? L.bm[s] : L.un;
-            uint32_t run = 0;
-            for (uint32_t w0 = 0; w0 < nw; w0 += 512) {
-                const uint32_t wl = w0 + lane * 8;
-                uint32_t pc[8], sum = 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) { pc[i] = wl + i < nw ? (uint32_t)__popc(words[wl + i]) : 0u; sum += pc[i]; }
-                const uint32_t incl = wave_inclusive(sum, OpAdd<uint32_t>());
-                uint32_t r = run + incl - sum;
-#pragma unroll
-                for (int i = 0; i < 8; ++i) if (wl + i < nw) { L.pre[s][wl + i] = (uint16_t)r; r += pc[i]; }
-                run += shfl_idx(incl, 63);
-            }
-            if (lane == 0) L.ser_tot[s] = run;
+        const bool side = n_out > 1 && !blk_sort;   // wave 0 sorts; the other waves take the prefix popcounts
+        if (side && wave == 0) {
+            if (n_out <= 128) wave_reg_sort_u32<2>(L.out, n_out);
+            else if (n_out <= 256) wave_reg_sort_u32<4>(L.out, n_out);
+            else wave_reg_sort_u32<8>(L.out, n_out);
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         }
-        WN_PH(3);
-        const uint64_t abase = o.arena_off[t] + (o.cnz[c.j1] - o.cnz[c.j0]);
+        // ---- exclusive prefix popcounts of every series (keys 0..nk-1, union = nk): a wave per series, 8 words a lane
+        const uint32_t pw0 = side ? 1u : 0u;
+        if (wave >= pw0) {
+            for (uint32_t s = wave - pw0; s <= c.nk; s += WAVES - pw0) {
+                const uint32_t *words = s < c.nk ? L.bm[s] : L.un;
+                uint32_t run = 0;
+                for (uint32_t w0 = 0; w0 < nw; w0 += 512) {
+                    const uint32_t wl = w0 + lane * 8;
+                    uint32_t pc[8], sum = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) { pc[i] = wl + i < nw ? (uint32_t)__popc(words[wl + i]) : 0u; sum += pc[i]; }
+                    const uint32_t incl = wave_inclusive(sum, OpAdd<uint32_t>());
+                    uint32_t r = run + incl - sum;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) if (wl + i < nw) { L.pre[s][wl + i] = (uint16_t)r; r += pc[i]; }
+                    run += shfl_idx(incl, 63);
+                }
+                if (lane == 0) L.ser_tot[s] = run;
+            }
+        }
         uint32_t *dsc = o.dep_scratch + c.e0;
-        // ---- the sorted entries below the span (one wave): distinct TxnIds first in the union, each key's first slots
+        uint32_t *drank = blk_sort ? L.out : L.out2;   // (the buffer the sorted entries are not in)
+        // ---- the sorted entries below the span (one wave): distinct TxnIds first in the union, each key's first slots;
+        // their ranks go to LDS and the block maps them to TxnIds with the span's (a load per chunk here would serialise
+        // the chunks)
         if (wave == 0 && n_out) {
             const uint64_t lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
             uint32_t distinct = 0;
             for (uint32_t q0 = 0; q0 < n_out; q0 += 64) {
                 const uint32_t q = q0 + lane;
                 const bool in = q < n_out;
-                const uint32_t xq = in ? L.out[q] : 0u;
+                const uint32_t xq = in ? srt[q] : 0u;
                 const uint32_t kj = xq & 63u;
-                const bool nw_ = in && (q == 0 || (L.out[q - 1] >> 6) != (xq >> 6));
+                const bool nw_ = in && (q == 0 || (srt[q - 1] >> 6) != (xq >> 6));
                 const uint64_t bal = __ballot(nw_);
                 const uint32_t idx = distinct + (uint32_t)__popcll(bal & lt) + (nw_ ? 1u : 0u) - 1u;
                 uint64_t peers = __ballot(in);
@@ -1694,8 +1877,8 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
                 }
                 const uint32_t before = (uint32_t)__popcll(peers & lt);
                 if (in) {
-                    o.arena[abase + (o.dep_off[c.j0 + kj] - c.e0) + L.kc[kj] + before] = (int32_t)idx;
-                    if (nw_) dsc[idx] = o.txn_of_rank[xq >> 6];
+                    o.arena[abase + T.koff[kj] + L.kc[kj] + before] = (int32_t)idx;
+                    if (nw_) drank[idx] = xq >> 6;
                 }
                 __builtin_amdgcn_wave_barrier();
                 if (in && before == 0) L.kc[kj] += (uint32_t)__popcll(peers);
@@ -1707,49 +1890,93 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
         } else if (tid == 0) {
             L.d_out = 0;
         }
+        if (pre) win_pre_land(L.T[cur ^ 1u], L.R[cur ^ 1u], np);
         __syncthreads();
-        // ---- the span: item (series, word); a key's words give its keysToTxnIds indices (union index = word prefix +
-        // popcount), the union's words its TxnId ranks, mapped to TxnIds below with independent loads in flight
+        WN_PH(3);
+        // ---- the span. The union's words give its TxnId ranks: a thread takes WIN_U set bits of each of its (at most
+        // two: WIN_W <= 2 BLOCK) words per round, loads their TxnIds together and stores them in place (no rank pass, no
+        // read-back).
         const uint32_t d_out = L.d_out, nu = L.ser_tot[c.nk];
-        const uint32_t items = (c.nk + 1) * nw;
+        uint32_t bits[2], rb[2], at[2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint32_t w = tid + (uint32_t)u * BLOCK;
+            const bool okw = w < nw;
+            bits[u] = okw ? L.un[w] : 0u;
+            rb[u] = base + 32 * w;
+            at[u] = okw ? d_out + L.pre[c.nk][w] : 0u;
+        }
+        uint32_t r[2][WIN_U], br[4];
+        bool h[2][WIN_U];
+        // the first round's loads, and those of the TxnIds below the span (d_out <= WIN_OUT = 4 a thread), stay in flight
+        // over the key items
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int q = 0; q < WIN_U; ++q) {
+                h[u][q] = bits[u] != 0;
+                r[u][q] = h[u][q] ? rb[u] + (uint32_t)__builtin_ctz(bits[u]) : 0u;
+                bits[u] &= bits[u] - 1;
+            }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) br[q] = tid + (uint32_t)q * BLOCK < d_out ? drank[tid + (uint32_t)q * BLOCK] : 0u;
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int q = 0; q < WIN_U; ++q)
+                if (h[u][q]) r[u][q] = o.txn_of_rank[r[u][q]];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (tid + (uint32_t)q * BLOCK < d_out) br[q] = o.txn_of_rank[br[q]];
+        // a key's words give its keysToTxnIds indices (union index = word prefix + popcount): item (key, word), the key's
+        // first entry from LDS
+        const uint32_t items = c.nk * nw;
         for (uint32_t i = tid; i < items; i += BLOCK) {
             const uint32_t s = i / nw, w = i - s * nw;
+            uint32_t kb = L.bm[s][w];
+            if (!kb) continue;
             const uint32_t ubase = d_out + L.pre[c.nk][w];
-            if (s == c.nk) {
-                uint32_t bits = L.un[w], j = 0;
-                while (bits) {
-                    dsc[ubase + j] = base + 32 * w + (uint32_t)__builtin_ctz(bits);
-                    bits &= bits - 1;
-                    ++j;
-                }
-            } else {
-                uint32_t bits = L.bm[s][w];
-                if (!bits) continue;
-                const uint32_t uw = L.un[w];
-                int32_t *dst = o.arena + abase + (o.dep_off[c.j0 + s] - c.e0) + L.out_k[s] + L.pre[s][w];
-                uint32_t j = 0;
-                while (bits) {
-                    const uint32_t b2 = (uint32_t)__builtin_ctz(bits);
-                    dst[j] = (int32_t)(ubase + (uint32_t)__popc(uw & ((1u << b2) - 1u)));
-                    bits &= bits - 1;
-                    ++j;
-                }
+            const uint32_t uw = L.un[w];
+            int32_t *dst = o.arena + abase + T.koff[s] + L.out_k[s] + L.pre[s][w];
+            uint32_t j = 0;
+            while (kb) {
+                const uint32_t b2 = (uint32_t)__builtin_ctz(kb);
+                dst[j] = (int32_t)(ubase + (uint32_t)__popc(uw & ((1u << b2) - 1u)));
+                kb &= kb - 1;
+                ++j;
             }
         }
-        __syncthreads();   // the block's rank writes are visible to the block
-        WN_PH(4);
-        for (uint32_t i0 = d_out + tid; i0 < d_out + nu; i0 += 4 * BLOCK) {
-            uint32_t r[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) r[u] = i0 + (uint32_t)u * BLOCK < d_out + nu ? dsc[i0 + (uint32_t)u * BLOCK] : 0u;
+        for (int q = 0; q < 4; ++q)
+            if (tid + (uint32_t)q * BLOCK < d_out) dsc[tid + (uint32_t)q * BLOCK] = br[q];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (i0 + (uint32_t)u * BLOCK < d_out + nu) r[u] = o.txn_of_rank[r[u]];
+        for (int u = 0; u < 2; ++u)
 #pragma unroll
-            for (int u = 0; u < 4; ++u) if (i0 + (uint32_t)u * BLOCK < d_out + nu) dsc[i0 + (uint32_t)u * BLOCK] = r[u];
+            for (int q = 0; q < WIN_U; ++q)
+                if (h[u][q]) dsc[at[u]++] = r[u][q];
+        while (bits[0] | bits[1]) {   // words with more than WIN_U set bits
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int q = 0; q < WIN_U; ++q) {
+                    h[u][q] = bits[u] != 0;
+                    r[u][q] = h[u][q] ? rb[u] + (uint32_t)__builtin_ctz(bits[u]) : 0u;
+                    bits[u] &= bits[u] - 1;
+                }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int q = 0; q < WIN_U; ++q)
+                    if (h[u][q]) r[u][q] = o.txn_of_rank[r[u][q]];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int q = 0; q < WIN_U; ++q)
+                    if (h[u][q]) dsc[at[u]++] = r[u][q];
         }
         if (tid == 0) o.u_cnt[t] = d_out + nu;
         __syncthreads();
-        WN_PH(5);
+        WN_PH(4);
     }
 #ifdef ACC_PHASE_PROF
     if (tid == 0)
@@ -2134,6 +2361,7 @@ __device__ __forceinline__ void group_reg_sort(EntT *buf, uint32_t sub, uint32_t
 #ifdef ACC_PHASE_PROF
 // tuning build only (tools/build_prof.sh): per-phase wave cycles of k_v3_stream, one row of 8 per wave (no atomics)
 __device__ unsigned long long *g_st_prof;
+__device__ unsigned long long *g_sr_prof;   // the RUNS instance's rows (its own waves: the lean pass's rows stay as they were)
 #define ST_PH(i) ph[i] = clock64()
 #else
 #define ST_PH(i) ((void)0)
@@ -2367,8 +2595,8 @@ __global__ __launch_bounds__(NT, ACC_ST_WAVES * 64 / NT) void k_v3_stream(V3Stre
     }
 #ifdef ACC_PHASE_PROF
     ST_PH(6);
-    if (lane == 0 && !LIST) {
-        unsigned long long *row = g_st_prof + 8 * (size_t)tile;
+    if (lane == 0) {
+        unsigned long long *row = (LIST ? g_sr_prof : g_st_prof) + 8 * (size_t)tile;
         for (int i = 0; i < 6; ++i) row[i] = ph[i + 1] - ph[i];
         row[7] = 1;
     }
@@ -2944,18 +3172,22 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     V2Out wo{};
     bool win_ok = false;
 #ifdef ACC_PHASE_PROF
-    unsigned long long *win_buf = nullptr;
+    unsigned long long *win_buf = nullptr, *sr_buf = nullptr;
+    size_t sr_rows = 0;
 #endif
     uint64_t *vcnt = nullptr;
     uint32_t *med_list = nullptr, *big_list = nullptr, *fb_list = nullptr;
+    // persistent write-tier grids: min(work, the tier's default, the cap in flags bits 16..31 when set (testing))
+    const unsigned tgm = (ctx->flags >> ACC_OPT_TIER_GRID_SHIFT) ? (ctx->flags >> ACC_OPT_TIER_GRID_SHIFT) : ~0u;
+    auto tier_grid = [&](unsigned work, unsigned dflt) { return dim3(std::max(1u, std::min(std::min(work, dflt), tgm))); };
     // the sorting tiers: medium (<= MED_CAP raw entries), block (<= BIG_E), huge (<= HUGE_E, fed by the block tier)
     auto sort_tiers = [&](bool with_med) {
         if (with_med)
-            launch(ctx, "v2_write_med", k_v2_write_big<MED_CAP, BLOCK>, dim3(std::min<unsigned>(nbig, 2048)), dim3(BLOCK), 0,
+            launch(ctx, "v2_write_med", k_v2_write_big<MED_CAP, BLOCK>, tier_grid(nbig, 2048), dim3(BLOCK), 0,
                    (const uint32_t *)med_list, vv, (const uint64_t *)vcnt, wo);
-        launch(ctx, "v2_write_big", k_v2_write_big<BIG_E, 512>, dim3(std::min<unsigned>(nbig, 1024)), dim3(512), 0,
+        launch(ctx, "v2_write_big", k_v2_write_big<BIG_E, 512>, tier_grid(nbig, 1024), dim3(512), 0,
                (const uint32_t *)big_list, vv, (const uint64_t *)vcnt, wo);
-        launch(ctx, "v2_write_huge", k_v2_write_big<HUGE_E, 1024>, dim3(std::min<unsigned>(nbig, 64)), dim3(1024), 0,
+        launch(ctx, "v2_write_huge", k_v2_write_big<HUGE_E, 1024>, tier_grid(nbig, 64), dim3(1024), 0,
                (const uint32_t *)wo.huge_list, vv, (const uint64_t *)vcnt, wo);
     };
     uint32_t *dep_st = ctx->get<uint32_t>("v3_dep_stream", (size_t)n * ST_SLOT);   // stream txns' TxnIds, slot t * ST_SLOT
@@ -3018,19 +3250,19 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
 #endif
             // the window tier takes every big txn of <= 16 keys; the sorting tiers run after the next host sync, only
             // when it passed txns on or some txn has more keys (no launch without work)
-            launch(ctx, "v2_write_win", k_v2_write_win<8>, dim3(std::min<unsigned>(nbig, 2048)), dim3(BLOCK), 0,
+            launch(ctx, "v2_write_win", k_v2_write_win<8>, tier_grid(nbig, 2048), dim3(BLOCK), 0,
                    (const uint32_t *)ctx->get<uint32_t>("v2_w8_list", nbig), (const uint64_t *)(gstat + 7), vv,
                    (const uint64_t *)vcnt, wo);
             // (> 8 keys is rare: a small persistent grid, launched only when the mark pass saw a big txn of 9-16 keys)
             if (any16)
-                launch(ctx, "v2_write_win16", k_v2_write_win<16>, dim3(std::min<unsigned>(nbig, 256)), dim3(BLOCK), 0,
+                launch(ctx, "v2_write_win16", k_v2_write_win<16>, tier_grid(nbig, 256), dim3(BLOCK), 0,
                        (const uint32_t *)ctx->get<uint32_t>("v2_w16_list", nbig), (const uint64_t *)(gstat + 8), vv,
                        (const uint64_t *)vcnt, wo);
         } else if (big_ok) {
             sort_tiers(true);
         } else {
             // ranks beyond 25 bits: u64 records in the wave tier (k_v3_route sends everything else to the global path)
-            launch(ctx, "v2_write_medium", k_v2_write_medium, dim3(std::min<unsigned>(gB, 2048)), dim3(BLOCK), 0,
+            launch(ctx, "v2_write_medium", k_v2_write_medium, tier_grid(gB, 2048), dim3(BLOCK), 0,
                    (const uint64_t *)gstat, (const uint32_t *)med_list, vv, (const uint64_t *)vcnt, wo);
         }
         ctx->launch_stream = nullptr;
@@ -3061,6 +3293,10 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
             sr.list = rlist; sr.n = nrun;
             const uint32_t rblocks = (nrun + tt - 1) / tt;
             ctx->launch_stream = ctx->aux[1];
+#ifdef ACC_PHASE_PROF
+            sr_rows = (size_t)rblocks * (st_nt / 64);
+            sr_buf = prof_arm(ctx, "v3_sr_prof", HIP_SYMBOL(g_sr_prof), 8 * sr_rows, ctx->aux[1]);
+#endif
             if (rbits <= 28) launch(ctx, "v3_stream_runs", k_v3_stream<uint32_t, st_nt, ST_G, ST_N2, true, true>, dim3(rblocks), dim3(st_nt), 0, sr);
             else launch(ctx, "v3_stream_runs", k_v3_stream<uint64_t, st_nt, ST_G, ST_N2, true, true>, dim3(rblocks), dim3(st_nt), 0, sr);
             ctx->launch_stream = nullptr;
@@ -3088,10 +3324,25 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     if (nbig && win_ok) {
         const std::vector<unsigned long long> h = prof_read(win_buf, 10, st);
         const double nt = h[6] ? (double)h[6] : 1.0;
-        fprintf(stderr, "[win_phase] txns=%llu avg cycles per txn (thread 0 of each block): runs+lowend %.0f gather %.0f "
-                "below-sort %.0f prefix %.0f span-writes %.0f rank-map %.0f list-wait %.0f | avg E %.1f span words %.1f below %.1f\n",
-                h[6], h[0] / nt, h[1] / nt, h[2] / nt, h[3] / nt, h[4] / nt, h[5] / nt, h[9] / nt, h[7] / nt,
+        fprintf(stderr, "[win_phase] txns=%llu avg cycles per txn (thread 0 of each block): lowend %.0f gather %.0f "
+                "union %.0f sort|prefix|below %.0f span-writes %.0f list-wait %.0f | avg E %.1f span words %.1f below %.1f\n",
+                h[6], h[0] / nt, h[1] / nt, h[2] / nt, h[3] / nt, h[4] / nt, h[9] / nt, h[7] / nt,
                 (double)(h[8] >> 32) / nt, (double)(h[8] & 0xFFFFFFFFull) / nt);
+    }
+#endif
+#ifdef ACC_PHASE_PROF
+    if (sr_buf) {
+        const std::vector<unsigned long long> h = prof_read(sr_buf, 8 * sr_rows, st);
+        double sum[6] = {};
+        size_t w = 0;
+        for (size_t r = 0; r < sr_rows; ++r) {
+            if (!h[8 * r + 7]) continue;
+            ++w;
+            for (int i = 0; i < 6; ++i) sum[i] += (double)h[8 * r + i];
+        }
+        const double d = w ? (double)w : 1.0;
+        fprintf(stderr, "[sr_phase] waves=%zu avg cycles: setup %.0f records %.0f gather %.0f sort %.0f emit-lds %.0f lookback+copy %.0f\n",
+                w, sum[0] / d, sum[1] / d, sum[2] / d, sum[3] / d, sum[4] / d, sum[5] / d);
     }
 #endif
     finish();

@@ -112,6 +112,10 @@ typedef struct acc_rlist {
 #define ACC_OPT_FORCE_REPLAY 0x2u  /* always take the exact FAST-bisection replay path (testing) */
 #define ACC_OPT_NO_WINDOW_TIER 0x4u  /* KeyDeps: the sorting build tiers instead of the window tier (testing) */
 #define ACC_OPT_RD_WIDE_SORT 0x8u    /* RangeDeps: 64-bit sort keys in the lane-group build tiers (testing) */
+/* flags bits 16..31 (testing): persistent KeyDeps write-tier grids, the window tier and the sorting tiers, are capped at
+ * this many blocks (0: the defaults). It rides in flags because the layout of acc_opts is fixed. */
+#define ACC_OPT_TIER_GRID_SHIFT 16
+#define ACC_OPT_TIER_GRID(n) ((uint32_t)(n) << ACC_OPT_TIER_GRID_SHIFT)
 #define ACC_OPT_PD_SERIAL 0x10u      /* acc_partial_deps_batch: both halves in order on this context (one buffer set:
                                         less device memory, no overlap) */
 

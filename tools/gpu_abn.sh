@@ -1,13 +1,13 @@
 #!/bin/bash
 # Same-box timing of several library builds: CFGS="2 3" STEPS=20 bash tools/gpu_abn.sh new base u2 ...
 # "new" = the in-tree library ("new+VAR=VALUE": with that environment for bench.py), any other name =
-# tools/ab/<name>.so. Two alternating rounds per config.
+# tools/ab/<name>.so. ROUNDS (default 2) alternating rounds per config.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 steps=${STEPS:-20}
 for cfg in ${CFGS:-2}; do
-    for i in 1 2; do
+    for i in $(seq 1 ${ROUNDS:-2}); do
         for v in "$@"; do
             lib=""; envs=""
             case "$v" in new) ;; new+*) envs="${v#new+}"; envs="${envs//,/ }" ;; *) lib=tools/ab/$v.so ;; esac

@@ -2,8 +2,9 @@
 
 Inputs (both from one GPU box): a bench log of the product library with per-kernel timings
 (ACC_BENCH_KERNELS=1 python bench.py --config 2 --full ...) and a log of the tuning build (tools/build_prof.sh ->
-tools/ab/prof.so, -DACC_PHASE_PROF) whose stderr carries the count pass's [ct_phase] and the stream pass's [st_phase]
-per-wave cycle counters. Usage: python tools/phases_json.py KERNELS_LOG PROF_LOG OUT_JSON"""
+tools/ab/prof.so, -DACC_PHASE_PROF) whose stderr carries the count pass's [ct_phase], the stream pass's [st_phase] (lean instance) and [sr_phase] (RUNS
+instance) per-wave cycle counters and the window tier's [win_phase] per-txn ones. A second PROF_LOG (the parent's
+tuning build) is recorded as "before". Usage: python tools/phases_json.py KERNELS_LOG PROF_LOG OUT_JSON [PROF_LOG_BEFORE]"""
 import json
 import re
 import sys
@@ -39,10 +40,13 @@ def parse_avg(line):
 
 def main():
     klog, plog, out = sys.argv[1:4]
+    before = sys.argv[4] if len(sys.argv) > 4 else None
     k = last_json(klog)
     kern = k.get("kernels_ms_per_step", {})
     ct = phase_lines(plog, "ct_phase")
     st = phase_lines(plog, "st_phase")
+    sr = phase_lines(plog, "sr_phase")
+    win = phase_lines(plog, "win_phase")
     waves_ct = int(re.search(r"waves=(\d+)", ct[-1]).group(1)) if ct else None
     waves_st = int(re.search(r"waves=(\d+)", st[-1]).group(1)) if st else None
     res = {
@@ -55,6 +59,11 @@ def main():
                                   "raw": ct[-1] if ct else None},
         "stream_pass_k_v3_stream": {"waves": waves_st, "avg_cycles_per_wave": parse_avg(st[-1]) if st else None,
                                     "raw": st[-1] if st else None},
+        "stream_pass_runs_instance": {"waves": int(re.search(r"waves=(\d+)", sr[-1]).group(1)) if sr else None,
+                                      "avg_cycles_per_wave": parse_avg(sr[-1]) if sr else None, "raw": sr[-1] if sr else None},
+        "window_tier_k_v2_write_win": {"raw": win[-1] if win else None},
+        "before": {tag: (phase_lines(before, tag) or [None])[-1] for tag in ("win_phase", "st_phase", "sr_phase")}
+        if before else None,
         "note": "per-wave cycles from clock64() brackets in the -DACC_PHASE_PROF tuning build (same kernels, one extra "
                 "store per wave); kernel ms from HIP events around each launch in the product build",
     }
