@@ -49,7 +49,8 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_map_reduce_full", "acc_map_reduce_full_ranges", "acc_latest_deps_merge", "acc_partial_deps_batch",
            "acc_deps_from_json", "acc_deps_to_json",
            "acc_cfk_create", "acc_cfk_destroy", "acc_cfk_update", "acc_cfk_view", "acc_cfk_apply", "acc_cfk_snap_to_batch",
-           "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed", "acc_max_conflicts",
+           "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed",
+           "acc_cfk_map_reduce_full", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
@@ -305,6 +306,14 @@ class CfkMixedQueries(C.Structure):
                 ("end_inclusive", C.c_uint32), ("lane_seg", C.c_uint32)]
 
 
+class CfkRecoveryIn(C.Structure):
+    _fields_ = [("n_query", C.c_uint32), ("mem", C.c_uint32), ("n_pairs", C.c_uint64), ("n_ranges", C.c_uint64),
+                ("test_txn", TsCols), ("key_off", C.c_void_p), ("key_code", C.c_void_p),
+                ("rng_off", C.c_void_p), ("rng_start", C.c_void_p), ("rng_end", C.c_void_p),
+                ("end_inclusive", C.c_uint32), ("started_at", C.c_uint8), ("test_dep", C.c_uint8),
+                ("test_status", C.c_uint8), ("flags", C.c_uint8), ("test_kinds", C.c_int32)]
+
+
 ACC_RCMD_ERASED = 1
 
 
@@ -525,6 +534,8 @@ def load():
         L.acc_cfk_keydeps.restype = C.c_int
         L.acc_cfk_keydeps_mixed.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkMixedQueries), C.POINTER(KeydepsView)]
         L.acc_cfk_keydeps_mixed.restype = C.c_int
+        L.acc_cfk_map_reduce_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRecoveryIn), C.POINTER(KeydepsView)]
+        L.acc_cfk_map_reduce_full.restype = C.c_int
         L.acc_maxconflicts_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.acc_maxconflicts_create.restype = C.c_int
         L.acc_maxconflicts_destroy.argtypes = [C.c_void_p]

@@ -1112,6 +1112,34 @@ class CfkStore:
         self.ctx.check(self.ctx._lib.acc_cfk_keydeps_mixed(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
         return self.ctx.copy_out(view, None)
 
+    def map_reduce_full(self, queries: dict, started_at: int, test_dep: int, test_status: int, test_kinds: int = -1,
+                        executes_after: bool = False, end_inclusive: int = 1) -> "BatchKeyDeps":
+        """SafeCommandStore.mapReduceFull's key half for a batch of recovery queries against the resident store
+        (acc_cfk_map_reduce_full; local/CommandsForKey.java:553-612): queries = the keydeps_mixed dict without
+        executeAts (msb, lsb, node: each query's testTxnId; key_off, key_code; rng_off, rng_start, rng_end, optional for
+        a batch of key-domain queries only). started_at / test_dep / test_status: the TestStartedAt / TestDep /
+        TestStatus ordinals (L.ACC_STARTED_*, L.ACC_DEP_*, L.ACC_STATUS_*); test_kinds: a mask over Kind ordinals, or -1
+        for testTxnId.kind().witnessedBy(); executes_after: keep only executeAt > testTxnId. Host arrays in, host out:
+        per query the KeyDeps of every visited (key, TxnId) in the keydeps / keydeps_mixed layout, dep_txn = indices
+        into the store's view. The store's segments and missing[] lists are read in place; the store is not modified."""
+        q = queries
+        n = len(q["msb"])
+        a = dict(qm=np.ascontiguousarray(q["msb"], dtype=np.uint64), ql=np.ascontiguousarray(q["lsb"], dtype=np.uint64),
+                 qn=np.ascontiguousarray(q["node"], dtype=np.int32), ko=np.ascontiguousarray(q["key_off"], dtype=np.uint32),
+                 kc=np.ascontiguousarray(q["key_code"], dtype=np.uint64))
+        if q.get("rng_off") is not None:
+            a.update(ro=np.ascontiguousarray(q["rng_off"], dtype=np.uint32), rs=np.ascontiguousarray(q["rng_start"], dtype=np.uint64),
+                     re=np.ascontiguousarray(q["rng_end"], dtype=np.uint64))
+        else:
+            a.update(ro=np.zeros(n + 1, np.uint32), rs=np.zeros(0, np.uint64), re=np.zeros(0, np.uint64))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ri = L.CfkRecoveryIn(n, L.ACC_MEM_HOST, len(a["kc"]), len(a["rs"]), L.TsCols(p("qm"), p("ql"), p("qn")), p("ko"), p("kc"),
+                             p("ro"), p("rs"), p("re"), int(end_inclusive), started_at, test_dep, test_status,
+                             L.ACC_FULL_EXECUTES_AFTER if executes_after else 0, test_kinds)
+        view = L.KeydepsView()
+        self.ctx.check(self.ctx._lib.acc_cfk_map_reduce_full(self.ctx.handle, self._h, C.byref(ri), C.byref(view)))
+        return self.ctx.copy_out(view, None)
+
     def missing_view(self) -> "L.CfkBatchView":
         """The store's txn-major view with each pair's missing[] as txn indices (device), for cfk_map_reduce_full."""
         bv = L.CfkBatchView()
@@ -1303,6 +1331,26 @@ class ReplicaStore:
             out["rangedeps_new"] = self.rcmd.rangedeps(nq)
         elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
+        return out
+
+    def begin_recovery(self, queries: dict) -> dict:
+        """BeginRecovery's four questions about each query's txn (messages/BeginRecovery.java:334, 348, 365, 378),
+        answered from the resident CommandsForKey store (CfkStore.map_reduce_full; queries as there, ranges by the
+        store's bound type): accepted_started_before_without (STARTED_BEFORE, WITHOUT, IS_PROPOSED, keeping only
+        executeAt > the txn: the deps of :334-341) and stable_started_before_with (STARTED_BEFORE, WITH, IS_STABLE) as
+        KeyDeps; has_accepted_started_after_without (STARTED_AFTER, WITHOUT, IS_PROPOSED) and
+        has_stable_executes_after_without (ANY, WITHOUT, IS_STABLE) as one boolean per query. The range-command half
+        of the same questions is Context.map_reduce_full_ranges: the resident range-command store keeps no status,
+        executeAt or deps."""
+        names = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
+                     stable_started_before_with="stableStartedBeforeAndWitnessed",
+                     has_accepted_started_after_without="hasAcceptedOrCommittedStartedAfterWithoutWitnessing",
+                     has_stable_executes_after_without="hasStableExecutesAfterWithoutWitnessing")
+        out = {}
+        for name, scan in names.items():
+            sa, td, ts, after = L.RECOVERY_SCANS[scan]
+            r = self.cfk.map_reduce_full(queries, sa, td, ts, executes_after=after, end_inclusive=self.end_inclusive)
+            out[name] = np.diff(np.asarray(r.u_off).astype(np.int64)) > 0 if name.startswith("has_") else r
         return out
 
     def close(self):

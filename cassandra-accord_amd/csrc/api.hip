@@ -40,6 +40,7 @@ void cfk_missing(acc_cfk *cfk, acc_cfk_batch_view *out);
 void cfk_free(acc_cfk *cfk);
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
 void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *view);
+void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *view);
 acc_cfk *cfk_new(int device);
 acc_rcmd *rcmd_new(int device, uint32_t end_inclusive);
 void rcmd_free(acc_rcmd *store);
@@ -325,6 +326,15 @@ int acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_querie
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_keydeps_mixed(ctx, cfk, q, out_view);
+    });
+}
+
+int acc_cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *out_view)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_map_reduce_full(ctx, cfk, q, out_view);
     });
 }
 

@@ -509,6 +509,8 @@ CfkResident cfk_resident(const acc_cfk *cfk)
     r.em = k.em; r.el = k.el; r.en = k.en;
     r.xm = k.xm; r.xl = k.xl; r.xn = k.xn;
     r.st = k.st;
+    r.miss_off = k.miss_off;
+    r.mm = k.mm; r.ml = k.ml; r.mn = k.mn;
     r.tm = S.tm; r.tl = S.tl; r.tn = S.tn;
     return r;
 }

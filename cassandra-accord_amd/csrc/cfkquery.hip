@@ -42,6 +42,9 @@
 //                  it with an empty prefix and the lane kernels fill the slot after them, so neither the chunk kernels
 //                  nor the offset machinery know about the tier.
 //
+// acc_cfk_map_reduce_full (the last section): BeginRecovery's CommandsForKey.mapReduceFull scans over the same resident
+// segments, behind the same front end and in front of the same builder (build_keydeps).
+//
 // Results live in cq_* buffers only: acc_cfk_apply_deps trades the context's cd_* / cb_* buffers with the store.
 #include "keydeps.hpp"
 #include "cfkquery.hpp"
@@ -55,7 +58,11 @@ constexpr uint32_t CAP_MAX = 1024;    // hits of a query the one-wave build tier
 constexpr uint32_t LANE_SEG_DEFAULT = 16;   // acc_cfk_mixed_queries::lane_seg == 0 (the measured table)
 
 enum : uint64_t { E_KIND_ARG = 1, E_KIND_STATE = 2, E_RANGE = 4, E_OFF = 8, E_KEYS = 16, E_TIE = 32,
-                  E_RKEYS = 64, E_KRANGES = 128, E_ROFF = 256, E_RBOUND = 512, E_RORDER = 1024 };
+                  E_RKEYS = 64, E_KRANGES = 128, E_ROFF = 256, E_RBOUND = 512, E_RORDER = 1024, E_KIND_BY = 2048 };
+
+// which kinds a front end's validation refuses: PreAccept asks Kind.witnesses() of every query, a recovery scan asks
+// Kind.witnessedBy() of its testTxnId only when the caller gave no Kinds mask (k_rc_query, recovery.hip)
+enum : uint32_t { KINDS_WITNESSES = 0, KINDS_WITNESSED_BY = 1, KINDS_UNCHECKED = 2 };
 
 struct Queries {
     const uint64_t *qm, *ql, *xm, *xl;   // TxnId, executeAt (= TxnId columns when the caller gave none)
@@ -506,15 +513,19 @@ __global__ __launch_bounds__(BLOCK) void k_cq_uoff(uint32_t nq, const uint32_t *
 // ---------------------------------------------------------------- acc_cfk_keydeps_mixed: the front end and the lane tier
 
 // Q.off / Q.key: the caller's key_off / key_code
-__global__ __launch_bounds__(BLOCK) void k_cq_rvalidate(Queries Q, Ranges R, uint64_t *__restrict__ errs)
+__global__ __launch_bounds__(BLOCK) void k_cq_rvalidate(Queries Q, Ranges R, uint32_t kinds, uint64_t *__restrict__ errs)
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     if (q >= Q.nq) return;
     uint64_t e = 0;
     const uint64_t l = Q.ql[q];
     const uint32_t kind = (uint32_t)(l >> 1) & 7u;
-    if (kind > ACC_KIND_LOCAL_ONLY) e |= E_KIND_ARG;          // Kind.ofOrdinal
-    else if (witnesses(kind) == 0) e |= E_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+    if (kinds == KINDS_WITNESSES) {
+        if (kind > ACC_KIND_LOCAL_ONLY) e |= E_KIND_ARG;          // Kind.ofOrdinal
+        else if (witnesses(kind) == 0) e |= E_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+    } else if (kinds == KINDS_WITNESSED_BY && witnessed_by(kind) < 0) {
+        e |= kind == ACC_KIND_LOCAL_ONLY ? E_KIND_BY : E_KIND_ARG;   // Kind.witnessedBy(): LocalOnly throws
+    }
     const bool range = l & 1u;
     const uint32_t k0 = Q.off[q], k1 = Q.off[q + 1];
     if (k1 < k0 || k1 > Q.Qp || (q == 0 && k0 != 0) || (q == Q.nq - 1 && k1 != Q.Qp)) e |= E_OFF;
@@ -566,22 +577,16 @@ __global__ __launch_bounds__(BLOCK) void k_cq_roff(uint32_t n, const uint64_t *_
     if (i < n) out[i] = (uint32_t)in[i];
 }
 
-// k_cq_locate over the expanded pairs (Q.off: their offsets): a key-domain pair searches its key; a covered pair finds
-// its range by the per-range offsets and knows its segment; a covered pair with a short segment goes to the lane tier,
-// which finds the prefix itself (lane_w: the segment's length until then). Writes every pair's key code.
-__global__ __launch_bounds__(BLOCK) void k_cq_rexpand(Queries Q, Ranges R, CfkResident s, uint32_t lane_seg, uint64_t *__restrict__ x_key,
-                                                      uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_a,
-                                                      uint32_t *__restrict__ pair_w, uint8_t *__restrict__ pair_t0,
-                                                      uint64_t *__restrict__ chunks, uint8_t *__restrict__ lane,
-                                                      uint32_t *__restrict__ lane_w, uint64_t *__restrict__ nlane)
+// an expanded pair (Q.off: the expanded offsets): its query, its key's code and its segment (s.nk: the key has no CFK).
+// A key-domain pair searches its key; a covered pair finds its range by the per-range offsets (no thread walks a wide
+// range) and knows its segment.
+__device__ __forceinline__ uint32_t pair_segment(const Queries &Q, const Ranges &R, const CfkResident &s, uint32_t i, uint32_t &q,
+                                                 uint64_t &k, bool &range)
 {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= Q.Qp) return;
-    const uint32_t q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
+    q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
     const uint32_t j = i - Q.off[q];
-    uint32_t a = 0, w = 0, t0 = 0, ln = 0, seg = s.nk;
-    uint64_t k;
-    const bool range = Q.ql[q] & 1u;
+    uint32_t seg = s.nk;
+    range = Q.ql[q] & 1u;
     if (range) {
         const uint32_t r0 = R.rng_off[q], r1 = R.rng_off[q + 1];
         const uint64_t at = R.cum[r0] + j;
@@ -594,6 +599,24 @@ __global__ __launch_bounds__(BLOCK) void k_cq_rexpand(Queries Q, Ranges R, CfkRe
         while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
         if (lo < s.nk && s.key[lo] == k) seg = lo;
     }
+    return seg;
+}
+
+// k_cq_locate over the expanded pairs: a key-domain pair is located as there, a covered pair knows its segment; a
+// covered pair with a short segment goes to the lane tier, which finds the prefix itself (lane_w: the segment's length
+// until then). Writes every pair's key code.
+__global__ __launch_bounds__(BLOCK) void k_cq_rexpand(Queries Q, Ranges R, CfkResident s, uint32_t lane_seg, uint64_t *__restrict__ x_key,
+                                                      uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_a,
+                                                      uint32_t *__restrict__ pair_w, uint8_t *__restrict__ pair_t0,
+                                                      uint64_t *__restrict__ chunks, uint8_t *__restrict__ lane,
+                                                      uint32_t *__restrict__ lane_w, uint64_t *__restrict__ nlane)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q.Qp) return;
+    uint32_t q, a = 0, w = 0, t0 = 0, ln = 0;
+    uint64_t k;
+    bool range;
+    const uint32_t seg = pair_segment(Q, R, s, i, q, k, range);
     if (seg < s.nk) {
         const uint32_t s0 = s.ent_off[seg], s1 = s.ent_off[seg + 1];
         a = s0;
@@ -686,6 +709,7 @@ static void check_cq_errors(uint64_t e)
     if (e & E_RBOUND) fail(ACC_E_ARG, "a range needs start < end");
     if (e & E_RORDER) fail(ACC_E_ARG, "ranges of a query must be sorted and must not overlap (Ranges.ofSortedAndDeoverlapped)");
     if (e & E_KIND_STATE) fail(ACC_E_STATE, "Kind.witnesses(): unhandled kind LocalOnly (AssertionError)");
+    if (e & E_KIND_BY) fail(ACC_E_STATE, "Kind.witnessedBy(): unhandled kind LocalOnly (AssertionError)");
     if (e & E_TIE)
         fail(ACC_E_STATE, "two or more committed entries of one key execute at a query's executeAt: the FAST bisection "
                           "of committed[] is not determined");
@@ -754,6 +778,74 @@ static void stage_ids(acc_ctx *ctx, Queries &Q, const acc_ts_cols &txn_id, const
 
 static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view);
 
+// the caller's participants of a call over both domains (acc_cfk_mixed_queries, acc_cfk_recovery_in)
+struct Parts {
+    const uint32_t *key_off;
+    const uint64_t *key_code;
+    const uint32_t *rng_off;
+    const uint64_t *rng_start, *rng_end;
+    uint32_t n_pairs, n_ranges, end_inclusive, mem;
+};
+
+// The front end both entries over both domains share (r1, r2 above): stages the participants, validates (kinds by the
+// entry's rule; nothing after it indexes by an offset or trusts key or range order before it has passed), finds the
+// store keys every range covers and the expanded pair offsets. Q (nq and the ids staged) leaves as the queries over the
+// expanded pairs: off their offsets, Qp their number, key = xkey, which the entry's expand kernel fills (pair_segment).
+// Returns the covered (range query, key) pairs.
+static uint64_t expand_queries(acc_ctx *ctx, const CfkResident &s, Queries &Q, Ranges &R, const Parts &in, uint32_t kinds,
+                               uint64_t *errs, uint64_t *&xkey)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = Q.nq, NR = in.n_ranges, mem = in.mem;
+    Q.Qp = in.n_pairs;       // over the caller's keys until the expansion
+    Q.off = stage_in(ctx, "cq_in_off", in.key_off, (size_t)nq + 1, mem);
+    Q.key = stage_in(ctx, "cq_in_key", in.key_code, in.n_pairs, mem);
+    R.key_off = Q.off;
+    R.key_code = Q.key;
+    R.rng_off = stage_in(ctx, "cq_in_roff", in.rng_off, (size_t)nq + 1, mem);
+    R.start = stage_in(ctx, "cq_in_rs", in.rng_start, NR, mem);
+    R.end = stage_in(ctx, "cq_in_re", in.rng_end, NR, mem);
+    R.nr = NR;
+    R.end_inclusive = in.end_inclusive;
+
+    // ---- validate
+    ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
+    launch(ctx, "cq_rvalidate", k_cq_rvalidate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, kinds, errs);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    check_cq_errors(ctx->pinned[0]);
+
+    // ---- bounds: the store keys every range covers, the expanded pair offsets
+    uint32_t *rlo = ctx->get<uint32_t>("cq_rlo", NR);
+    uint64_t *rcnt = ctx->get<uint64_t>("cq_rcnt", NR);
+    uint64_t *rcum = ctx->get<uint64_t>("cq_rcum", (size_t)NR + 1);
+    if (NR) {
+        launch(ctx, "cq_rbounds", k_cq_rbounds, dim3(grid_for(NR, BLOCK)), dim3(BLOCK), 0, R, s, rlo, rcnt);
+        scan<uint64_t, OpAdd<uint64_t>>(ctx, rcnt, rcum, NR, true, rcum + NR);
+    } else {
+        ACC_HIP(hipMemsetAsync(rcum, 0, 8, st));
+    }
+    R.lo = rlo;
+    R.cum = rcum;
+    uint64_t *qcnt = ctx->get<uint64_t>("cq_qcnt", nq);
+    uint64_t *xoff64 = ctx->get<uint64_t>("cq_xoff64", (size_t)nq + 1);
+    launch(ctx, "cq_rcount", k_cq_rcount, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, qcnt);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, qcnt, xoff64, nq, true, xoff64 + nq);
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, xoff64 + nq, 8, hipMemcpyDeviceToHost, st));
+    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, rcum + NR, 8, hipMemcpyDeviceToHost, st));
+    ctx->sync();
+    const uint64_t X = ctx->pinned[0], covered = ctx->pinned[1];
+    if (X >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs after expanding the ranges (>= 2^32 - 1)");
+    const uint32_t Xp = (uint32_t)X;
+    uint32_t *xoff = ctx->get<uint32_t>("cq_xoff", (size_t)nq + 1);
+    xkey = ctx->get<uint64_t>("cq_xkey", Xp);
+    launch(ctx, "cq_roff", k_cq_roff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq + 1, (const uint64_t *)xoff64, xoff);
+    Q.off = xoff;
+    Q.key = xkey;
+    Q.Qp = Xp;
+    return covered;
+}
+
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keydeps_view *view)
 {
     if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
@@ -810,61 +902,19 @@ void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *
         return;
     }
 
-    Queries Q{};       // over the caller's keys until the expansion
+    Queries Q{};
     Q.nq = nq;
-    Q.Qp = Kp;
-    Q.off = stage_in(ctx, "cq_in_off", in->key_off, (size_t)nq + 1, mem);
-    Q.key = stage_in(ctx, "cq_in_key", in->key_code, Kp, mem);
     stage_ids(ctx, Q, in->txn_id, in->execute_at, nq, mem);
     Ranges R{};
-    R.key_off = Q.off;
-    R.key_code = Q.key;
-    R.rng_off = stage_in(ctx, "cq_in_roff", in->rng_off, (size_t)nq + 1, mem);
-    R.start = stage_in(ctx, "cq_in_rs", in->rng_start, NR, mem);
-    R.end = stage_in(ctx, "cq_in_re", in->rng_end, NR, mem);
-    R.nr = NR;
-    R.end_inclusive = in->end_inclusive;
-
-    // ---- validate: nothing below indexes by an offset or trusts key or range order before this has passed
     uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
-    ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
-    launch(ctx, "cq_rvalidate", k_cq_rvalidate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, errs);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_cq_errors(ctx->pinned[0]);
-
-    // ---- bounds: the store keys every range covers, the expanded pair offsets
-    uint32_t *rlo = ctx->get<uint32_t>("cq_rlo", NR);
-    uint64_t *rcnt = ctx->get<uint64_t>("cq_rcnt", NR);
-    uint64_t *rcum = ctx->get<uint64_t>("cq_rcum", (size_t)NR + 1);
-    if (NR) {
-        launch(ctx, "cq_rbounds", k_cq_rbounds, dim3(grid_for(NR, BLOCK)), dim3(BLOCK), 0, R, s, rlo, rcnt);
-        scan<uint64_t, OpAdd<uint64_t>>(ctx, rcnt, rcum, NR, true, rcum + NR);
-    } else {
-        ACC_HIP(hipMemsetAsync(rcum, 0, 8, st));
-    }
-    R.lo = rlo;
-    R.cum = rcum;
-    uint64_t *qcnt = ctx->get<uint64_t>("cq_qcnt", nq);
-    uint64_t *xoff64 = ctx->get<uint64_t>("cq_xoff64", (size_t)nq + 1);
-    launch(ctx, "cq_rcount", k_cq_rcount, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, qcnt);
-    scan<uint64_t, OpAdd<uint64_t>>(ctx, qcnt, xoff64, nq, true, xoff64 + nq);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, xoff64 + nq, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, rcum + NR, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t X = ctx->pinned[0], covered = ctx->pinned[1];
-    if (X >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs after expanding the ranges (>= 2^32 - 1)");
-    const uint32_t Xp = (uint32_t)X;
+    uint64_t *xkey = nullptr;
+    const uint64_t covered = expand_queries(ctx, s, Q, R, Parts{ in->key_off, in->key_code, in->rng_off, in->rng_start, in->rng_end, Kp, NR,
+                                                                  in->end_inclusive, mem }, KINDS_WITNESSES, errs, xkey);
+    const uint32_t Xp = Q.Qp;
 
     // ---- expand: every pair's query, key and segment; the lane tier's pairs
-    uint32_t *xoff = ctx->get<uint32_t>("cq_xoff", (size_t)nq + 1);
-    uint64_t *xkey = ctx->get<uint64_t>("cq_xkey", Xp);
     uint64_t *nlane = ctx->get<uint64_t>("cq_nlane", 1);
-    launch(ctx, "cq_roff", k_cq_roff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq + 1, (const uint64_t *)xoff64, xoff);
     ACC_HIP(hipMemsetAsync(nlane, 0, 8, st));
-    Q.off = xoff;
-    Q.key = xkey;
-    Q.Qp = Xp;
     const Located L = located_bufs(ctx, Xp, lane_seg != 0);   // ACC_CFQ_LANE_NONE: every pair takes the chunk path
     if (Xp)
         launch(ctx, "cq_rexpand", k_cq_rexpand, dim3(grid_for(Xp, BLOCK)), dim3(BLOCK), 0, Q, R, s, lane_seg, xkey, L.pair_q, L.pair_a,
@@ -875,51 +925,56 @@ void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *
     ctx->stat("cfq.lane_pairs", ctx->pinned[8]);
 }
 
-// From the located pairs on: chunk offsets, M and the tie count, the count pass, every offset, emit, KeyDeps.Builder
-static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
+// The pairs' chunk offsets, the chunk total (the one host read) and the chunk -> pair map
+static uint64_t chunk_layout(acc_ctx *ctx, uint32_t Qp, const uint64_t *chunks, uint64_t *&chunk_off, uint32_t *&chunk_item)
 {
     hipStream_t st = ctx->stream;
-    const uint64_t wl0 = ctx->wave_launches;
-    const uint32_t nq = Q.nq, Qp = Q.Qp;
-    uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
-    cap = std::min(cap, CAP_MAX);
-    uint32_t *const pair_q = L.pair_q, *const pair_a = L.pair_a, *const pair_w = L.pair_w;
-    uint8_t *const pair_t0 = L.pair_t0;
-    uint64_t *const chunks = L.chunks;
-    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", (size_t)nq + 1);
-    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", (size_t)nq + 1);
-    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", (size_t)nq + 1);
-    uint64_t *chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
+    chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
     if (Qp) scan<uint64_t, OpAdd<uint64_t>>(ctx, chunks, chunk_off, Qp, true, chunk_off + Qp);
     else ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
     ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_off + Qp, 8, hipMemcpyDeviceToHost, st));
     ctx->sync();
     const uint64_t NC = ctx->pinned[0];
     if (NC >= (1ull << 33)) fail(ACC_E_CAP, "the queries read too many segment entries in one call (>= 2^41)");
-    uint32_t *chunk_item = ctx->get<uint32_t>("cq_chunk_item", NC);
-    const Pairs P{ pair_q, pair_a, pair_w, chunk_off, chunk_item, Qp };
-    const Lanes lanes{ L.lane, L.lane_w };
+    chunk_item = ctx->get<uint32_t>("cq_chunk_item", NC);
+    if (NC) launch(ctx, "cq_items", k_cq_items, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off, chunk_item);
+    return NC;
+}
 
-    // ---- M and the tie count, the count pass, every offset
-    Part part{ ctx->get<uint64_t>("cq_part_m", NC), ctx->get<uint64_t>("cq_part_l", NC), ctx->get<int32_t>("cq_part_n", NC),
-               ctx->get<uint32_t>("cq_part_f", NC) };
-    uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
+// what build_keydeps hands the entry's emit pass, and what it reports back for the entry's stats
+struct EmitArgs {
+    const uint64_t *chunk_eoff, *epos, *gcnt, *goff;
+    int tb;
+    uint32_t *hit;
+    uint64_t *gkey;
+};
+
+struct Built {
+    uint64_t hits, sorted_hits;
+};
+
+// KeyDeps.Builder per query from the per-chunk counts of emitted entries (chunk_cnt, NC of them; the pairs' chunks at
+// chunk_off): every offset, then emit(EmitArgs) writes each emitted entry's view index into its hit slot (and its
+// (query, index) key when the query sorts), then the header, the one-wave tier up to cfq_wave_cap hits, the radix-sort
+// tier beyond it, the unique scan, dep_txn, u_off and the view. Both scans of the resident store end here.
+template <class Emit>
+static Built build_keydeps(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const uint32_t *pair_q, const uint64_t *chunk_off,
+                           const uint64_t *chunk_cnt, uint64_t NC, uint64_t *errs, acc_keydeps_view *view, Emit emit)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = Q.nq, Qp = Q.Qp;
+    uint32_t cap = ctx->opts.cfq_wave_cap ? ctx->opts.cfq_wave_cap : CAP_MAX;
+    cap = std::min(cap, CAP_MAX);
+    uint64_t *arena_off = ctx->get<uint64_t>("cq_arena_off", (size_t)nq + 1);
+    uint64_t *kd_off = ctx->get<uint64_t>("cq_kd_off", (size_t)nq + 1);
+    uint64_t *u_off = ctx->get<uint64_t>("cq_u_off", (size_t)nq + 1);
     uint64_t *chunk_eoff = ctx->get<uint64_t>("cq_chunk_eoff", NC + 1);
-    if (NC) {
-        launch(ctx, "cq_items", k_cq_items, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off, chunk_item);
-        launch_waves(ctx, "cq_max", k_cq_max, NC, NC, Q, s, P, (const uint8_t *)pair_t0, part, chunk_cnt, errs);
-        launch_waves(ctx, "cq_fold", k_cq_fold, Qp, P, part, errs);
-        launch_waves(ctx, "cq_count", k_cq_count, NC, NC, Q, s, P, part, chunk_cnt);
-        if (L.lane)
-            launch(ctx, "cq_lane_max", k_cq_lane_max, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part, chunk_cnt, errs);
-        scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt, chunk_eoff, NC, true, chunk_eoff + NC);
-    } else {
-        ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
-    }
+    if (NC) scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt, chunk_eoff, NC, true, chunk_eoff + NC);
+    else ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
     uint64_t *epos = ctx->get<uint64_t>("cq_epos", (size_t)Qp + 1);
     uint64_t *kept = ctx->get<uint64_t>("cq_kept", Qp);
     uint64_t *kpos = ctx->get<uint64_t>("cq_kpos", (size_t)Qp + 1);
-    launch(ctx, "cq_epos", k_cq_epos, dim3(grid_for((size_t)Qp + 1, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off,
+    launch(ctx, "cq_epos", k_cq_epos, dim3(grid_for((size_t)Qp + 1, BLOCK)), dim3(BLOCK), 0, Qp, chunk_off,
            (const uint64_t *)chunk_eoff, epos, kept);
     if (Qp) scan<uint64_t, OpAdd<uint64_t>>(ctx, kept, kpos, Qp, true, kpos + Qp);
     else ACC_HIP(hipMemsetAsync(kpos, 0, 8, st));
@@ -942,12 +997,7 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
     const int qbits = bits_for(nq - 1);
     uint32_t *hit = ctx->get<uint32_t>("cq_hit", E);
     uint64_t *gkey = ctx->get<uint64_t>("cq_gkey", G);
-    if (E)
-        launch_waves(ctx, "cq_emit", k_cq_emit, NC, NC, Q, s, P, part, (const uint64_t *)chunk_eoff,
-               (const uint64_t *)epos, (const uint64_t *)gcnt, (const uint64_t *)goff, tb, hit, gkey);
-    if (E && L.lane)
-        launch(ctx, "cq_lane_emit", k_cq_lane_emit, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part,
-               (const uint64_t *)chunk_eoff, (const uint64_t *)epos, (const uint64_t *)gcnt, (const uint64_t *)goff, tb, hit, gkey);
+    if (E) emit(EmitArgs{ chunk_eoff, epos, gcnt, goff, tb, hit, gkey });
 
     // ---- KeyDeps.Builder layout
     int32_t *arena = ctx->get<int32_t>("cq_arena", TK + E);
@@ -956,7 +1006,7 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
     uint32_t *dep_txn = ctx->get<uint32_t>("cq_dep_txn", E);
     uint64_t TU = 0;
     if (E) {
-        launch(ctx, "cq_header", k_cq_header, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, (const uint32_t *)pair_q,
+        launch(ctx, "cq_header", k_cq_header, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, pair_q,
                (const uint64_t *)kpos, (const uint64_t *)epos, (const uint64_t *)arena_off, arena, key_idx, kd_key);
         uint32_t *uflag = ctx->get<uint32_t>("cq_uflag", E);
         uint32_t *uval = ctx->get<uint32_t>("cq_uval", E);
@@ -987,14 +1037,252 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
         ctx->sync();
     }
-    ctx->stat("cfq.pairs", Qp);
-    ctx->stat("cfq.chunks", NC);
-    ctx->stat("cfq.hits", E);
-    ctx->stat("cfq.sorted_hits", G);
-    ctx->stat("cfq.wave_launches", ctx->wave_launches - wl0);
     *view = acc_keydeps_view{ nq, TK + E, TK, TU, E, arena_off, arena, kd_off, key_idx, u_off, dep_txn, kd_key };
     ctx->kd_view = *view;
     ctx->kd_valid = true;
+    return Built{ E, G };
+}
+
+// From the located pairs on: chunk offsets, M and the tie count, the count pass, then emit and KeyDeps.Builder
+static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
+{
+    const uint64_t wl0 = ctx->wave_launches;
+    const uint32_t Qp = Q.Qp;
+    uint64_t *chunk_off = nullptr;
+    uint32_t *chunk_item = nullptr;
+    const uint64_t NC = chunk_layout(ctx, Qp, L.chunks, chunk_off, chunk_item);
+    const Pairs P{ L.pair_q, L.pair_a, L.pair_w, chunk_off, chunk_item, Qp };
+    const Lanes lanes{ L.lane, L.lane_w };
+
+    // ---- M and the tie count, the count pass
+    Part part{ ctx->get<uint64_t>("cq_part_m", NC), ctx->get<uint64_t>("cq_part_l", NC), ctx->get<int32_t>("cq_part_n", NC),
+               ctx->get<uint32_t>("cq_part_f", NC) };
+    uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
+    if (NC) {
+        launch_waves(ctx, "cq_max", k_cq_max, NC, NC, Q, s, P, (const uint8_t *)L.pair_t0, part, chunk_cnt, errs);
+        launch_waves(ctx, "cq_fold", k_cq_fold, Qp, P, part, errs);
+        launch_waves(ctx, "cq_count", k_cq_count, NC, NC, Q, s, P, part, chunk_cnt);
+        if (L.lane)
+            launch(ctx, "cq_lane_max", k_cq_lane_max, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part, chunk_cnt, errs);
+    }
+    const Built b = build_keydeps(ctx, s, Q, L.pair_q, chunk_off, chunk_cnt, NC, errs, view, [&](const EmitArgs &e) {
+        launch_waves(ctx, "cq_emit", k_cq_emit, NC, NC, Q, s, P, part, e.chunk_eoff, e.epos, e.gcnt, e.goff, e.tb, e.hit, e.gkey);
+        if (L.lane)
+            launch(ctx, "cq_lane_emit", k_cq_lane_emit, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, s, P, lanes, part, e.chunk_eoff,
+                   e.epos, e.gcnt, e.goff, e.tb, e.hit, e.gkey);
+    });
+    ctx->stat("cfq.pairs", Qp);
+    ctx->stat("cfq.chunks", NC);
+    ctx->stat("cfq.hits", b.hits);
+    ctx->stat("cfq.sorted_hits", b.sorted_hits);
+    ctx->stat("cfq.wave_launches", ctx->wave_launches - wl0);
+}
+
+// ================================================================ acc_cfk_map_reduce_full: the recovery scans
+// CommandsForKey.mapReduceFull (local/CommandsForKey.java:553-612) for a batch of BeginRecovery queries
+// (messages/BeginRecovery.java:330-380) on the resident segments, the recovery counterpart of the scan above. The
+// front end is acc_cfk_keydeps_mixed's (rvalidate, rbounds, rcount, pair_segment); the rest:
+//   window   per pair: pos = the lower bound of X = testTxnId among the segment's TxnIds, isKnown = the entry there
+//            compares equal to X; the window TestStartedAt admits ([start, pos), [pos, end) or the segment; nothing for
+//            WITH when X is no member), its 256-entry chunks. Every pair takes the chunk path.
+//   count    one wave per chunk, four entries per lane: the per-entry tests, cheapest first (kind, status, hasInfo,
+//            executeAt > X), and only for WITH / WITHOUT entries that passed them the binary search of X in the
+//            entry's missing[] (raw TxnIds, read in place; divergent per lane by nature)
+//   emit     the same walk, compacting in position order; each entry as its store-view index (view_index)
+//   build    build_keydeps. No M pass and no tie rule.
+
+namespace cr {
+
+struct Params {
+    uint32_t started_at, test_dep, test_status, exec_after;
+    int32_t test_kinds;
+};
+
+__global__ __launch_bounds__(BLOCK) void k_cr_window(Queries Q, Ranges R, CfkResident s, Params p, uint64_t *__restrict__ x_key,
+                                                     uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_a,
+                                                     uint32_t *__restrict__ pair_w, uint64_t *__restrict__ chunks)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= Q.Qp) return;
+    uint32_t q, a = 0, w = 0;
+    uint64_t k;
+    bool range;
+    const uint32_t seg = pair_segment(Q, R, s, i, q, k, range);
+    if (seg < s.nk) {
+        const uint32_t s0 = s.ent_off[seg], s1 = s.ent_off[seg + 1];
+        const uint64_t Xm = Q.qm[q], Xl = Q.ql[q];
+        const int32_t Xn = Q.qn[q];
+        // Arrays.binarySearch(txns, testTxnId): found <=> X is a member; pos = its index or the insert point
+        uint32_t x = s0, y = s1;
+        while (x < y) {
+            const uint32_t m = (x + y) >> 1;
+            if (ts_cmp(s.em[m], s.el[m], s.en[m], Xm, Xl, Xn) < 0) x = m + 1; else y = m;
+        }
+        const bool known = x < s1 && ts_cmp(s.em[x], s.el[x], s.en[x], Xm, Xl, Xn) == 0;
+        if (known || p.test_dep != ACC_DEP_WITH) {
+            const uint32_t start = p.started_at == ACC_STARTED_AFTER ? x : s0;
+            const uint32_t end = p.started_at == ACC_STARTED_BEFORE ? x : s1;
+            a = start;
+            w = end - start;
+        }
+    }
+    x_key[i] = k;
+    pair_q[i] = q;
+    pair_a[i] = a;
+    pair_w[i] = w;
+    chunks[i] = (w + CH - 1) / CH;
+}
+
+struct Scan {
+    uint32_t base, end, q, mask;
+    uint64_t Xm, Xl;
+    int32_t Xn;
+};
+
+__device__ __forceinline__ Scan scan_ctx(uint64_t cw, const Queries &Q, const Pairs &P, const Params &p)
+{
+    Scan c;
+    const uint32_t item = P.item[cw];
+    c.q = P.q[item];
+    c.base = P.a[item] + (uint32_t)(cw - P.chunk_off[item]) * CH;
+    c.end = P.a[item] + P.w[item];
+    c.Xm = Q.qm[c.q]; c.Xl = Q.ql[c.q]; c.Xn = Q.qn[c.q];
+    const int by = p.test_kinds < 0 ? witnessed_by((uint32_t)(c.Xl >> 1) & 7u) : p.test_kinds;   // validated: >= 0
+    c.mask = (uint32_t)by;
+    return c;
+}
+
+// the per-entry tests of CommandsForKey.mapReduceFull (:577-607) plus the optional executeAt > testTxnId map filter
+__device__ __forceinline__ bool visited(const CfkResident &s, const Params &p, const Scan &c, uint32_t e)
+{
+    // the status byte first: it alone refuses most entries of a steady-state segment, whose TxnId word is then not read
+    const uint32_t st = s.st[e];
+    switch (p.test_status) {
+    case ACC_STATUS_IS_PROPOSED: if (st != ACC_ST_ACCEPTED && st != ACC_ST_COMMITTED) return false; break;
+    case ACC_STATUS_IS_STABLE:   if (st < ACC_ST_STABLE || st >= ACC_ST_INVALID_OR_TRUNCATED) return false; break;
+    default:                     if (st == ACC_ST_TRANSITIVELY_KNOWN) return false; break;
+    }
+    const bool dep = p.test_dep != ACC_DEP_ANY;
+    if (dep && (st < ACC_ST_ACCEPTED || st > ACC_ST_APPLIED)) return false;   // !InternalStatus.hasInfo
+    if (!((c.mask >> ((uint32_t)(s.el[e] >> 1) & 7u)) & 1u)) return false;
+    if ((dep || p.exec_after) && ts_cmp(s.xm[e], s.xl[e], s.xn[e], c.Xm, c.Xl, c.Xn) <= 0) return false;
+    if (dep) {
+        uint32_t lo = s.miss_off[e], hi = s.miss_off[e + 1];
+        bool in_missing = false;
+        while (lo < hi) {
+            const uint32_t m = (lo + hi) >> 1;
+            const int d = ts_cmp(s.mm[m], s.ml[m], s.mn[m], c.Xm, c.Xl, c.Xn);
+            if (d < 0) lo = m + 1; else if (d > 0) hi = m; else { in_missing = true; break; }
+        }
+        if (in_missing == (p.test_dep == ACC_DEP_WITH)) return false;        // hasAsDep != (testDep == WITH)
+    }
+    return true;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cr_count(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Params p,
+                                                    uint64_t *__restrict__ chunk_cnt)
+{
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (cw >= nchunks) return;
+    const Scan c = scan_ctx(cw, Q, P, p);
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t u = 0; u < CH / 64; ++u) {
+        const uint32_t e = c.base + u * 64 + lane_id();
+        cnt += (uint32_t)__popcll(__ballot(e < c.end && visited(s, p, c, e)));
+    }
+    if (lane_id() == 0) chunk_cnt[cw] = cnt;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_cr_emit(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Params p,
+                                                   const uint64_t *__restrict__ chunk_eoff, const uint64_t *__restrict__ epos,
+                                                   const uint64_t *__restrict__ gcnt, const uint64_t *__restrict__ goff, int tb,
+                                                   uint32_t *__restrict__ hit, uint64_t *__restrict__ gkey)
+{
+    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (cw >= nchunks) return;
+    const Scan c = scan_ctx(cw, Q, P, p);
+    const uint64_t lt = (1ull << lane_id()) - 1;
+    uint64_t out = chunk_eoff[cw];
+    if (chunk_eoff[cw + 1] == out) return;
+    const bool big = gcnt[c.q] != 0;
+    const uint64_t gbase = big ? goff[c.q] - epos[Q.off[c.q]] : 0;   // hit slot -> slot among the sorting tier's hits
+#pragma unroll
+    for (uint32_t u = 0; u < CH / 64; ++u) {
+        const uint32_t e = c.base + u * 64 + lane_id();
+        const bool m = e < c.end && visited(s, p, c, e);
+        const uint64_t bal = __ballot(m);
+        if (m) {
+            const uint32_t lo = view_index(s, e);
+            const uint64_t o = out + (uint64_t)__popcll(bal & lt);
+            hit[o] = lo;
+            if (big) gkey[gbase + o] = ((uint64_t)c.q << tb) | lo;
+        }
+        out += (uint64_t)__popcll(bal);
+    }
+}
+
+}  // namespace cr
+
+void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *in, acc_keydeps_view *view)
+{
+    if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
+    const CfkResident s = resident_checked(cfk, in->mem);
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
+    if (in->started_at > 2 || in->test_dep > 2 || in->test_status > 2)
+        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
+    if (in->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
+    if (in->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
+    if (in->n_pairs >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs in one call (>= 2^32 - 1)");
+    if (in->n_ranges >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many ranges in one call (>= 2^32 - 1)");
+    const uint64_t wl0 = ctx->wave_launches;
+    ctx->kd_valid = false;
+    const uint32_t nq = in->n_query, mem = in->mem;
+    if (nq == 0) {
+        if (in->n_pairs) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+        if (in->n_ranges) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+        empty_result(ctx, view);
+        return;
+    }
+    const cr::Params prm{ in->started_at, in->test_dep, in->test_status, (uint32_t)(in->flags & ACC_FULL_EXECUTES_AFTER),
+                          in->test_kinds < 0 ? -1 : in->test_kinds };
+
+    Queries Q{};
+    Q.nq = nq;
+    stage_ids(ctx, Q, in->test_txn, acc_ts_cols{ nullptr, nullptr, nullptr }, nq, mem);
+    Ranges R{};
+    uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
+    uint64_t *xkey = nullptr;
+    const uint64_t covered = expand_queries(ctx, s, Q, R, Parts{ in->key_off, in->key_code, in->rng_off, in->rng_start, in->rng_end,
+                                                                  (uint32_t)in->n_pairs, (uint32_t)in->n_ranges, in->end_inclusive, mem },
+                                            prm.test_kinds < 0 ? KINDS_WITNESSED_BY : KINDS_UNCHECKED, errs, xkey);
+    const uint32_t Qp = Q.Qp;
+
+    // ---- window: pos, isKnown, the entries TestStartedAt admits, their chunks
+    uint32_t *pair_q = ctx->get<uint32_t>("cq_pair_q", Qp), *pair_a = ctx->get<uint32_t>("cq_pair_a", Qp);
+    uint32_t *pair_w = ctx->get<uint32_t>("cq_pair_w", Qp);
+    uint64_t *chunks = ctx->get<uint64_t>("cq_chunks", Qp);
+    if (Qp)
+        launch(ctx, "cr_window", cr::k_cr_window, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Q, R, s, prm, xkey, pair_q, pair_a, pair_w,
+               chunks);
+    uint64_t *chunk_off = nullptr;
+    uint32_t *chunk_item = nullptr;
+    const uint64_t NC = chunk_layout(ctx, Qp, chunks, chunk_off, chunk_item);
+    const Pairs P{ pair_q, pair_a, pair_w, chunk_off, chunk_item, Qp };
+
+    // ---- count, then emit and KeyDeps.Builder
+    uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
+    if (NC) launch_waves(ctx, "cr_count", cr::k_cr_count, NC, NC, Q, s, P, prm, chunk_cnt);
+    const Built b = build_keydeps(ctx, s, Q, pair_q, chunk_off, chunk_cnt, NC, errs, view, [&](const EmitArgs &e) {
+        launch_waves(ctx, "cr_emit", cr::k_cr_emit, NC, NC, Q, s, P, prm, e.chunk_eoff, e.epos, e.gcnt, e.goff, e.tb, e.hit, e.gkey);
+    });
+    ctx->stat("cfr.pairs", Qp);
+    ctx->stat("cfr.chunks", NC);
+    ctx->stat("cfr.hits", b.hits);
+    ctx->stat("cfr.sorted_hits", b.sorted_hits);
+    ctx->stat("cfr.range_pairs", covered);
+    ctx->stat("cfr.wave_launches", ctx->wave_launches - wl0);
 }
 
 }  // namespace acc
+

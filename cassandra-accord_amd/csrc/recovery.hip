@@ -32,19 +32,6 @@ struct RcParams {
     uint32_t started_at, test_dep, test_status, exec_after;
 };
 
-// Kind.witnessedBy() (primitives/Txn.java:247-262) as a mask over Kind ordinals: EphemeralRead -> Nothing,
-// Read -> WsOrSyncPoints, Write -> AnyGloballyVisible, SyncPoint / ExclusiveSyncPoint -> ExclusiveSyncPoints
-__device__ __forceinline__ int witnessed_by(uint32_t kind)
-{
-    switch (kind) {
-    case 2:         return 0;
-    case 0:         return (1 << 1) | (1 << 3) | (1 << 4);
-    case 1:         return (1 << 0) | (1 << 1) | (1 << 3) | (1 << 4);
-    case 3: case 4: return 1 << 4;
-    default:        return -1;
-    }
-}
-
 template <class T>
 __device__ __forceinline__ uint32_t rc_lower(const T *a, uint32_t lo, uint32_t hi, T v)
 {

@@ -37,6 +37,20 @@ __device__ __forceinline__ uint32_t witnesses(uint32_t kind)
     }
 }
 
+// Kind.witnessedBy() (primitives/Txn.java:247-262) as a mask over Kind ordinals: EphemeralRead -> Nothing,
+// Read -> WsOrSyncPoints, Write -> AnyGloballyVisible, SyncPoint / ExclusiveSyncPoint -> ExclusiveSyncPoints;
+// -1 = throws (LocalOnly) or no such ordinal. The recovery scans' default Kinds (recovery.hip, cfkquery.hip).
+__device__ __forceinline__ int witnessed_by(uint32_t kind)
+{
+    switch (kind) {
+    case 2:         return 0;
+    case 0:         return (1 << 1) | (1 << 3) | (1 << 4);
+    case 1:         return (1 << 0) | (1 << 1) | (1 << 3) | (1 << 4);
+    case 3: case 4: return 1 << 4;
+    default:        return -1;
+    }
+}
+
 // Kind class for the Kinds predicates (Txn.java:140-152): Read 0, Write 1, SyncPoint/ExclusiveSyncPoint 2;
 // EphemeralRead and LocalOnly are witnessed by no predicate (3 = none).
 __device__ __forceinline__ uint32_t kind_class(uint32_t kind)

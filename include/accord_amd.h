@@ -41,6 +41,8 @@
  *   acc_deps_to_json       (the in-tree Deps wire format) parsed / written on device, with the KeyDeps / RangeDeps Builder.
  *   acc_cfk_*              CommandsForKey.update for batches of commands   local/CommandsForKey.java:652-706
  *                          against a CFK store kept in HBM (SafeCommandStore.updateCommandsForKey :217-240).
+ *   acc_cfk_map_reduce_full  the same recovery scans (BeginRecovery.java:330-380 -> CommandsForKey.mapReduceFull
+ *                          local/CommandsForKey.java:553-612) read from the resident CFK store's segments in place.
  *   acc_rcmd_*             the rangeCommands map of a CommandStore kept in HBM: InMemorySafeStore.update
  *                          impl/InMemoryCommandStore.java:739-762 (RangeCommand.update = ranges.with(add), :524-539) for
  *                          batches of commands, and the range-command half of mapReduceActive (:863-870, :883-960) for
@@ -965,6 +967,52 @@ typedef struct acc_cfk_mixed_queries {
     uint32_t    lane_seg;              /* see above; 0: the library default */
 } acc_cfk_mixed_queries;
 int  acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *out_view);
+
+/* The recovery scans on the resident store: acc_map_reduce_full's questions (BeginRecovery's four,
+ * messages/BeginRecovery.java:330-380 -> SafeCommandStore.mapReduceFull -> CommandsForKey.mapReduceFull,
+ * local/CommandsForKey.java:553-612) asked of the live CommandsForKey of the recovered txn's keys and of nothing else,
+ * as the reference does: the key-major segments and each entry's missing[] (raw TxnIds, sorted) are read in place; the
+ * store is not re-ranked, re-sorted or rebuilt, and the per-pair missing[] indices of acc_cfk_missing are not read.
+ * Per (query, key) pair over the key's segment, with X = test_txn[q] and every comparison Timestamp.compareTo:
+ * pos = the lower bound of X among the segment's TxnIds (Arrays.binarySearch's index or insert point, :561-562),
+ * isKnown = the entry at pos compares equal to X; a pair with !isKnown and test_dep = WITH contributes nothing (:563-564).
+ * The window is [segment start, pos) for STARTED_BEFORE, [pos, segment end) for STARTED_AFTER (X's own entry included
+ * when it is a member) and the whole segment for ANY (:566-575). An entry of the window is visited iff its kind
+ * ((lsb >> 1) & 7) is in the Kinds mask (:580), it passes the status test (:581-596: IS_PROPOSED = ACCEPTED or
+ * COMMITTED; IS_STABLE = STABLE <= s < INVALID_OR_TRUNCATED; ANY_STATUS = not TRANSITIVELY_KNOWN), for WITH / WITHOUT
+ * its status hasInfo (ACCEPTED..APPLIED), its executeAt > X and (X is absent from its missing[]) == (test_dep == WITH)
+ * (:597-605; a binary search of X in the entry's missing[]), and with ACC_FULL_EXECUTES_AFTER its executeAt > X
+ * (BeginRecovery.java:339-341).
+ * A key-domain query (TxnId domain bit 0) lists keys; a key without a CFK contributes nothing. A range-domain query
+ * (domain bit 1) lists ranges and runs the same scan on every store key each range covers, bounds by end_inclusive,
+ * range by range: mapReduceForKey's Range case (impl/InMemoryCommandStore.java:274-289), which mapReduceFull (:874-881)
+ * uses exactly as mapReduceActive does. There is no special case for it: a range-domain X is a member of a key only if
+ * a stored TxnId compares equal to it.
+ * Result per query: the Deps.Builder KeyDeps of every visited (key, TxnId) in the acc_keydeps_view layout of
+ * acc_cfk_keydeps / acc_cfk_keydeps_mixed: key_idx into the query's own keys (its covered keys in range order for a
+ * range-domain query), kd_key their codes, dep_txn = indices into the store's acc_cfk_view txn order, ascending. It is
+ * the context's last KeyDeps result (acc_keydeps_copy_out copies it). The boolean predicates
+ * (hasAcceptedOrCommittedStartedAfterWithoutWitnessing, hasStableExecutesAfterWithoutWitnessing) are
+ * u_off[q+1] > u_off[q]. The store is not modified. The one-wave / sorting build tiers split at acc_opts.cfq_wave_cap.
+ * Errors: the participant validation of acc_cfk_keydeps_mixed (domain / participant mismatch, offsets, unsorted or
+ * duplicate keys, bad ranges, end_inclusive > 1: ACC_E_ARG; 2^32 - 1 or more pairs after expansion: ACC_E_CAP);
+ * started_at, test_dep or test_status > 2, unknown flags bits, test_kinds > 0x3F: ACC_E_ARG; with test_kinds == -1 a
+ * LocalOnly X (Kind.witnessedBy() throws): ACC_E_STATE, an invalid kind ordinal: ACC_E_ARG (with a Kinds mask X's kind
+ * is not read, as in acc_map_reduce_full); a non-empty status-only store (acc_cfk_update): ACC_E_STATE. An empty
+ * store, n_query == 0 and queries without participants give empty results; a failed call leaves the context usable.
+ * The range-command half of the same questions stays with acc_map_reduce_full_ranges: the resident range-command
+ * store (acc_rcmd) keeps no status, executeAt or deps. */
+typedef struct acc_cfk_recovery_in {
+    uint32_t    n_query, mem;            /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t    n_pairs, n_ranges;       /* key_off[n_query], rng_off[n_query] */
+    acc_ts_cols test_txn;                /* [n_query] testTxnId: any TxnId, store member or not */
+    const uint32_t *key_off;  const uint64_t *key_code;              /* key-domain queries: sorted unique keys */
+    const uint32_t *rng_off;  const uint64_t *rng_start, *rng_end;   /* range-domain queries */
+    uint32_t    end_inclusive;           /* the store's Range bound type, as acc_cfk_mixed_queries */
+    uint8_t     started_at, test_dep, test_status, flags;   /* exactly acc_recovery_in's */
+    int32_t     test_kinds;              /* Kinds mask, or -1: testTxnId.kind().witnessedBy() */
+} acc_cfk_recovery_in;
+int  acc_cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *out_view);
 
 /* ---- A device-resident range-command store and the RangeDeps of new txns ----
  * The other half of PreAccept.calculatePartialDeps beside acc_cfk_keydeps_mixed: the deps on the store's range commands
