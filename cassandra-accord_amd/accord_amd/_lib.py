@@ -54,6 +54,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
+           "acc_rcmd_update_cmds", "acc_rcmd_state_view", "acc_rcmd_map_reduce_full",
            "acc_ranges_of", "acc_ranges_with", "acc_ranges_subtract", "acc_ranges_merge_touching", "acc_ranges_select",
            "acc_ranges_index_of", "acc_ranges_contains_all_keys", "acc_ranges_contains_all", "acc_rangedeps_is_covered_by",
            "acc_partial_deps_covering", "acc_rmm_without", "acc_recovery_deps_reduce"]
@@ -328,6 +329,22 @@ class RcmdTable(C.Structure):
                 ("rng_start", C.c_void_p), ("rng_end", C.c_void_p), ("dict_start", C.c_void_p), ("dict_end", C.c_void_p)]
 
 
+ACC_RCMD_KEEP_DEPS = 8
+
+
+class RcmdCmdUpdates(C.Structure):
+    _fields_ = [("n_upd", C.c_uint32), ("mem", C.c_uint32), ("n_ranges", C.c_uint64), ("txn_id", TsCols),
+                ("flags", C.c_void_p), ("rng_off", C.c_void_p), ("rng_start", C.c_void_p), ("rng_end", C.c_void_p),
+                ("execute_at", TsCols), ("status", C.c_void_p), ("n_deps", C.c_uint64), ("dep_off", C.c_void_p),
+                ("dep_txn", TsCols), ("dep_start", C.c_void_p), ("dep_end", C.c_void_p), ("dep_is_key", C.c_void_p)]
+
+
+class RcmdState(C.Structure):
+    _fields_ = [("n_cmd", C.c_uint32), ("reserved", C.c_uint32), ("n_deps", C.c_uint64), ("execute_at", TsCols),
+                ("status", C.c_void_p), ("flags", C.c_void_p), ("dep_off", C.c_void_p), ("dep_txn", TsCols),
+                ("dep_start", C.c_void_p), ("dep_end", C.c_void_p), ("dep_is_key", C.c_void_p)]
+
+
 class ConflictsIn(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("n_upd", C.c_uint32), ("end_inclusive", C.c_uint32), ("n_keys", C.c_uint64),
                 ("n_ranges", C.c_uint64), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
@@ -556,6 +573,12 @@ def load():
         L.acc_rcmd_view.restype = C.c_int
         L.acc_rcmd_rangedeps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkMixedQueries), C.POINTER(RangedepsView)]
         L.acc_rcmd_rangedeps.restype = C.c_int
+        L.acc_rcmd_update_cmds.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RcmdCmdUpdates)]
+        L.acc_rcmd_update_cmds.restype = C.c_int
+        L.acc_rcmd_state_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(RcmdState)]
+        L.acc_rcmd_state_view.restype = C.c_int
+        L.acc_rcmd_map_reduce_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRecoveryIn), C.POINTER(RangedepsView)]
+        L.acc_rcmd_map_reduce_full.restype = C.c_int
     except AttributeError:
         if not os.environ.get("ACC_LIB_PATH"):   # an older tuning build (A/B runs) may lack them; the product may not
             raise

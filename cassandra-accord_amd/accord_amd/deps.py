@@ -1164,6 +1164,10 @@ def _mixed_queries_in(q: dict, end_inclusive: int, lane_seg: int, keep: list) ->
                              p("ko"), p("kc"), p("ro"), p("rs"), p("re"), int(end_inclusive), int(lane_seg))
 
 
+_RCMD_DEP_COLS = (("dep_off", np.uint32), ("dep_msb", np.uint64), ("dep_lsb", np.uint64), ("dep_node", np.int32),
+                  ("dep_start", np.uint64), ("dep_end", np.uint64), ("dep_is_key", np.uint8))
+
+
 class RangeCmdStore:
     """A CommandStore's range commands kept in HBM (acc_rcmd_*): the rangeCommands map that InMemorySafeStore.update
     adds to (impl/InMemoryCommandStore.java:739-762, RangeCommand.update = ranges.with(add)) with its stabbing index,
@@ -1190,7 +1194,12 @@ class RangeCmdStore:
     def update(self, upd: dict):
         """Apply updates in array order: upd = dict(msb, lsb, node: the TxnIds (may repeat); flags: 0 or
         L.ACC_RCMD_ERASED per update, default 0; rng_off, rng_start, rng_end: each update's ranges, sorted and
-        non-overlapping). Key-domain TxnIds are ignored."""
+        non-overlapping). Key-domain TxnIds are ignored.
+        With a status key the update carries each command's state (acc_rcmd_update_cmds): status = Status ordinals
+        0..10; optional xmsb, xlsb, xnode = executeAts (default the TxnIds); optional dep_off, dep_msb, dep_lsb,
+        dep_node, dep_start, dep_end, dep_is_key = each update's PartialDeps as (TxnId, key | range) pairs sorted by
+        TxnId (default none); flags may then also hold L.ACC_RCMD_HAS_DEPS and L.ACC_RCMD_KEEP_DEPS (keep the stored
+        deps). Without it the stored state of an existing command stays and a new one starts NotDefined at its TxnId."""
         n = len(upd["msb"])
         fl = upd.get("flags")
         a = dict(tm=np.ascontiguousarray(upd["msb"], dtype=np.uint64), tl=np.ascontiguousarray(upd["lsb"], dtype=np.uint64),
@@ -1199,8 +1208,72 @@ class RangeCmdStore:
                  ro=np.ascontiguousarray(upd["rng_off"], dtype=np.uint32), rs=np.ascontiguousarray(upd["rng_start"], dtype=np.uint64),
                  re=np.ascontiguousarray(upd["rng_end"], dtype=np.uint64))
         p = lambda k: a[k].ctypes.data  # noqa: E731
-        ui = L.RcmdUpdates(n, L.ACC_MEM_HOST, len(a["rs"]), L.TsCols(p("tm"), p("tl"), p("tn")), p("fl"), p("ro"), p("rs"), p("re"))
-        self.ctx.check(self.ctx._lib.acc_rcmd_update(self.ctx.handle, self._h, C.byref(ui)))
+        if upd.get("status") is None:
+            ui = L.RcmdUpdates(n, L.ACC_MEM_HOST, len(a["rs"]), L.TsCols(p("tm"), p("tl"), p("tn")), p("fl"), p("ro"), p("rs"), p("re"))
+            self.ctx.check(self.ctx._lib.acc_rcmd_update(self.ctx.handle, self._h, C.byref(ui)))
+            return
+        a["st"] = np.ascontiguousarray(upd["status"], dtype=np.uint8)
+        ex = L.TsCols(None, None, None)
+        if upd.get("xmsb") is not None:
+            a.update(xm=np.ascontiguousarray(upd["xmsb"], dtype=np.uint64), xl=np.ascontiguousarray(upd["xlsb"], dtype=np.uint64),
+                     xn=np.ascontiguousarray(upd["xnode"], dtype=np.int32))
+            ex = L.TsCols(p("xm"), p("xl"), p("xn"))
+        if upd.get("dep_off") is not None:
+            for k, dt in _RCMD_DEP_COLS:
+                a[k] = np.ascontiguousarray(upd[k], dtype=dt)
+        else:
+            a["dep_off"] = np.zeros(n + 1, np.uint32)
+            for k, dt in _RCMD_DEP_COLS[1:]:
+                a[k] = np.zeros(0, dt)
+        ui = L.RcmdCmdUpdates(n, L.ACC_MEM_HOST, len(a["rs"]), L.TsCols(p("tm"), p("tl"), p("tn")), p("fl"), p("ro"), p("rs"), p("re"),
+                              ex, p("st"), len(a["dep_msb"]), p("dep_off"), L.TsCols(p("dep_msb"), p("dep_lsb"), p("dep_node")),
+                              p("dep_start"), p("dep_end"), p("dep_is_key"))
+        self.ctx.check(self.ctx._lib.acc_rcmd_update_cmds(self.ctx.handle, self._h, C.byref(ui)))
+
+    def state_view(self) -> "L.RcmdState":
+        """The state columns as device pointers (acc_rcmd_state_view; valid until the next update)."""
+        v = L.RcmdState()
+        self.ctx.check(self.ctx._lib.acc_rcmd_state_view(self.ctx.handle, self._h, C.byref(v)))
+        return v
+
+    def state(self) -> dict:
+        """Host copy of each command's state in table() order: xmsb, xlsb, xnode (executeAt), status, flags
+        (ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS) [n_cmd]; dep_off [n_cmd + 1]; dep_msb, dep_lsb, dep_node, dep_start,
+        dep_end, dep_is_key [n_deps]."""
+        v = self.state_view()
+        n, nd = int(v.n_cmd), int(v.n_deps)
+        g = lambda ptr, cnt, dt: device_array(self.ctx, ptr, cnt, dt) if cnt else np.zeros(0, dt)  # noqa: E731
+        return dict(xmsb=g(v.execute_at.msb, n, np.uint64), xlsb=g(v.execute_at.lsb, n, np.uint64),
+                    xnode=g(v.execute_at.node, n, np.int32), status=g(v.status, n, np.uint8), flags=g(v.flags, n, np.uint8),
+                    dep_off=g(v.dep_off, n + 1, np.uint32), dep_msb=g(v.dep_txn.msb, nd, np.uint64),
+                    dep_lsb=g(v.dep_txn.lsb, nd, np.uint64), dep_node=g(v.dep_txn.node, nd, np.int32),
+                    dep_start=g(v.dep_start, nd, np.uint64), dep_end=g(v.dep_end, nd, np.uint64),
+                    dep_is_key=g(v.dep_is_key, nd, np.uint8))
+
+    def map_reduce_full(self, queries: dict, started_at: int, test_dep: int, test_status: int, test_kinds: int = -1,
+                        executes_after: bool = False) -> "BatchRangeDeps":
+        """SafeCommandStore.mapReduceFull's range-command half for a batch of recovery queries against the resident
+        store (acc_rcmd_map_reduce_full; InMemorySafeStore.mapReduceRangesInternal,
+        impl/InMemoryCommandStore.java:883-960): queries and tests as CfkStore.map_reduce_full, ranges and keys by the
+        store's bound type. Host arrays out in the rangedeps() layout: range_id into the store's dictionary, dep_txn =
+        indices into table() order. The store is read in place and not modified."""
+        q = queries
+        n = len(q["msb"])
+        a = dict(qm=np.ascontiguousarray(q["msb"], dtype=np.uint64), ql=np.ascontiguousarray(q["lsb"], dtype=np.uint64),
+                 qn=np.ascontiguousarray(q["node"], dtype=np.int32), ko=np.ascontiguousarray(q["key_off"], dtype=np.uint32),
+                 kc=np.ascontiguousarray(q["key_code"], dtype=np.uint64))
+        if q.get("rng_off") is not None:
+            a.update(ro=np.ascontiguousarray(q["rng_off"], dtype=np.uint32), rs=np.ascontiguousarray(q["rng_start"], dtype=np.uint64),
+                     re=np.ascontiguousarray(q["rng_end"], dtype=np.uint64))
+        else:
+            a.update(ro=np.zeros(n + 1, np.uint32), rs=np.zeros(0, np.uint64), re=np.zeros(0, np.uint64))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ri = L.CfkRecoveryIn(n, L.ACC_MEM_HOST, len(a["kc"]), len(a["rs"]), L.TsCols(p("qm"), p("ql"), p("qn")), p("ko"), p("kc"),
+                             p("ro"), p("rs"), p("re"), int(q.get("end_inclusive", self.end_inclusive)), started_at, test_dep,
+                             test_status, L.ACC_FULL_EXECUTES_AFTER if executes_after else 0, test_kinds)
+        view = L.RangedepsView()
+        self.ctx.check(self.ctx._lib.acc_rcmd_map_reduce_full(self.ctx.handle, self._h, C.byref(ri), C.byref(view)))
+        return self.ctx.copy_out_range(view)
 
     def view(self) -> "L.RcmdTable":
         """The table as device pointers (acc_rcmd_view; valid until the next update)."""
@@ -1333,6 +1406,11 @@ class ReplicaStore:
             out["keydeps"] = self.cfk.calculate_partial_deps()
         return out
 
+    _RECOVERY_NAMES = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
+                           stable_started_before_with="stableStartedBeforeAndWitnessed",
+                           has_accepted_started_after_without="hasAcceptedOrCommittedStartedAfterWithoutWitnessing",
+                           has_stable_executes_after_without="hasStableExecutesAfterWithoutWitnessing")
+
     def begin_recovery(self, queries: dict) -> dict:
         """BeginRecovery's four questions about each query's txn (messages/BeginRecovery.java:334, 348, 365, 378),
         answered from the resident CommandsForKey store (CfkStore.map_reduce_full; queries as there, ranges by the
@@ -1340,16 +1418,23 @@ class ReplicaStore:
         executeAt > the txn: the deps of :334-341) and stable_started_before_with (STARTED_BEFORE, WITH, IS_STABLE) as
         KeyDeps; has_accepted_started_after_without (STARTED_AFTER, WITHOUT, IS_PROPOSED) and
         has_stable_executes_after_without (ANY, WITHOUT, IS_STABLE) as one boolean per query. The range-command half
-        of the same questions is Context.map_reduce_full_ranges: the resident range-command store keeps no status,
-        executeAt or deps."""
-        names = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
-                     stable_started_before_with="stableStartedBeforeAndWitnessed",
-                     has_accepted_started_after_without="hasAcceptedOrCommittedStartedAfterWithoutWitnessing",
-                     has_stable_executes_after_without="hasStableExecutesAfterWithoutWitnessing")
+        of the same questions is begin_recovery_ranges, answered from the resident range-command store."""
         out = {}
-        for name, scan in names.items():
+        for name, scan in self._RECOVERY_NAMES.items():
             sa, td, ts, after = L.RECOVERY_SCANS[scan]
             r = self.cfk.map_reduce_full(queries, sa, td, ts, executes_after=after, end_inclusive=self.end_inclusive)
+            out[name] = np.diff(np.asarray(r.u_off).astype(np.int64)) > 0 if name.startswith("has_") else r
+        return out
+
+    def begin_recovery_ranges(self, queries: dict) -> dict:
+        """The range-command half of begin_recovery's four questions (the second half of every
+        SafeCommandStore.mapReduceFull call, impl/InMemoryCommandStore.java:874-881), answered from the resident
+        range-command store over the state its updates carried (RangeCmdStore.map_reduce_full): the same four names,
+        the two deps as RangeDeps, the two has_* as one boolean per query. queries as begin_recovery takes them."""
+        out = {}
+        for name, scan in self._RECOVERY_NAMES.items():
+            sa, td, ts, after = L.RECOVERY_SCANS[scan]
+            r = self.rcmd.map_reduce_full(queries, sa, td, ts, executes_after=after)
             out[name] = np.diff(np.asarray(r.u_off).astype(np.int64)) > 0 if name.startswith("has_") else r
         return out
 

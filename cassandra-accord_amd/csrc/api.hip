@@ -47,6 +47,9 @@ void rcmd_free(acc_rcmd *store);
 void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in);
 void rcmd_table(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_table *out);
 void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rangedeps_view *view);
+void rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *in);
+void rcmd_state(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out);
+void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *view);
 }  // namespace acc
 
 namespace {
@@ -371,6 +374,33 @@ int acc_rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_querie
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::rcmd_rangedeps(ctx, store, q, out_view);
+    });
+}
+
+int acc_rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *updates)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_update_cmds(ctx, store, updates);
+    });
+}
+
+int acc_rcmd_state_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_state(ctx, store, out);
+    });
+}
+
+int acc_rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *out_view)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_map_reduce_full(ctx, store, q, out_view);
     });
 }
 

@@ -27,10 +27,23 @@
 // acc_rcmd_rangedeps: the queries validated; per query two binary searches over the stored TxnId columns (lim = stored
 // TxnIds below executeAt, tpos = its own table index or none); then rd_stab_queries and rd_build_txns as they are, with
 // the entry columns, class offsets and dictionary pointing at the store.
+// acc_rcmd_update_cmds is the same update with the state columns of each command (status, executeAt, HAS_DEPS and the
+// flattened PartialDeps: what RangeCommand.command points at); acc_rcmd_update is the call without them. The fold also
+// leaves, per touched command, which update its status / executeAt and which its deps come from; k_rc_counts counts the
+// deps of every output row beside its ranges, one more scan gives the new dep_off, and k_rc_write takes each row's state
+// and deps span from the stored row or from the delta. The deps arrays are rewritten on every update, like the table.
+// acc_rcmd_map_reduce_full (the recovery scans, mapReduceRangesInternal :883-960 with every TestStartedAt / TestDep /
+// TestStatus): k_rc_qprep's recovery variant gives lim per TestStartedAt (STARTED_BEFORE: #TxnIds < X; ANY: n;
+// STARTED_AFTER: n - #TxnIds <= X over a mirrored position column y' = n - 1 - y, so the stabbing pass's "y < lim" admits
+// exactly the commands after X) and the Kinds mask; rd_stab_queries as it is lists the (stored range, command)
+// candidates of each participant; k_rcr_filter, a wave per participant, tests each candidate's command (recovery_pred.hpp,
+// the predicate acc_map_reduce_full_ranges evaluates) and compacts the survivors in place in the participant's span;
+// rd_build_txns as it is builds the result.
 // Integer work only: HBM/latency bound, no MFMA.
 
 #include "rangedeps.hpp"
 #include "ranges_with.hpp"
+#include "recovery_pred.hpp"
 
 #include <type_traits>
 
@@ -47,6 +60,16 @@ struct acc_rcmd {
     uint8_t *flags = nullptr;
     uint32_t *rng_off = nullptr;
     uint64_t *rs = nullptr, *re = nullptr;
+    // the state of each command (flags holds HAS_DEPS beside ERASED) and its deps, dep_off[n] = ND
+    uint64_t ND = 0;
+    uint64_t *em = nullptr, *el = nullptr;
+    int32_t *en = nullptr;
+    uint8_t *status = nullptr;
+    uint32_t *dep_off = nullptr;
+    uint64_t *dm = nullptr, *dl = nullptr;
+    int32_t *dn = nullptr;
+    uint64_t *ds = nullptr, *de = nullptr;
+    uint8_t *dk = nullptr;
     // the index (rd_range_dict's arrays; class_off lies NCLS + 1 words into cls)
     uint64_t *dict_s = nullptr, *dict_e = nullptr;
     uint32_t *dincl = nullptr;
@@ -55,7 +78,7 @@ struct acc_rcmd {
     uint8_t *cs_kind = nullptr;
     uint32_t *cls = nullptr;
     // byte sizes of the arrays above in declaration order (adopted from the context: they differ from the counts)
-    size_t bytes[15] = {};
+    size_t bytes[26] = {};
 };
 
 namespace acc {
@@ -63,13 +86,23 @@ namespace acc {
 namespace rc {
 
 enum : uint64_t {
-    E_KIND = 1, E_FLAGS = 2, E_OFF = 4, E_BOUND = 8, E_ORDER = 16,
+    E_KIND = 1, E_FLAGS = 2, E_OFF = 4, E_BOUND = 8, E_ORDER = 16, E_STATUS = 32, E_DOFF = 64, E_DEPS = 128,
     // queries
     E_Q_KIND_ARG = 1 << 8, E_Q_KIND_STATE = 1 << 9, E_Q_KOFF = 1 << 10, E_Q_ROFF = 1 << 11, E_Q_RKEYS = 1 << 12,
     E_Q_KRANGES = 1 << 13, E_Q_KEYS = 1 << 14,
 };
 
 constexpr uint32_t NONE = 0xFFFFFFFFu;
+constexpr uint32_t DROP = 0xFFFFFFFEu;   // a deps source: the command holds none
+
+// a command's deps, flattened: (TxnId, key | range) pairs sorted by TxnId
+struct DepCols {
+    const uint32_t *off;
+    const uint64_t *m, *l;
+    const int32_t *n;
+    const uint64_t *s, *e;
+    const uint8_t *k;
+};
 
 struct Delta {
     const uint64_t *tm, *tl;
@@ -78,6 +111,12 @@ struct Delta {
     const uint32_t *rng_off;
     const uint64_t *rs, *re;
     uint32_t D, NR;
+    // acc_rcmd_update_cmds (state != 0): executeAt, status and deps of every update
+    uint32_t state, ND;
+    const uint64_t *xm, *xl;
+    const int32_t *xn;
+    const uint8_t *status;
+    DepCols dep;
 };
 
 struct Table {
@@ -87,6 +126,10 @@ struct Table {
     const uint32_t *rng_off;
     const uint64_t *rs, *re;
     uint32_t n;
+    const uint64_t *em, *el;
+    const int32_t *en;
+    const uint8_t *status;
+    DepCols dep;
 };
 
 struct TableOut {
@@ -95,6 +138,14 @@ struct TableOut {
     uint8_t *flags;
     uint32_t *rng_off;
     uint64_t *rs, *re;
+    uint64_t *em, *el;
+    int32_t *en;
+    uint8_t *status;
+    uint32_t *dep_off;
+    uint64_t *dm, *dl;
+    int32_t *dn;
+    uint64_t *ds, *de;
+    uint8_t *dk;
 };
 
 // a Ranges in two columns, and the sink of one with(): what ranges_with.hpp reads and writes on the device
@@ -120,7 +171,9 @@ struct SpanSink {
 // Ranges.ofSortedAndDeoverlapped with start < end inside them; the TxnId's compare words. A key-domain TxnId
 // (InMemorySafeStore.update: txnId.domain() != Range -> return) gets bit 0 of its second word set, which IDENTITY_LSB
 // leaves out: it never groups with a range-domain TxnId. g: [0] errors, [1] key-domain updates.
-__global__ __launch_bounds__(BLOCK) void k_rc_validate(Delta d, uint64_t *__restrict__ g, uint64_t *__restrict__ w0,
+// With state columns, k_rr_check's rules per update: the Status ordinal, dep_off from 0 to n_deps without decreasing and,
+// inside it, TxnIds non-decreasing by Timestamp.compareTo, dep_is_key <= 1 and start < end for a range entry.
+__global__ __launch_bounds__(BLOCK) void k_rc_validate(Delta d, uint8_t allowed, uint64_t *__restrict__ g, uint64_t *__restrict__ w0,
                                                        uint64_t *__restrict__ w1, uint64_t *__restrict__ w2)
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
@@ -128,7 +181,17 @@ __global__ __launch_bounds__(BLOCK) void k_rc_validate(Delta d, uint64_t *__rest
     uint64_t e = 0;
     const uint64_t l = d.tl[i];
     if (((l >> 1) & 7u) > ACC_KIND_LOCAL_ONLY) e |= E_KIND;
-    if (d.flags[i] & ~(uint8_t)ACC_RCMD_ERASED) e |= E_FLAGS;
+    if (d.flags[i] & ~allowed) e |= E_FLAGS;
+    if (d.state) {
+        if (d.status[i] > 10) e |= E_STATUS;
+        const uint32_t d0 = d.dep.off[i], d1 = d.dep.off[i + 1];
+        if (d1 < d0 || d1 > d.ND || (i == 0 && d0 != 0) || (i == d.D - 1 && d1 != d.ND)) e |= E_DOFF;
+        else
+            for (uint32_t j = d0; j < d1; ++j) {
+                if (d.dep.k[j] > 1 || (!d.dep.k[j] && d.dep.s[j] >= d.dep.e[j])) e |= E_DEPS;
+                if (j > d0 && ts_cmp(d.dep.m[j - 1], d.dep.l[j - 1], d.dep.n[j - 1], d.dep.m[j], d.dep.l[j], d.dep.n[j]) > 0) e |= E_DEPS;
+            }
+    }
     const uint32_t r0 = d.rng_off[i], r1 = d.rng_off[i + 1];
     if (r1 < r0 || r1 > d.NR || (i == 0 && r0 != 0) || (i == d.D - 1 && r1 != d.NR)) e |= E_OFF;
     else
@@ -191,10 +254,14 @@ __global__ __launch_bounds__(BLOCK) void k_rc_locate(uint32_t G, Delta d, Table 
 //   else ranges = ranges == null ? add : ranges.with(add), replayed by with_of.
 // Scratch of group r: two buffers of bound[r] ranges from 2 * boff[r], taking turns as the sink. Leaves the group's
 // row, its Ranges as a pointer pair (stored columns, the delta's columns or scratch) and count, and its erased flag.
+// With it the sources of its state: ssrc = the update its status and executeAt come from (NONE: the stored row's, or the
+// defaults of a row plain acc_rcmd_update inserts), dsrc = the update its deps and HAS_DEPS bit come from (NONE: the
+// stored row's, none for an inserted one; DROP: none).
 struct Folded {
     uint32_t *row, *cnt;
     uint8_t *erased;
     const uint64_t **ps, **pe;
+    uint32_t *ssrc, *dsrc;
 };
 __global__ __launch_bounds__(BLOCK) void k_rc_fold(uint32_t G, Delta d, Table s, const uint32_t *__restrict__ perm,
                                                    const uint32_t *__restrict__ gstart, const uint32_t *__restrict__ pos,
@@ -221,11 +288,13 @@ __global__ __launch_bounds__(BLOCK) void k_rc_fold(uint32_t G, Delta d, Table s,
     const uint32_t cap = (uint32_t)cap64;
     uint64_t *const bs[2] = { scr_s + 2 * b0, scr_s + 2 * b0 + cap64 };
     uint64_t *const be[2] = { scr_e + 2 * b0, scr_e + 2 * b0 + cap64 };
-    uint32_t which = 0, ignored = 0;
+    uint32_t which = 0, ignored = 0, ssrc = NONE, dsrc = NONE;
     for (uint32_t p = gstart[r]; p < gstart[r + 1]; ++p) {
         const uint32_t u = perm[p];
         if (erased) { ++ignored; continue; }
-        if (d.flags[u] & ACC_RCMD_ERASED) { erased = true; cur = Span{ nullptr, nullptr, 0 }; continue; }
+        if (d.state) ssrc = u;
+        if (d.flags[u] & ACC_RCMD_ERASED) { erased = true; cur = Span{ nullptr, nullptr, 0 }; dsrc = DROP; continue; }
+        if (d.state && !(d.flags[u] & ACC_RCMD_KEEP_DEPS)) dsrc = u;
         const uint32_t a = d.rng_off[u];
         const Span add{ d.rs + a, d.re + a, d.rng_off[u + 1] - a };
         SpanSink sink{ bs[which], be[which], 0, cap };
@@ -240,6 +309,8 @@ __global__ __launch_bounds__(BLOCK) void k_rc_fold(uint32_t G, Delta d, Table s,
     f.erased[r] = erased ? 1 : 0;
     f.ps[r] = cur.s;
     f.pe[r] = cur.e;
+    f.ssrc[r] = ssrc;
+    f.dsrc[r] = dsrc;
     if (ignored) atomicAdd((unsigned long long *)&st[0], (unsigned long long)ignored);
     if (!isnew[r]) atomicAdd((unsigned long long *)&st[1], 1ull);
 }
@@ -254,17 +325,24 @@ __global__ __launch_bounds__(BLOCK) void k_rc_insflag(uint32_t n2, const uint32_
     insf[x] = g != NONE && isnew[g] ? 1u : 0u;
 }
 
-// ranges of new row x: its group's fold, or the stored row x - #inserted below it
-__global__ __launch_bounds__(BLOCK) void k_rc_counts(uint32_t n2, Table s, const uint32_t *__restrict__ grow,
-                                                     const uint32_t *__restrict__ insx, const uint32_t *__restrict__ gcnt,
-                                                     uint64_t *__restrict__ cnt)
+// ranges of new row x: its group's fold, or the stored row x - #inserted below it; its deps (dcnt, when asked for):
+// those of the update the fold named, else the stored row's
+__global__ __launch_bounds__(BLOCK) void k_rc_counts(uint32_t n2, Delta d, Table s, const uint32_t *__restrict__ grow,
+                                                     const uint32_t *__restrict__ insx, const uint32_t *__restrict__ isnew, Folded f,
+                                                     uint64_t *__restrict__ cnt, uint64_t *__restrict__ dcnt)
 {
     const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
     if (x >= n2) return;
     const uint32_t g = grow[x];
-    if (g != NONE) { cnt[x] = gcnt[g]; return; }
     const uint32_t j = x - insx[x];
-    cnt[x] = s.rng_off[j + 1] - s.rng_off[j];
+    const bool stored = g == NONE || !isnew[g];
+    cnt[x] = g != NONE ? f.cnt[g] : s.rng_off[j + 1] - s.rng_off[j];
+    if (!dcnt) return;
+    const uint32_t src = g != NONE ? f.dsrc[g] : NONE;
+    uint32_t nd = 0;
+    if (src == NONE) nd = stored ? s.dep.off[j + 1] - s.dep.off[j] : 0u;
+    else if (src != DROP) nd = d.dep.off[src + 1] - d.dep.off[src];
+    dcnt[x] = nd;
 }
 
 // every column of new row x, once; the index's per-row inputs with it (rd_range_dict reads tinfo.y = table index,
@@ -273,7 +351,8 @@ __global__ __launch_bounds__(BLOCK) void k_rc_counts(uint32_t n2, Table s, const
 __global__ __launch_bounds__(BLOCK) void k_rc_write(uint32_t n2, Delta d, Table s, const uint32_t *__restrict__ first,
                                                     const uint32_t *__restrict__ grow, const uint32_t *__restrict__ insx,
                                                     const uint32_t *__restrict__ isnew, Folded f,
-                                                    const uint64_t *__restrict__ off, TableOut o, uint4 *__restrict__ tinfo,
+                                                    const uint64_t *__restrict__ off, const uint64_t *__restrict__ doff,
+                                                    TableOut o, uint4 *__restrict__ tinfo,
                                                     uint32_t *__restrict__ rowner, uint32_t *__restrict__ eflag,
                                                     uint64_t *__restrict__ g)
 {
@@ -290,8 +369,32 @@ __global__ __launch_bounds__(BLOCK) void k_rc_write(uint32_t n2, Delta d, Table 
         } else {
             o.tm[x] = s.tm[j]; o.tl[x] = s.tl[j]; o.tn[x] = s.tn[j];
         }
+        const bool stored = gr == NONE || !isnew[gr];
+        const uint32_t ssrc = gr != NONE ? f.ssrc[gr] : NONE, dsrc = gr != NONE ? f.dsrc[gr] : NONE;
         if (gr != NONE) { ps = f.ps[gr]; pe = f.pe[gr]; fl = f.erased[gr] ? (uint8_t)ACC_RCMD_ERASED : (uint8_t)0; }
-        else { const uint32_t a = s.rng_off[j]; ps = s.rs + a; pe = s.re + a; fl = s.flags[j]; }
+        else { const uint32_t a = s.rng_off[j]; ps = s.rs + a; pe = s.re + a; fl = s.flags[j] & ACC_RCMD_ERASED; }
+        // state: status and executeAt of the update the fold named, else the stored row's, else NotDefined at the TxnId
+        if (ssrc != NONE) { o.em[x] = d.xm[ssrc]; o.el[x] = d.xl[ssrc]; o.en[x] = d.xn[ssrc]; o.status[x] = d.status[ssrc]; }
+        else if (stored) { o.em[x] = s.em[j]; o.el[x] = s.el[j]; o.en[x] = s.en[j]; o.status[x] = s.status[j]; }
+        else { o.em[x] = o.tm[x]; o.el[x] = o.tl[x]; o.en[x] = o.tn[x]; o.status[x] = 0; }
+        // deps and HAS_DEPS likewise; doff == nullptr: no command holds deps, before or after
+        DepCols dc = s.dep;
+        uint32_t db = 0;
+        if (dsrc == NONE) {
+            if (stored) { fl |= s.flags[j] & ACC_RCMD_HAS_DEPS; db = doff ? s.dep.off[j] : 0u; }
+        } else if (dsrc != DROP) {
+            fl |= d.flags[dsrc] & ACC_RCMD_HAS_DEPS;
+            dc = d.dep;
+            db = d.dep.off[dsrc];
+        }
+        const uint64_t d0 = doff ? doff[x] : 0ull, d1 = doff ? doff[x + 1] : 0ull;
+        o.dep_off[x] = (uint32_t)d0;
+        if (x == n2 - 1) o.dep_off[n2] = (uint32_t)d1;
+        for (uint64_t k = d0; k < d1; ++k) {
+            const uint64_t a = db + (k - d0);
+            o.dm[k] = dc.m[a]; o.dl[k] = dc.l[a]; o.dn[k] = dc.n[a];
+            o.ds[k] = dc.s[a]; o.de[k] = dc.e[a]; o.dk[k] = dc.k[a];
+        }
         o.flags[x] = fl;
         const uint64_t a0 = off[x], a1 = off[x + 1];
         o.rng_off[x] = (uint32_t)a0;
@@ -328,8 +431,13 @@ struct Queries {
 // passed, its row {lim, tpos, witnesses, domain}: lim = stored TxnIds below S = executeAt (STARTED_BEFORE, :901-902),
 // tpos = the table index of a stored TxnId Timestamp.equals to its own (never a dep of itself) or NONE; the owner of
 // each of its keys and ranges; the OR-mask of the query low bounds against the first one (g[1]).
-__global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, uint4 *__restrict__ tinfo, uint32_t *__restrict__ owner,
-                                                    uint32_t *__restrict__ rowner, uint64_t *__restrict__ g)
+// RECOVERY (acc_rcmd_map_reduce_full; X = the query's testTxnId, no executeAt): the mask is test_kinds, or for -1
+// X.kind().witnessedBy() with k_rr_query's errors; lower = #stored TxnIds < X and upper = #stored TxnIds <= X give
+// lim = lower (STARTED_BEFORE), n (ANY), or n - upper over the mirrored positions (STARTED_AFTER); tpos = NONE: a command
+// Timestamp.equals to X is visited like any other (:895-906).
+template <bool RECOVERY>
+__global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, int test_kinds, uint32_t started_at, uint4 *__restrict__ tinfo,
+                                                    uint32_t *__restrict__ owner, uint32_t *__restrict__ rowner, uint64_t *__restrict__ g)
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     uint64_t ml = 0;
@@ -337,8 +445,19 @@ __global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, uint4 *_
         uint64_t e = 0;
         const uint64_t l = Q.tl[q];
         const uint32_t kind = (uint32_t)(l >> 1) & 7u;
-        if (kind > ACC_KIND_LOCAL_ONLY) e |= E_Q_KIND_ARG;          // Kind.ofOrdinal
-        else if (witnesses(kind) == 0) e |= E_Q_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+        uint32_t mask = 0;
+        if constexpr (RECOVERY) {
+            int m = test_kinds;
+            if (m < 0) {
+                m = witnessed_by(kind);
+                if (m < 0) e |= kind == ACC_KIND_LOCAL_ONLY ? E_Q_KIND_STATE : E_Q_KIND_ARG;
+            }
+            mask = m < 0 ? 0u : (uint32_t)m;
+        } else {
+            if (kind > ACC_KIND_LOCAL_ONLY) e |= E_Q_KIND_ARG;          // Kind.ofOrdinal
+            else if (witnesses(kind) == 0) e |= E_Q_KIND_STATE;         // Kind.witnesses(): LocalOnly throws
+            mask = witnesses(kind);
+        }
         const bool range = l & 1u;
         const uint64_t ref = Q.P ? Q.key[0] : Q.R ? Q.rs[0] : 0ull;
         const uint32_t k0 = Q.key_off[q], k1 = Q.key_off[q + 1];
@@ -361,28 +480,118 @@ __global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, uint4 *_
                 ml |= Q.rs[j] ^ ref;
             }
         if (e) atomicOr((unsigned long long *)&g[0], (unsigned long long)e);
-        // lim: first stored TxnId >= S; tpos: first stored TxnId >= the query's own, when equal
-        const uint64_t sm = Q.xm[q], sl = Q.xl[q];
-        const int32_t sn = Q.xn[q];
-        uint32_t lo = 0, hi = s.n;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi) >> 1;
-            if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], sm, sl, sn) < 0) lo = m + 1; else hi = m;
+        if constexpr (RECOVERY) {
+            const uint64_t xm = Q.tm[q];
+            const int32_t xn = Q.tn[q];
+            uint32_t lo = 0, hi = s.n;
+            while (lo < hi) {
+                const uint32_t m = (lo + hi) >> 1;
+                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, l, xn) < 0) lo = m + 1; else hi = m;
+            }
+            const uint32_t lower = lo;
+            hi = s.n;
+            while (lo < hi) {
+                const uint32_t m = (lo + hi) >> 1;
+                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, l, xn) <= 0) lo = m + 1; else hi = m;
+            }
+            const uint32_t upper = lo;
+            const uint32_t lim = started_at == 0 ? lower : started_at == 1 ? s.n - upper : s.n;
+            tinfo[q] = make_uint4(lim, NONE, mask, range ? 1u : 0u);
+        } else {
+            // lim: first stored TxnId >= S; tpos: first stored TxnId >= the query's own, when equal
+            const uint64_t sm = Q.xm[q], sl = Q.xl[q];
+            const int32_t sn = Q.xn[q];
+            uint32_t lo = 0, hi = s.n;
+            while (lo < hi) {
+                const uint32_t m = (lo + hi) >> 1;
+                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], sm, sl, sn) < 0) lo = m + 1; else hi = m;
+            }
+            const uint32_t lim = lo;
+            const uint64_t qm = Q.tm[q];
+            const int32_t qn = Q.tn[q];
+            lo = 0; hi = s.n;
+            while (lo < hi) {
+                const uint32_t m = (lo + hi) >> 1;
+                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], qm, l, qn) < 0) lo = m + 1; else hi = m;
+            }
+            const uint32_t tpos = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], qm, l, qn) == 0 ? lo : NONE;
+            tinfo[q] = make_uint4(lim, tpos, mask, range ? 1u : 0u);
         }
-        const uint32_t lim = lo;
-        const uint64_t qm = Q.tm[q];
-        const int32_t qn = Q.tn[q];
-        lo = 0; hi = s.n;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi) >> 1;
-            if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], qm, l, qn) < 0) lo = m + 1; else hi = m;
-        }
-        const uint32_t tpos = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], qm, l, qn) == 0 ? lo : NONE;
-        tinfo[q] = make_uint4(lim, tpos, witnesses(kind), range ? 1u : 0u);
     }
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) ml |= shfl_xor(ml, dd);
     if (lane_id() == 0 && ml) atomicOr((unsigned long long *)&g[1], (unsigned long long)ml);
+}
+
+// ---------------------------------------------------------------- recovery scans
+
+// the store's columns as recovery_pred.hpp names them
+struct StateCols {
+    const uint64_t *tm, *tl, *em, *el;
+    const int32_t *tn, *en;
+    const uint8_t *status, *flags;
+    const uint32_t *roff;
+    const uint64_t *rs, *re;
+    const uint32_t *doff;
+    const uint64_t *dm, *dl;
+    const int32_t *dn;
+    const uint64_t *ds, *de;
+    const uint8_t *dk;
+    uint32_t end_incl;
+};
+
+// STARTED_AFTER stabs positions counted from the top of the table
+__global__ __launch_bounds__(BLOCK) void k_rcr_mirror(uint32_t NE, uint32_t n, const uint2 *__restrict__ info, uint2 *__restrict__ out)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= NE) return;
+    const uint2 v = info[i];
+    out[i] = make_uint2(v.x, n - 1u - v.y);
+}
+
+// One wave per participant (key or range of a query) over the raw entries the stabbing pass left in its span of ent:
+// 64 entries at a time, a lane per entry tests its command (rr_command_passes: flags and status byte, executeAt against
+// X, and for what is left under WITH / WITHOUT the search of X in the command's deps); survivors are compacted in entry
+// order to the front of the same span (writes never pass the chunk being read) with their table positions un-mirrored,
+// and the participant's count is rewritten; its first entry stays. st: [0] entries kept, [1] deps searches.
+__global__ __launch_bounds__(BLOCK) void k_rcr_filter(uint64_t first, uint64_t nparts, uint32_t P, const uint32_t *__restrict__ owner,
+                                                      const uint32_t *__restrict__ rowner, StateCols c, const uint64_t *__restrict__ qm,
+                                                      const uint64_t *__restrict__ ql, const int32_t *__restrict__ qn,
+                                                      const uint4 *__restrict__ tinfo, RcParams prm, uint32_t mirror_n,
+                                                      ulonglong2 *__restrict__ q_out, uint64_t *__restrict__ ent,
+                                                      uint64_t *__restrict__ st)
+{
+    const uint64_t w = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (w >= nparts) return;
+    const uint32_t q = w < P ? owner[w] : rowner[w - P];
+    const uint64_t xm = qm[q], xl = ql[q];
+    const int32_t xn = qn[q];
+    const uint32_t mask = tinfo[q].z;
+    const ulonglong2 span = q_out[w];
+    const uint64_t lt = (1ull << lane_id()) - 1;
+    uint64_t kept = 0;
+    uint32_t probes = 0;
+    for (uint64_t base = 0; base < span.y; base += 64) {
+        const uint64_t k = base + lane_id();
+        bool pass = false, probed = false;
+        uint64_t x = 0;
+        if (k < span.y) {
+            x = ent[span.x + k];
+            uint32_t pos = (uint32_t)x;
+            if (mirror_n) pos = mirror_n - 1u - pos;
+            x = (x & 0xFFFFFFFF00000000ull) | pos;
+            pass = rr_command_passes(c, prm, pos, mask, xm, xl, xn, &probed);
+        }
+        const uint64_t bal = __ballot(pass);
+        probes += (uint32_t)__popcll(__ballot(probed));
+        if (pass) ent[span.x + kept + (uint64_t)__popcll(bal & lt)] = x;
+        kept += (uint64_t)__popcll(bal);
+    }
+    if (lane_id() == 0) {
+        q_out[w] = make_ulonglong2(span.x, kept);
+        if (kept) atomicAdd((unsigned long long *)&st[0], (unsigned long long)kept);
+        if (probes) atomicAdd((unsigned long long *)&st[1], (unsigned long long)probes);
+    }
 }
 
 }  // namespace rc
@@ -404,12 +613,17 @@ void rcmd_free(acc_rcmd *s)
     (void)hipSetDevice(s->device);
     for (void *p : { (void *)s->tm, (void *)s->tl, (void *)s->tn, (void *)s->flags, (void *)s->rng_off, (void *)s->rs, (void *)s->re,
                      (void *)s->dict_s, (void *)s->dict_e, (void *)s->dincl, (void *)s->cs_s, (void *)s->cs_e, (void *)s->cs_info,
-                     (void *)s->cs_kind, (void *)s->cls })
+                     (void *)s->cs_kind, (void *)s->cls, (void *)s->em, (void *)s->el, (void *)s->en, (void *)s->status,
+                     (void *)s->dep_off, (void *)s->dm, (void *)s->dl, (void *)s->dn, (void *)s->ds, (void *)s->de, (void *)s->dk })
         (void)hipFree(p);
     delete s;
 }
 
-static Table table_of(const acc_rcmd *s) { return Table{ s->tm, s->tl, s->tn, s->flags, s->rng_off, s->rs, s->re, s->n }; }
+static Table table_of(const acc_rcmd *s)
+{
+    return Table{ s->tm, s->tl, s->tn, s->flags, s->rng_off, s->rs, s->re, s->n, s->em, s->el, s->en, s->status,
+                  DepCols{ s->dep_off, s->dm, s->dl, s->dn, s->ds, s->de, s->dk } };
+}
 
 void rcmd_table(acc_ctx *ctx, acc_rcmd *s, acc_rcmd_table *out)
 {
@@ -425,13 +639,28 @@ void rcmd_table(acc_ctx *ctx, acc_rcmd *s, acc_rcmd_table *out)
                            s->rng_off ? s->rng_off : z, s->rs, s->re, s->dict_s, s->dict_e };
 }
 
-void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
+void rcmd_state(acc_ctx *ctx, acc_rcmd *s, acc_rcmd_state *out)
 {
-    if (!store || !in) fail(ACC_E_ARG, "null argument");
+    if (!s || !out) fail(ACC_E_ARG, "null argument");
+    uint32_t *z = nullptr;
+    if (!s->dep_off) {   // an empty store: dep_off = one zero
+        z = ctx->get<uint32_t>("rc_zero", 4);
+        ACC_HIP(hipMemsetAsync(z, 0, 16, ctx->stream));
+        ctx->sync();
+    }
+    *out = acc_rcmd_state{ s->n, 0u, s->ND, acc_ts_cols{ s->em, s->el, s->en }, s->status, s->flags, s->dep_off ? s->dep_off : z,
+                           acc_ts_cols{ s->dm, s->dl, s->dn }, s->ds, s->de, s->dk };
+}
+
+// acc_rcmd_update (state == false: in's state columns are not read) and acc_rcmd_update_cmds
+static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *in, bool state)
+{
     if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
     if (in->n_ranges >= 0xFFFFFFFFull) fail(ACC_E_ARG, "n_ranges must be < 2^32 - 1");
+    if (state && in->n_deps >= 0xFFFFFFFFull) fail(ACC_E_ARG, "n_deps must be < 2^32 - 1");
     hipStream_t st = ctx->stream;
     const uint32_t D = in->n_upd, NR = (uint32_t)in->n_ranges, mem = in->mem;
+    const uint32_t NDin = state ? (uint32_t)in->n_deps : 0u;
     ctx->stat("rcmd.inserted", 0);
     ctx->stat("rcmd.updated", 0);
     ctx->stat("rcmd.skipped_key_domain", 0);
@@ -440,10 +669,12 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     ctx->stat("rcmd.stored_ranges", store->n_dict);
     if (D == 0) {
         if (NR) fail(ACC_E_ARG, "rng_off must start at 0, be non-decreasing and end at n_ranges");
+        if (NDin) fail(ACC_E_ARG, "dep_off must start at 0, be non-decreasing and end at n_deps");
         return;
     }
     Delta d{};
     d.D = D; d.NR = NR;
+    d.state = state ? 1u : 0u; d.ND = NDin;
     d.tm = stage_in(ctx, "rc_in_tm", in->txn_id.msb, D, mem);
     d.tl = stage_in(ctx, "rc_in_tl", in->txn_id.lsb, D, mem);
     d.tn = stage_in(ctx, "rc_in_tn", in->txn_id.node, D, mem);
@@ -451,12 +682,27 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     d.rng_off = stage_in(ctx, "rc_in_roff", in->rng_off, (size_t)D + 1, mem);
     d.rs = stage_in(ctx, "rc_in_rs", in->rng_start, NR, mem);
     d.re = stage_in(ctx, "rc_in_re", in->rng_end, NR, mem);
+    if (state) {
+        if (in->execute_at.msb) {
+            d.xm = stage_in(ctx, "rc_in_xm", in->execute_at.msb, D, mem);
+            d.xl = stage_in(ctx, "rc_in_xl", in->execute_at.lsb, D, mem);
+            d.xn = stage_in(ctx, "rc_in_xn", in->execute_at.node, D, mem);
+        } else {
+            d.xm = d.tm; d.xl = d.tl; d.xn = d.tn;
+        }
+        d.status = stage_in(ctx, "rc_in_status", in->status, D, mem);
+        d.dep = DepCols{ stage_in(ctx, "rc_in_doff", in->dep_off, (size_t)D + 1, mem),
+                         stage_in(ctx, "rc_in_dm", in->dep_txn.msb, NDin, mem), stage_in(ctx, "rc_in_dl", in->dep_txn.lsb, NDin, mem),
+                         stage_in(ctx, "rc_in_dn", in->dep_txn.node, NDin, mem), stage_in(ctx, "rc_in_ds", in->dep_start, NDin, mem),
+                         stage_in(ctx, "rc_in_de", in->dep_end, NDin, mem), stage_in(ctx, "rc_in_dk", in->dep_is_key, NDin, mem) };
+    }
+    const uint8_t allowed = state ? (uint8_t)(ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS | ACC_RCMD_KEEP_DEPS) : (uint8_t)ACC_RCMD_ERASED;
 
     // ---- 1, 2. validate; the TxnIds' dense ranks and stable sorted order
     uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
     ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
     uint64_t *w[3] = { ctx->get<uint64_t>("rc_w0", D), ctx->get<uint64_t>("rc_w1", D), ctx->get<uint64_t>("rc_w2", D) };
-    launch(ctx, "rc_validate", k_rc_validate, dim3(grid_for(D, BLOCK)), dim3(BLOCK), 0, d, g, w[0], w[1], w[2]);
+    launch(ctx, "rc_validate", k_rc_validate, dim3(grid_for(D, BLOCK)), dim3(BLOCK), 0, d, allowed, g, w[0], w[1], w[2]);
     const uint64_t *words[3] = { w[0], w[1], w[2] };
     const DenseRank dr = dense_rank(ctx, "rc_dr", D, 3, words, nullptr, nullptr, true);
     uint32_t G, nkey;
@@ -467,10 +713,15 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
         rb.wait();
         const uint64_t e = hg[0];
         if (e & E_KIND) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in TxnId flags");
-        if (e & E_FLAGS) fail(ACC_E_ARG, "flags: only ACC_RCMD_ERASED may be set");
+        if (e & E_FLAGS)
+            fail(ACC_E_ARG, state ? "flags: only ACC_RCMD_ERASED, ACC_RCMD_HAS_DEPS and ACC_RCMD_KEEP_DEPS may be set"
+                                  : "flags: only ACC_RCMD_ERASED may be set");
         if (e & E_OFF) fail(ACC_E_ARG, "rng_off must start at 0, be non-decreasing and end at n_ranges");
         if (e & E_BOUND) fail(ACC_E_ARG, "range start must be below its end (Range: start >= end)");
         if (e & E_ORDER) fail(ACC_E_ARG, "ranges of an update must be sorted and deoverlapped (Ranges.ofSortedAndDeoverlapped)");
+        if (e & E_STATUS) fail(ACC_E_ARG, "invalid Status ordinal");
+        if (e & E_DOFF) fail(ACC_E_ARG, "dep_off must start at 0, be non-decreasing and end at n_deps");
+        if (e & E_DEPS) fail(ACC_E_ARG, "deps of an update must be sorted by TxnId, dep_is_key 0 or 1, ranges with start < end");
         G = (uint32_t)(uint64_t)cnt;
         nkey = (uint32_t)hg[1];
     }
@@ -508,7 +759,8 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     uint32_t *grow = ctx->get<uint32_t>("rc_grow", n2);
     ACC_HIP(hipMemsetAsync(grow, 0xFF, (size_t)n2 * sizeof(uint32_t), st));
     Folded f{ ctx->get<uint32_t>("rc_f_row", G), ctx->get<uint32_t>("rc_f_cnt", G), ctx->get<uint8_t>("rc_f_erased", G),
-              ctx->get<const uint64_t *>("rc_f_ps", G), ctx->get<const uint64_t *>("rc_f_pe", G) };
+              ctx->get<const uint64_t *>("rc_f_ps", G), ctx->get<const uint64_t *>("rc_f_pe", G),
+              ctx->get<uint32_t>("rc_f_ssrc", G), ctx->get<uint32_t>("rc_f_dsrc", G) };
     launch(ctx, "rc_fold", k_rc_fold, dim3(grid_for(G, BLOCK)), dim3(BLOCK), 0, G, d, s, dr.perm, (const uint32_t *)gstart,
            (const uint32_t *)pos, (const uint32_t *)isnew, (const uint32_t *)newx, (const uint64_t *)boff, scr_s, scr_e, grow, f, g + 4);
 
@@ -518,20 +770,33 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     launch(ctx, "rc_insflag", k_rc_insflag, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, (const uint32_t *)grow,
            (const uint32_t *)isnew, insf);
     scan<uint32_t, OpAdd<uint32_t>>(ctx, insf, insx, n2, true, insx + n2);
-    launch(ctx, "rc_counts", k_rc_counts, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, s, (const uint32_t *)grow,
-           (const uint32_t *)insx, (const uint32_t *)f.cnt, cnt);
+    // deps are counted and scanned only when a command holds some, before or after (a store fed by acc_rcmd_update alone
+    // runs the launches it always ran)
+    const bool deps = state || store->ND > 0;
+    uint64_t *dcnt = deps ? ctx->get<uint64_t>("rc_dcnt", n2) : nullptr;
+    uint64_t *doff = deps ? ctx->get<uint64_t>("rc_doff", (size_t)n2 + 1) : nullptr;
+    launch(ctx, "rc_counts", k_rc_counts, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, d, s, (const uint32_t *)grow,
+           (const uint32_t *)insx, (const uint32_t *)isnew, f, cnt, dcnt);
     scan<uint64_t, OpAdd<uint64_t>>(ctx, cnt, off, n2, true, off + n2);
-    uint64_t R2;
+    if (deps) scan<uint64_t, OpAdd<uint64_t>>(ctx, dcnt, doff, n2, true, doff + n2);
+    uint64_t R2, ND2 = 0;
     {
         ReadBack rb(ctx);
         const auto a = rb.u64(off + n2);
+        ReadBack::Word<uint64_t> b;
+        if (deps) b = rb.u64(doff + n2);
         rb.wait();
-        R2 = a;
+        R2 = a; ND2 = b;
     }
     if (R2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (ranges >= 2^32 - 1)");
+    if (ND2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (deps >= 2^32 - 1)");
     TableOut o{ ctx->get<uint64_t>("rc_t_tm", n2), ctx->get<uint64_t>("rc_t_tl", n2), ctx->get<int32_t>("rc_t_tn", n2),
                 ctx->get<uint8_t>("rc_t_flags", n2), ctx->get<uint32_t>("rc_t_rng_off", (size_t)n2 + 1),
-                ctx->get<uint64_t>("rc_t_rs", R2), ctx->get<uint64_t>("rc_t_re", R2) };
+                ctx->get<uint64_t>("rc_t_rs", R2), ctx->get<uint64_t>("rc_t_re", R2),
+                ctx->get<uint64_t>("rc_t_em", n2), ctx->get<uint64_t>("rc_t_el", n2), ctx->get<int32_t>("rc_t_en", n2),
+                ctx->get<uint8_t>("rc_t_status", n2), ctx->get<uint32_t>("rc_t_doff", (size_t)n2 + 1),
+                ctx->get<uint64_t>("rc_t_dm", ND2), ctx->get<uint64_t>("rc_t_dl", ND2), ctx->get<int32_t>("rc_t_dn", ND2),
+                ctx->get<uint64_t>("rc_t_ds", ND2), ctx->get<uint64_t>("rc_t_de", ND2), ctx->get<uint8_t>("rc_t_dk", ND2) };
     RdBuild b;
     b.n = n2;
     b.R = (size_t)R2;
@@ -541,7 +806,7 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     b.eflag = ctx->get<uint32_t>("rd_eflag", R2);
     b.eidx = ctx->get<uint32_t>("rd_eidx", R2 + 1);
     launch(ctx, "rc_write", k_rc_write, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, d, s, (const uint32_t *)dr.first,
-           (const uint32_t *)grow, (const uint32_t *)insx, (const uint32_t *)isnew, f, (const uint64_t *)off, o, b.tinfo, b.rowner,
+           (const uint32_t *)grow, (const uint32_t *)insx, (const uint32_t *)isnew, f, (const uint64_t *)off, (const uint64_t *)doff, o, b.tinfo, b.rowner,
            b.eflag, g);
 
     // ---- 6. the index from the new table (rd_range_dict as acc_rangedeps_batch runs it)
@@ -582,6 +847,10 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     adopt("rd_dict_s", store->dict_s); adopt("rd_dict_e", store->dict_e); adopt("rd_dincl", store->dincl);
     adopt("rd_cs_s", store->cs_s); adopt("rd_cs_e", store->cs_e); adopt("rd_cs_info", store->cs_info);
     adopt("rd_cs_kind", store->cs_kind); adopt("rd_cls", store->cls);
+    adopt("rc_t_em", store->em); adopt("rc_t_el", store->el); adopt("rc_t_en", store->en); adopt("rc_t_status", store->status);
+    adopt("rc_t_doff", store->dep_off); adopt("rc_t_dm", store->dm); adopt("rc_t_dl", store->dl); adopt("rc_t_dn", store->dn);
+    adopt("rc_t_ds", store->ds); adopt("rc_t_de", store->de); adopt("rc_t_dk", store->dk);
+    store->ND = ND2;
     store->n = n2;
     store->R = (uint32_t)R2;
     store->NE = b.NE;
@@ -593,6 +862,21 @@ void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
     ctx->stat("rcmd.erased_ignored", n_ign);
     ctx->stat("rcmd.entries", b.NE);
     ctx->stat("rcmd.stored_ranges", n_dict);
+}
+
+void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
+{
+    if (!store || !in) fail(ACC_E_ARG, "null argument");
+    acc_rcmd_cmd_updates u{};
+    u.n_upd = in->n_upd; u.mem = in->mem; u.n_ranges = in->n_ranges; u.txn_id = in->txn_id; u.flags = in->flags;
+    u.rng_off = in->rng_off; u.rng_start = in->rng_start; u.rng_end = in->rng_end;
+    rcmd_update_impl(ctx, store, &u, false);
+}
+
+void rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *in)
+{
+    if (!store || !in) fail(ACC_E_ARG, "null argument");
+    rcmd_update_impl(ctx, store, in, true);
 }
 
 static void rcmd_check_query_errors(uint64_t e)
@@ -676,7 +960,8 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
     b.tinfo = ctx->get<uint4>("rd_tinfo", nq);
     uint32_t *owner = ctx->get<uint32_t>("owner", b.P);
     b.rowner = ctx->get<uint32_t>("rd_rowner", b.R);
-    launch(ctx, "rc_qprep", k_rc_qprep, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), b.tinfo, owner, b.rowner, g);
+    launch(ctx, "rc_qprep", k_rc_qprep<false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), 0, 0u, b.tinfo, owner,
+           b.rowner, g);
     {
         ReadBack rb(ctx);
         const auto hg = rb.words((const uint64_t *)g, 2);
@@ -713,6 +998,136 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
     ctx->stat("rangedeps.block_txns", b.block_txns);
     ctx->stat("rangedeps.global_txns", b.tier_txns[10]);
     ctx->sync();
+    *view = acc_rangedeps_view{ nq, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
+                                b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
+    ctx->rd_view = *view;
+    ctx->rd_valid = true;
+}
+
+void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *in, acc_rangedeps_view *view)
+{
+    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->started_at > 2 || in->test_dep > 2 || in->test_status > 2)
+        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
+    if (in->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
+    if (in->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
+    if (in->end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
+    if (in->n_pairs + in->n_ranges >= 0xFFFFFFFFull || in->n_pairs >= 0xFFFFFFFFull || in->n_ranges >= 0xFFFFFFFFull)
+        fail(ACC_E_ARG, "n_pairs + n_ranges must be < 2^32");
+    hipStream_t st = ctx->stream;
+    const uint64_t wl0 = ctx->wave_launches;
+    ctx->rd_valid = false;
+    const uint32_t nq = in->n_query, mem = in->mem, n = store->n;
+    RdBuild b;
+    b.n = nq;
+    b.npos = n;
+    b.P = (size_t)in->n_pairs;
+    b.R = (size_t)in->n_ranges;
+    b.Q = (uint32_t)(b.P + b.R);
+    b.end_inclusive = (int)store->end_inclusive;
+    b.arena_off = ctx->get<uint64_t>("rd_arena_off", (size_t)nq + 1);
+    b.rd_off = ctx->get<uint64_t>("rd_rd_off", (size_t)nq + 1);
+    b.u_off = ctx->get<uint64_t>("rd_u_off", (size_t)nq + 1);
+    const uint64_t *dict_s = store->dict_s ? store->dict_s : ctx->get<uint64_t>("rc_dict0", 2);
+    const uint64_t *dict_e = store->dict_e ? store->dict_e : ctx->get<uint64_t>("rc_dict0", 2);
+    auto stats = [&](uint64_t raw, uint64_t kept, uint64_t probes) {
+        ctx->stat("rcr.queries", b.Q);
+        ctx->stat("rcr.raw_entries", raw);
+        ctx->stat("rcr.kept_entries", kept);
+        ctx->stat("rcr.dep_probes", probes);
+        ctx->stat("rcr.wave_launches", ctx->wave_launches - wl0);
+    };
+    auto empty = [&] {
+        ACC_HIP(hipMemsetAsync(b.arena_off, 0, ((size_t)nq + 1) * 8, st));
+        ACC_HIP(hipMemsetAsync(b.rd_off, 0, ((size_t)nq + 1) * 8, st));
+        ACC_HIP(hipMemsetAsync(b.u_off, 0, ((size_t)nq + 1) * 8, st));
+        *view = acc_rangedeps_view{ nq, store->n_dict, 0, 0, 0, 0, dict_s, dict_e, b.arena_off, ctx->get<int32_t>("rd_arena", 1),
+                                    b.rd_off, ctx->get<uint32_t>("rd_range_id", 1), b.u_off, ctx->get<uint32_t>("rd_dep_txn", 1) };
+        ctx->rd_view = *view;
+        ctx->rd_valid = true;
+        stats(0, 0, 0);
+        ctx->sync();
+    };
+    if (nq == 0) {
+        if (b.P) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+        if (b.R) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+        empty();
+        return;
+    }
+
+    // ---- stage and validate; the per-query rows
+    Queries Q{};
+    Q.nq = nq; Q.P = (uint32_t)b.P; Q.R = (uint32_t)b.R;
+    Q.tm = stage_in(ctx, "rc_q_tm", in->test_txn.msb, nq, mem);
+    Q.tl = stage_in(ctx, "rc_q_tl", in->test_txn.lsb, nq, mem);
+    Q.tn = stage_in(ctx, "rc_q_tn", in->test_txn.node, nq, mem);
+    Q.xm = Q.tm; Q.xl = Q.tl; Q.xn = Q.tn;
+    Q.key_off = stage_in(ctx, "rc_q_koff", in->key_off, (size_t)nq + 1, mem);
+    Q.key = stage_in(ctx, "rc_q_key", in->key_code, b.P, mem);
+    Q.rng_off = stage_in(ctx, "rc_q_roff", in->rng_off, (size_t)nq + 1, mem);
+    Q.rs = stage_in(ctx, "rc_q_rs", in->rng_start, b.R, mem);
+    Q.re = stage_in(ctx, "rc_q_re", in->rng_end, b.R, mem);
+    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
+    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
+    b.tinfo = ctx->get<uint4>("rd_tinfo", nq);
+    uint32_t *owner = ctx->get<uint32_t>("owner", b.P);
+    b.rowner = ctx->get<uint32_t>("rd_rowner", b.R);
+    launch(ctx, "rcr_qprep", k_rc_qprep<true>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), (int)in->test_kinds,
+           (uint32_t)in->started_at, b.tinfo, owner, b.rowner, g);
+    {
+        ReadBack rb(ctx);
+        const auto hg = rb.words((const uint64_t *)g, 2);
+        rb.wait();
+        const uint64_t e = hg[0];
+        if (e & E_Q_KIND_STATE) fail(ACC_E_STATE, "Kind.witnessedBy(): unhandled kind LocalOnly (AssertionError)");
+        if (e & E_Q_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in a testTxnId");
+        rcmd_check_query_errors(e);
+        b.mask_lo = hg[1];
+    }
+    if (store->NE == 0 || b.Q == 0) {   // nothing to stab, or nothing to stab with
+        empty();
+        return;
+    }
+
+    // ---- the stabbing pass as it is, over the store's index (STARTED_AFTER: positions counted from the top)
+    b.key_off = Q.key_off; b.rng_off = Q.rng_off;
+    b.key_code = Q.key; b.rs = Q.rs; b.re = Q.re;
+    b.tl = Q.tl;
+    b.owner = owner;
+    b.dict.batch_sorted = true;   // tpos is the table index: no txn_of_tpos
+    b.NE = store->NE;
+    b.dict_s = store->dict_s; b.dict_e = store->dict_e; b.dincl = store->dincl;
+    b.cs_s = store->cs_s; b.cs_e = store->cs_e; b.cs_info = store->cs_info; b.cs_kind = store->cs_kind;
+    b.class_off = store->cls + (rd::NCLS + 1);
+    const bool mirror = in->started_at == 1;
+    if (mirror) {
+        uint2 *mi = ctx->get<uint2>("rcr_info", store->NE);
+        launch(ctx, "rcr_mirror", k_rcr_mirror, dim3(grid_for(store->NE, BLOCK)), dim3(BLOCK), 0, store->NE, n,
+               (const uint2 *)store->cs_info, mi);
+        b.cs_info = mi;
+    }
+    rd_stab_queries(ctx, b);
+
+    // ---- the command tests on the candidates alone
+    const RcParams prm{ in->started_at, in->test_dep, in->test_status, (uint32_t)(in->flags & ACC_FULL_EXECUTES_AFTER) };
+    const StateCols c{ store->tm, store->tl, store->em, store->el, store->tn, store->en, store->status, store->flags, store->rng_off,
+                       store->rs, store->re, store->dep_off, store->dm, store->dl, store->dn, store->ds, store->de, store->dk,
+                       store->end_inclusive };
+    uint64_t *fst = g + 4;   // zeroed above; the prep kernel writes g[0], g[1]
+    if (b.E)
+        launch_waves(ctx, "rcr_filter", k_rcr_filter, (uint64_t)b.Q, (uint64_t)b.Q, (uint32_t)b.P, (const uint32_t *)owner,
+                     (const uint32_t *)b.rowner, c, Q.tm, Q.tl, Q.tn, (const uint4 *)b.tinfo, prm, mirror ? n : 0u, b.v.q_out, b.v.ent, fst);
+    rd_build_txns(ctx, b);
+    uint64_t kept, probes;
+    {
+        ReadBack rb(ctx);
+        const auto hs = rb.words((const uint64_t *)fst, 2);
+        rb.wait();
+        kept = hs[0]; probes = hs[1];
+    }
+    stats(b.E, kept, probes);
     *view = acc_rangedeps_view{ nq, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
                                 b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
     ctx->rd_view = *view;

@@ -18,6 +18,7 @@
 //   4. build          Deps.Builder: keys with >= 1 entry, one (query, TxnId rank) radix sort for the sorted unique
 //                     TxnIds and each entry's index, the Java keysToTxnIds layout.
 #include "keydeps.hpp"
+#include "recovery_pred.hpp"
 
 namespace acc {
 
@@ -26,10 +27,6 @@ constexpr uint32_t RC_CH = 256;   // CFK entries per work chunk: one wave, four 
 enum : uint64_t {
     RC_ERR_KIND_STATE = 1, RC_ERR_KIND_ARG = 2, RC_ERR_KEYS = 4, RC_ERR_QOFF = 8,
     RC_ERR_MISS_IDX = 16, RC_ERR_MISS_SORT = 32, RC_ERR_MISS_OFF = 64,
-};
-
-struct RcParams {
-    uint32_t started_at, test_dep, test_status, exec_after;
 };
 
 template <class T>
@@ -512,10 +509,7 @@ struct RrQueries {
     uint32_t nq;
 };
 
-__device__ __forceinline__ bool rr_contains(uint64_t s, uint64_t e, uint64_t k, bool ei)
-{
-    return ei ? (s < k && k <= e) : (s <= k && k < e);   // Range.contains (Range.java:40-138)
-}
+// rr_contains, rr_deps_intersect and rr_command_passes: recovery_pred.hpp (shared with the resident route, rcmd.hip)
 
 __global__ __launch_bounds__(BLOCK) void k_rr_check(RrCmds c, uint32_t *__restrict__ tflag, uint64_t *__restrict__ errs)
 {
@@ -616,30 +610,6 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
     if (e) atomicOr((unsigned long long *)errs, (unsigned long long)e);
 }
 
-// Deps.intersects(X, ranges of entry i): a KeyDeps entry of X whose key one of the ranges contains, or a RangeDeps entry
-// of X whose range intersects one of them
-__device__ bool rr_deps_intersect(const RrCmds &c, uint32_t i, uint64_t xm, uint64_t xl, int32_t xn)
-{
-    uint32_t lo = c.doff[i], hi = c.doff[i + 1];
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.dm[m], c.dl[m], c.dn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
-    const uint32_t r0 = c.roff[i], r1 = c.roff[i + 1];
-    const bool ei = c.end_incl != 0;
-    for (uint32_t j = lo; j < c.doff[i + 1] && ts_cmp(c.dm[j], c.dl[j], c.dn[j], xm, xl, xn) == 0; ++j) {
-        const uint64_t s = c.ds[j];
-        if (c.dk[j]) {
-            uint32_t a = r0, b = r1;   // first range whose end reaches the key
-            while (a < b) { const uint32_t m = (a + b) >> 1; if (ei ? c.re[m] < s : c.re[m] <= s) a = m + 1; else b = m; }
-            if (a < r1 && rr_contains(c.rs[a], c.re[a], s, ei)) return true;
-        } else {
-            const uint64_t t = c.de[j];
-            uint32_t a = r0, b = r1;   // first range ending after s
-            while (a < b) { const uint32_t m = (a + b) >> 1; if (c.re[m] <= s) a = m + 1; else b = m; }
-            if (a < r1 && c.rs[a] < t) return true;
-        }
-    }
-    return false;
-}
-
 // does range (s, e) of a command intersect the query's participants (Routables.foldl over rangeCommand.ranges, sliced)
 __device__ __forceinline__ bool rr_hits_query(const RrQueries &Q, uint32_t q, uint64_t s, uint64_t e, bool ei)
 {
@@ -651,33 +621,6 @@ __device__ __forceinline__ bool rr_hits_query(const RrQueries &Q, uint32_t q, ui
     }
     while (a < b) { const uint32_t m = (a + b) >> 1; if (ei ? Q.ps[m] <= s : Q.ps[m] < s) a = m + 1; else b = m; }
     return a < end && rr_contains(s, e, Q.ps[a], ei);
-}
-
-// the per-command tests of mapReduceRangesInternal (:889-933) plus the optional executeAt > testTxnId map filter
-__device__ bool rr_command_passes(const RrCmds &c, const RcParams &p, uint32_t i, uint32_t mask, uint64_t xm, uint64_t xl, int32_t xn)
-{
-    const uint32_t f = c.flags[i];
-    const bool hist = (f & ACC_RCMD_HISTORICAL) != 0;
-    if (!(((mask >> ((c.tl[i] >> 1) & 7u)) & 1u))) return false;   // testKind.test(txnId.kind())
-    if (hist) {
-        if (p.test_status != 0 || p.test_dep != 2) return false;      // historical: ANY_STATUS + ANY_DEPS only
-        if (p.exec_after && ts_cmp(c.tm[i], c.tl[i], c.tn[i], xm, xl, xn) <= 0) return false;   // executeAt = txnId
-        return true;
-    }
-    if (f & ACC_RCMD_ERASED) return false;
-    const int ex_cmp = ts_cmp(c.em[i], c.el[i], c.en[i], xm, xl, xn);
-    // STARTED_BEFORE falls through into ANY's test (:897-901)
-    if (p.started_at != 1 && p.test_dep != 2 && ex_cmp < 0) return false;
-    const uint32_t st = c.status[i];
-    if (p.test_status == 1 && !(st == 3 || st == 4 || st == 5)) return false;   // IS_PROPOSED: Accepted, PreCommitted, Committed
-    if (p.test_status == 2 && !(st >= 6 && st < 9)) return false;               // IS_STABLE: Stable <= s < Truncated
-    if (p.test_dep != 2) {
-        if (!(f & ACC_RCMD_HAS_DEPS)) return false;
-        const bool has = rr_deps_intersect(c, i, xm, xl, xn);
-        if ((p.test_dep == 0) == !has) return false;
-    }
-    if (p.exec_after && ex_cmp <= 0) return false;
-    return true;
 }
 
 struct RrChunks {

@@ -47,6 +47,9 @@
  *                          impl/InMemoryCommandStore.java:739-762 (RangeCommand.update = ranges.with(add), :524-539) for
  *                          batches of commands, and the range-command half of mapReduceActive (:863-870, :883-960) for
  *                          new txns only, read from the store's resident stabbing index.
+ *   acc_rcmd_map_reduce_full  the range-command half of the recovery scans (mapReduceRangesInternal :883-960 with every
+ *                          TestStartedAt / TestDep / TestStatus) read from the same store and the state its updates
+ *                          carry (acc_rcmd_update_cmds).
  *   acc_levelise           execution-order restatement of Commands.updateWaitingOn local/Commands.java:776-830
  *                          (deterministic wavefront schedule).
  *
@@ -1000,8 +1003,9 @@ int  acc_cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queri
  * LocalOnly X (Kind.witnessedBy() throws): ACC_E_STATE, an invalid kind ordinal: ACC_E_ARG (with a Kinds mask X's kind
  * is not read, as in acc_map_reduce_full); a non-empty status-only store (acc_cfk_update): ACC_E_STATE. An empty
  * store, n_query == 0 and queries without participants give empty results; a failed call leaves the context usable.
- * The range-command half of the same questions stays with acc_map_reduce_full_ranges: the resident range-command
- * store (acc_rcmd) keeps no status, executeAt or deps. */
+ * The range-command half of the same questions is acc_rcmd_map_reduce_full below, which takes this query struct and
+ * answers from the resident range-command store (acc_rcmd); acc_map_reduce_full_ranges answers them over a table the
+ * caller passes whole. */
 typedef struct acc_cfk_recovery_in {
     uint32_t    n_query, mem;            /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
     uint64_t    n_pairs, n_ranges;       /* key_off[n_query], rng_off[n_query] */
@@ -1072,7 +1076,7 @@ typedef struct acc_rcmd_table {
     uint64_t    n_ranges;              /* rng_off[n_cmd] */
     uint32_t    n_dict, reserved;
     acc_ts_cols txn_id;                /* [n_cmd] TxnId order */
-    const uint8_t  *flags;             /* [n_cmd] 0 or ACC_RCMD_ERASED */
+    const uint8_t  *flags;             /* [n_cmd] ACC_RCMD_ERASED (and ACC_RCMD_HAS_DEPS once acc_rcmd_update_cmds set it) */
     const uint32_t *rng_off;           /* [n_cmd+1] */
     const uint64_t *rng_start, *rng_end; /* [n_ranges] */
     const uint64_t *dict_start, *dict_end; /* [n_dict] distinct ranges of the non-erased commands, Range::compare order */
@@ -1083,6 +1087,86 @@ void acc_rcmd_destroy(acc_rcmd *store);
 int  acc_rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *updates);
 int  acc_rcmd_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_table *out);
 int  acc_rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rangedeps_view *out_view);
+
+/* The state of each stored range command, and the recovery scans read from it.
+ * The reference's RangeCommand points at the live Command (RangeCommand.command, impl/InMemoryCommandStore.java:524-539),
+ * whose status, executeAt and PartialDeps mapReduceRangesInternal's recovery predicates read (:889-933). The store keeps
+ * them per command beside its Ranges: status (Status ordinal 0..10 as in acc_range_cmds_in), execute_at (raw bits), the
+ * ACC_RCMD_HAS_DEPS bit in the flags column and the PartialDeps flattened as acc_range_cmds_in describes them: (TxnId,
+ * key | range) pairs sorted by TxnId.
+ *
+ * acc_rcmd_update_cmds is acc_rcmd_update with these columns: the ranges fold exactly as there (same grouping by
+ * Timestamp.equals, array-order replay of Ranges.with, erasure rule and skipping of key-domain TxnIds; one
+ * implementation serves both), and per command (group of updates of one TxnId, in array order)
+ *   status, execute_at  those of the group's last update (execute_at.msb == NULL: the TxnIds, executeAtOrTxnId);
+ *   deps, HAS_DEPS      those of the group's last update without ACC_RCMD_KEEP_DEPS; if every update of the group
+ *                       carries it the stored deps and bit stay (a newly inserted command: none). An update's deps are
+ *                       [dep_off[u], dep_off[u+1]); those of a KEEP_DEPS or erasing update are validated and ignored;
+ *   ACC_RCMD_ERASED     the update stores its own status and executeAt, drops the deps and clears HAS_DEPS; every
+ *                       later update of an erased command changes nothing (rcmd.erased_ignored), its state included.
+ * A row that plain acc_rcmd_update inserts has status 0 (NotDefined), executeAt = its raw TxnId, no deps and HAS_DEPS
+ * clear; on an existing row acc_rcmd_update leaves the state as it is, except that erasing drops the deps and clears
+ * HAS_DEPS (an erased row holds neither ranges nor deps). Flags allowed here: ACC_RCMD_ERASED, ACC_RCMD_HAS_DEPS,
+ * ACC_RCMD_KEEP_DEPS; ACC_RCMD_HISTORICAL or any other bit: ACC_E_ARG. historicalRangeCommands stay unmodelled, as in
+ * acc_rcmd_rangedeps. Errors beside acc_rcmd_update's (all ACC_E_ARG, checked before anything indexes through an
+ * offset): status > 10; dep_off not starting at 0 / decreasing / not ending at n_deps; an update's dep TxnIds decreasing
+ * by Timestamp.compareTo; a range entry with start >= end; dep_is_key > 1. 2^32 - 1 or more stored deps: ACC_E_CAP. A
+ * rejected batch leaves the store unchanged. Every update rewrites the state columns with the table (rows shift when
+ * TxnIds are inserted below them and their deps move with them).
+ *
+ * acc_rcmd_state_view: DEVICE pointers to the state columns in acc_rcmd_view table order, valid until the next update
+ * of the store. flags is the table's flags column: ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS.
+ *
+ * acc_rcmd_map_reduce_full answers acc_map_reduce_full_ranges' questions from the resident store (no historical rows)
+ * for the query struct of acc_cfk_map_reduce_full, so one query batch serves both halves (end_inclusive must equal the
+ * store's: ACC_E_ARG). Per query X = test_txn[q] a stored command C is visited iff it is not erased; its TxnId is in the
+ * TestStartedAt window (< X for STARTED_BEFORE, > X strictly for STARTED_AFTER, any for ANY: no self-exclusion, under
+ * ANY a command Timestamp.equals to X is visited, :895-906); for STARTED_BEFORE and ANY with test_dep != ANY_DEPS its
+ * executeAt >= X (:901-905; STARTED_AFTER does not test it); the status test holds (IS_PROPOSED: Accepted,
+ * PreCommitted, Committed; IS_STABLE: Stable <= s < Truncated); its kind is in the Kinds mask (test_kinds == -1:
+ * X.kind().witnessedBy()); for WITH / WITHOUT HAS_DEPS is set and Deps.intersects(X, C.ranges) == (test_dep == WITH);
+ * with ACC_FULL_EXECUTES_AFTER executeAt > X. Each range of a visited C that contains one of X's keys or intersects one
+ * of X's ranges is collected per Range. The stabbing index lists the (stored range, command) candidates of each
+ * participant inside the TxnId window and the Kinds mask; only those are tested (stats rcr.queries, rcr.raw_entries,
+ * rcr.kept_entries, rcr.dep_probes, rcr.wave_launches). Result: an acc_rangedeps_view in the layout of
+ * acc_rcmd_rangedeps (range_id into the store's dictionary, dep_txn = table indices, ascending), the context's last
+ * RangeDeps result. The boolean predicates are u_off[q+1] > u_off[q]. The store is not modified. Errors: the participant
+ * validation of acc_rcmd_rangedeps (ACC_E_ARG); started_at, test_dep or test_status > 2, unknown flags bits, test_kinds
+ * > 0x3F: ACC_E_ARG; with test_kinds == -1 a LocalOnly X: ACC_E_STATE, an invalid kind ordinal: ACC_E_ARG. An empty
+ * store, n_query == 0 and queries without participants give empty results; a failed call leaves the context usable. */
+#define ACC_RCMD_KEEP_DEPS  8u
+
+typedef struct acc_rcmd_cmd_updates {
+    uint32_t    n_upd, mem;            /* as acc_rcmd_updates */
+    uint64_t    n_ranges;
+    acc_ts_cols txn_id;
+    const uint8_t  *flags;             /* [n_upd] ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS | ACC_RCMD_KEEP_DEPS */
+    const uint32_t *rng_off;
+    const uint64_t *rng_start, *rng_end;
+    acc_ts_cols execute_at;            /* [n_upd]; msb == NULL: the TxnIds */
+    const uint8_t  *status;            /* [n_upd] Status ordinals 0..10 */
+    uint64_t    n_deps;                /* dep_off[n_upd] */
+    const uint32_t *dep_off;           /* [n_upd+1] */
+    acc_ts_cols     dep_txn;           /* [n_deps] sorted by TxnId per update */
+    const uint64_t *dep_start, *dep_end;
+    const uint8_t  *dep_is_key;
+} acc_rcmd_cmd_updates;
+
+typedef struct acc_rcmd_state {
+    uint32_t    n_cmd, reserved;
+    uint64_t    n_deps;                /* dep_off[n_cmd] */
+    acc_ts_cols execute_at;            /* [n_cmd] table order */
+    const uint8_t  *status;            /* [n_cmd] */
+    const uint8_t  *flags;             /* [n_cmd] ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS */
+    const uint32_t *dep_off;           /* [n_cmd+1] */
+    acc_ts_cols     dep_txn;           /* [n_deps] */
+    const uint64_t *dep_start, *dep_end;
+    const uint8_t  *dep_is_key;
+} acc_rcmd_state;
+
+int  acc_rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *updates);
+int  acc_rcmd_state_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out);
+int  acc_rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *out_view);
 
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
