@@ -50,21 +50,24 @@ class Context:
 
     def __init__(self, device: int = 0, timing: bool = False, force_replay: bool = False, *, cfk_hot: int = 0,
                  lv_tier: str = "auto", lv_chunk: int = 0, no_window_tier: bool = False, rd_wide_sort: bool = False,
-                 pd_serial: bool = False, cfq_wave_cap: int = 0, wave_grid_max: int = 0, tier_grid_max: int = 0):
+                 pd_serial: bool = False, cfq_wave_cap: int = 0, wave_grid_max: int = 0, tier_grid_max: int = 0,
+                 no_stream_ahead: bool = False):
         """acc_opts, fixed for the context's life (the library reads no environment): timing = per-kernel HIP events;
         the rest force code paths for tests (force_replay: the exact replay scan; cfk_hot: the closed-form threshold of
         acc_cfk_apply; lv_tier / lv_chunk: the levelise walk; no_window_tier: the KeyDeps sorting tiers; rd_wide_sort:
         RangeDeps 64-bit sort keys; cfq_wave_cap: the hit count up to which acc_cfk_keydeps builds a query's KeyDeps in one
         wave; wave_grid_max: the most blocks one slice of a wave-per-item launch holds, 0 = 2^23, so that a few thousand
         chunks take many slices; tier_grid_max: the most blocks a persistent KeyDeps write-tier grid holds (flags bits 16..31),
-        0 = the defaults, so that a few dozen big txns take many iterations per block) or trade speed for memory (pd_serial: acc_partial_deps_batch on one buffer set)."""
+        0 = the defaults, so that a few dozen big txns take many iterations per block; no_stream_ahead: the KeyDeps lean
+        stream pass behind the size read-back, never ahead of it) or trade speed for memory (pd_serial: acc_partial_deps_batch on one buffer set)."""
         self.timing_enabled = timing
         self.device = device
         self._lib = L.load()
         h = C.c_void_p()
         flags = ((L.ACC_OPT_TIMING if timing else 0) | (L.ACC_OPT_FORCE_REPLAY if force_replay else 0) |
                  (L.ACC_OPT_NO_WINDOW_TIER if no_window_tier else 0) | (L.ACC_OPT_RD_WIDE_SORT if rd_wide_sort else 0) |
-                 (L.ACC_OPT_PD_SERIAL if pd_serial else 0))
+                 (L.ACC_OPT_PD_SERIAL if pd_serial else 0) |
+                 (L.ACC_OPT_KD_NO_STREAM_AHEAD if no_stream_ahead else 0))
         if not 0 <= int(tier_grid_max) <= 0xFFFF:
             raise ValueError("tier_grid_max must be within 0..65535")
         flags |= int(tier_grid_max) << L.ACC_OPT_TIER_GRID_SHIFT

@@ -113,6 +113,7 @@ void ctx_destroy(acc_ctx *ctx)
     }
     if (ctx->fork_ev) (void)hipEventDestroy(ctx->fork_ev);
     if (ctx->lane_ev) (void)hipEventDestroy(ctx->lane_ev);
+    if (ctx->read_ev) (void)hipEventDestroy(ctx->read_ev);
     if (ctx->pinned) (void)hipHostFree(ctx->pinned);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     acc_ctx *child = ctx->child;

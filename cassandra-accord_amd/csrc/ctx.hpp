@@ -63,6 +63,7 @@ struct acc_ctx {
     hipStream_t aux[NAUX] = {};
     hipEvent_t fork_ev = nullptr, join_ev[NAUX] = {};
     hipEvent_t lane_ev = nullptr;          // a point of the side lane (aux[0]) the main stream waits for: lane_mark / lane_wait
+    hipEvent_t read_ev = nullptr;          // behind a read-back on the main stream: read_mark / read_wait / fork_at_read
     bool lane_open = false;                // between lane_fork and lane_join: aux[0] may be running beside the main stream
     hipStream_t launch_stream = nullptr;   // where acc::launch enqueues (nullptr = `stream`)
     // decoupled look-back scan status, double buffered: each scan zeroes the words the previous scan dirtied in
@@ -180,6 +181,13 @@ struct acc_ctx {
         auto it = bufs.find(ns.empty() ? std::string(name) : ns + name);
         return it == bufs.end() ? nullptr : it->second.ptr;
     }
+    // the named buffer's capacity in bytes (0 if the context holds none): what a kernel enqueued before its size is
+    // known may write
+    size_t buf_cap(const char *name) const
+    {
+        auto it = bufs.find(ns.empty() ? std::string(name) : ns + name);
+        return it == bufs.end() || !it->second.ptr ? 0 : it->second.bytes;
+    }
 
     hipEvent_t take_event()
     {
@@ -219,19 +227,37 @@ struct acc_ctx {
 
     hipStream_t cur() const { return launch_stream ? launch_stream : stream; }
 
+    void need_aux()
+    {
+        if (fork_ev) return;
+        ACC_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+        ACC_HIP(hipEventCreateWithFlags(&lane_ev, hipEventDisableTiming));
+        ACC_HIP(hipEventCreateWithFlags(&read_ev, hipEventDisableTiming));
+        for (int i = 0; i < NAUX; ++i) {
+            ACC_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
+            ACC_HIP(hipEventCreateWithFlags(&join_ev[i], hipEventDisableTiming));
+        }
+    }
     // aux streams 0..k-1 wait for everything enqueued on the main stream so far
     void fork(int k)
     {
-        if (!fork_ev) {
-            ACC_HIP(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
-            ACC_HIP(hipEventCreateWithFlags(&lane_ev, hipEventDisableTiming));
-            for (int i = 0; i < NAUX; ++i) {
-                ACC_HIP(hipStreamCreateWithFlags(&aux[i], hipStreamNonBlocking));
-                ACC_HIP(hipEventCreateWithFlags(&join_ev[i], hipEventDisableTiming));
-            }
-        }
+        need_aux();
         ACC_HIP(hipEventRecord(fork_ev, stream));
         for (int i = 0; i < k; ++i) ACC_HIP(hipStreamWaitEvent(aux[i], fork_ev, 0));
+    }
+    // A read-back the host waits for while the main stream goes on: read_mark behind the copy, read_wait where the
+    // host needs the words (an event wait: the kernels enqueued behind the mark keep running), fork_at_read instead of
+    // fork for side-stream launches that rest on what the copy saw and must not queue behind those kernels. Unlike
+    // sync(), read_wait frees no replaced buffer and resolves no timing event: both wait for the next sync().
+    void read_mark()
+    {
+        need_aux();
+        ACC_HIP(hipEventRecord(read_ev, stream));
+    }
+    void read_wait() { ACC_HIP(hipEventSynchronize(read_ev)); }
+    void fork_at_read(int k)
+    {
+        for (int i = 0; i < k; ++i) ACC_HIP(hipStreamWaitEvent(aux[i], read_ev, 0));
     }
     // the main stream waits for aux streams 0..k-1
     void join(int k)

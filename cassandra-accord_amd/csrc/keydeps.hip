@@ -32,7 +32,8 @@
 //      tie words of the dictionary kernels. A sorted-batch dictionary that met a tie is redone by the general sort
 //      here and the columns built again (one more sync).
 //   3. sizes (keydeps_runs): E, the number of big txns and of stream txns with a run record, the 9-16-key flag: they
-//      size the result arrays and pick the launches.
+//      size the result arrays and pick the launches. The host waits on an event behind the copy: the lean stream
+//      pass, which needs none of them, is already enqueued and runs meanwhile (from a context's second call on).
 //   4. compaction (finish): the result totals, gather-count checks, the tiers' counts. Again after the sorting tiers
 //      or the global fallback (which has one sync of its own), when the first round left txns to them.
 // The replay path has syncs 1 and 2, then one for E and one for the result totals.
@@ -2136,7 +2137,7 @@ __global__ __launch_bounds__(BLOCK) void k_v3_mark(uint32_t n, const uint32_t *_
                                                    uint32_t *__restrict__ psz, uint32_t raw_cap,
                                                    uint32_t *__restrict__ bigflag, uint64_t *__restrict__ szA,
                                                    uint64_t *__restrict__ szK, uint64_t *__restrict__ any16,
-                                                   uint64_t *__restrict__ eb, uint32_t *__restrict__ runflag)
+                                                   uint64_t *__restrict__ eb, uint64_t *__restrict__ flagw)
 {
     const uint32_t t = (blockIdx.x * BLOCK + threadIdx.x) / MK_G, sub = threadIdx.x & (MK_G - 1);
     if (t >= n) return;   // group-uniform: shuffles stay inside the group
@@ -2170,7 +2171,9 @@ __global__ __launch_bounds__(BLOCK) void k_v3_mark(uint32_t n, const uint32_t *_
     const bool big = nk > (uint32_t)ST_G || e > (uint32_t)ST_N2 || (run_rec && raw > raw_cap);
     if (sub == 0) {
         bigflag[t] = big ? 1u : 0u;
-        runflag[t] = run_rec && !big ? 1u : 0u;   // a stream txn with a run record: the RUNS stream pass
+        // the two list flags in one word, scanned beside the sizes (k_v3_lists): big in the low half; in the high half a
+        // stream txn with a run record (the RUNS stream pass)
+        flagw[t] = (big ? 1ull : 0ull) | (run_rec && !big ? 1ull << 32 : 0ull);
         szA[t] = (uint64_t)kd + e;
         szK[t] = kd;
         eb[t] = big ? e : 0u;   // the big txns' entries: their TxnId scratch bases by the same multi-scan
@@ -2180,12 +2183,19 @@ __global__ __launch_bounds__(BLOCK) void k_v3_mark(uint32_t n, const uint32_t *_
 }
 
 
-// per big txn (one wave each, list order): dependency entries E from the per-pair counts of the mark pass
-__global__ __launch_bounds__(BLOCK) void k_v3_compact(uint32_t n, const uint32_t *__restrict__ bigflag,
-                                                      const uint32_t *__restrict__ bpos, uint32_t *__restrict__ blist)
+// the big txns and the stream txns with a run record, each list in txn order: a txn's places are the two halves of the
+// exclusive prefix of the mark pass's flag words (fewer than 2^30 txns: each half stays a count of its own)
+__global__ __launch_bounds__(BLOCK) void k_v3_lists(uint32_t n, const uint64_t *__restrict__ flagw,
+                                                    const uint64_t *__restrict__ fpos, uint32_t *__restrict__ blist,
+                                                    uint32_t *__restrict__ rlist)
 {
     const uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
-    if (t < n && bigflag[t]) blist[bpos[t]] = t;
+    if (t >= n) return;
+    const uint64_t f = flagw[t];
+    if (!f) return;
+    const uint64_t p = fpos[t];
+    if (f & 1u) blist[(uint32_t)p] = t;
+    else rlist[(uint32_t)(p >> 32)] = t;
 }
 // tier routing of the big txns (thread per list entry, one atomic per list per block). With ranks within 25 bits: the
 // window tier (<= 8 or <= 16 keys; gstat[7] / gstat[8]), else medium (E <= MED_E, <= MED_K keys) or the u32-record
@@ -2297,6 +2307,11 @@ struct V3Stream {
     int32_t *arena;
     uint32_t *key_idx, *dep_scr;              // dep_scr: TxnIds at the txn's slot t * ST_SLOT, compacted by k_v3_ucompact
     uint64_t *err;                            // gather count mismatches
+    // a pass enqueued ahead of the size read-back (e_dev set): the batch's E as the size scan left it, the pairs P and
+    // the ints the arena buffer holds. Every wave leaves before its first store when P + E does not fit.
+    const uint64_t *e_dev;
+    uint64_t pairs, arena_cap;
+    uint32_t t0;                              // !LIST: the pass takes the txns [t0, t0 + n)
     uint32_t n, ntiles;
 };
 
@@ -2367,6 +2382,13 @@ __device__ unsigned long long *g_sr_prof;   // the RUNS instance's rows (its own
 #define ST_PH(i) ((void)0)
 #endif
 
+// The share of the lean pass enqueued ahead of the size read-back: the first 1 / ACC_AHEAD_DIV of the txns. The whole
+// pass ahead (1) fills every CU before the window tier arrives, whose 37-KB blocks then wait for LDS until the lean
+// grid is spent (v2_write_win 0.56 -> 0.67 ms, and it ends the phase); a share that lasts about as long as the
+// read-back and the side-stream launches take keeps the GPU busy there and leaves the tier its places.
+#ifndef ACC_AHEAD_DIV
+#define ACC_AHEAD_DIV 8
+#endif
 // EntT: u32 (rank << 4 | key) when ranks fit 28 bits, else u64
 #ifndef ACC_ST_WAVES
 #define ACC_ST_WAVES 24   // resident waves per CU the stream pass is compiled for (32: a 64-VGPR budget that spills)
@@ -2383,6 +2405,8 @@ __global__ __launch_bounds__(NT, ACC_ST_WAVES * 64 / NT) void k_v3_stream(V3Stre
     uint64_t ph[8];
 #endif
     ST_PH(0);
+    // wave-uniform, and the kernel has no block barrier: no wave waits for one that left
+    if (s.e_dev && s.pairs + *s.e_dev > s.arena_cap) return;
     __shared__ EntT ent[TT][N2];
     __shared__ uint32_t kc[TT][G];
     __shared__ uint32_t kbase[TT][G];
@@ -2394,7 +2418,7 @@ __global__ __launch_bounds__(NT, ACC_ST_WAVES * 64 / NT) void k_v3_stream(V3Stre
     const uint32_t tile = blockIdx.x * (NT / 64) + (tid >> 6);   // wave tile: 64 / G txns
     const uint32_t slot = tile * (64 / G) + lane / G;
     const bool valid = slot < s.n;
-    const uint32_t t = LIST ? (valid ? s.list[slot] : 0u) : slot;
+    const uint32_t t = LIST ? (valid ? s.list[slot] : 0u) : s.t0 + slot;
     TxnCtx c{};
     bool big = false;
     uint64_t aoff = 0, koff = 0;
@@ -2924,6 +2948,8 @@ CfkBuild build_cfk(acc_ctx *ctx, const acc_batch_in *in, CfkOpts opts)
     const bool overlap = pair_plan(cb) && cb.dict.fast_ok && cb.pp.rk.bits + cb.dict.rbits + 1 <= 64;
     ctx->stat("keydeps.build_overlap", overlap ? 1 : 0);
     ctx->stat("keydeps.bc_sort_passes", 0);
+    ctx->stat("keydeps.stream_ahead", 0);   // (set by keydeps_runs: the replay path has no stream pass)
+    ctx->stat("keydeps.stream_ahead_redo", 0);
     if (overlap) ctx->lane_fork();
     else build_dictionary(ctx, n, cb.tm, cb.tl, cb.tn, cb.em, cb.el, cb.en, cb.g, cb.dict, true);
 
@@ -2963,7 +2989,7 @@ CfkBuild build_cfk(acc_ctx *ctx, const acc_batch_in *in, CfkOpts opts)
     cb.cols.bc_pm_in = ctx->get<uint64_t>("v2_bc_pm_in", P);
     cb.cols.bc_key = cb.bc_side ? nullptr : ctx->get<uint64_t>("v2_bc_key", P);
     // the count / mark passes' accumulators, zeroed by the column kernels (txn records, k_v2_apply); bigflag above
-    cb.tot = ctx->get<uint64_t>("v3_tot", 4);   // E, big txns, a 9-16-key big txn, stream txns with a run record
+    cb.tot = ctx->get<uint64_t>("v3_tot", 4);   // E, stream txns with a run record << 32 | big txns, a 9-16-key big txn
     cb.gstat = ctx->get<uint64_t>("v2_gstat", GSTAT_N + 6);   // + the batch totals and E / big counts (k_v3_ucompact)
     build_columns(ctx, cb, ps, ps.tinfo_done, overlap);
     if (cb.dict.ties_pending && ctx->pinned[6]) {
@@ -3102,7 +3128,6 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     vv.irec32 = reinterpret_cast<const uint32_t *>(ro.irec);
     vv.rec = ro.rec;
 
-    uint32_t *bpos = ctx->get<uint32_t>("v3_bpos", n);
     uint64_t *blk_e = ctx->get<uint64_t>("v3_blk_e", gP);
     uint32_t *psz = ctx->get<uint32_t>("v3_psz", P);   // the big txns' per-pair entry counts (mark pass -> bigfill)
 #ifdef ACC_PHASE_PROF
@@ -3134,37 +3159,87 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
     uint64_t *arena_off = ctx->get<uint64_t>("arena_off", (size_t)n + 1);
     uint64_t *szA = ctx->get<uint64_t>("v3_szA", n), *szK = ctx->get<uint64_t>("v3_szK", n);
     uint64_t *eb = ctx->get<uint64_t>("v3_eb", n), *dB = ctx->get<uint64_t>("v3_dB", (size_t)n + 1);
-    uint32_t *runflag = ctx->get<uint32_t>("v3_runflag", n);
+    // the two list flags of a txn as one word: its halves are the big txns' and the run-record stream txns' counts, each
+    // below 2^30, so the sum stays below the scan's 2^62
+    if (n >= (1u << 30)) fail(ACC_E_CAP, "n_txn must be < 2^30 (list flags scanned as one word)");
+    uint64_t *flagw = ctx->get<uint64_t>("v3_flagw", n), *fpos = ctx->get<uint64_t>("v3_fpos", n);
     launch(ctx, "v3_mark", k_v3_mark, dim3(grid_for((size_t)n * MK_G, BLOCK)), dim3(BLOCK), 0, n, key_off,
-           (const uint32_t *)ro.irec, (const uint4 *)rec, psz, raw_cap, bigflag, szA, szK, tot + 2, eb, runflag);
+           (const uint32_t *)ro.irec, (const uint4 *)rec, psz, raw_cap, bigflag, szA, szK, tot + 2, eb, flagw);
     uint64_t *blk_pre = ctx->get<uint64_t>("v3_blk_pre", gP);
-    {   // arena / key offsets, the count pass's per-block entry totals, the big txns' TxnId scratch bases: one launch
-        const uint64_t *si[4] = { szA, szK, blk_e, eb };
-        uint64_t *so[4] = { arena_off, kd_off, blk_pre, dB }, *stot[4] = { arena_off + n, kd_off + n, tot, dB + n };
-        const size_t sn[4] = { n, n, gP, n };
-        scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 4, si, so, sn, true, stot);
+    {   // arena / key offsets, the count pass's per-block entry totals, the big txns' TxnId scratch bases, the places in
+        // the two txn lists: one launch. tot[1] = stream txns with a run record << 32 | big txns
+        const uint64_t *si[5] = { szA, szK, blk_e, eb, flagw };
+        uint64_t *so[5] = { arena_off, kd_off, blk_pre, dB, fpos };
+        uint64_t *stot[5] = { arena_off + n, kd_off + n, tot, dB + n, tot + 1 };
+        const size_t sn[5] = { n, n, gP, n, n };
+        scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 5, si, so, sn, true, stot);
     }
     // the big-txn list in txn order (k_v3_bigfill's per-txn ranges abut: a big txn writes its end where the next
-    // txn's first pair starts, equal values when the next txn is big too)
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, bigflag, bpos, n, true, reinterpret_cast<uint32_t *>(tot + 1));
-    uint32_t *blist = ctx->get<uint32_t>("v3_blist", n);
-    launch(ctx, "v3_compact", k_v3_compact, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)bigflag,
-           (const uint32_t *)bpos, blist);
-    // the stream txns with a run record, for the RUNS stream pass
-    uint32_t *rpos = ctx->get<uint32_t>("v3_rpos", n), *rlist = ctx->get<uint32_t>("v3_rlist", n);
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, runflag, rpos, n, true, reinterpret_cast<uint32_t *>(tot + 3));
-    launch(ctx, "v3_compact", k_v3_compact, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint32_t *)runflag,
-           (const uint32_t *)rpos, rlist);
-    // ---- E (dependency entries), the big-txn count and the 9-16-key flag reach the host here
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, tot, 4 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t E = ctx->pinned[0];
-    const uint32_t nbig = (uint32_t)ctx->pinned[1];
-    const bool any16 = ctx->pinned[2] != 0;
-    const uint32_t nrun = (uint32_t)ctx->pinned[3];
-    if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 dependency entries in one batch");
+    // txn's first pair starts, equal values when the next txn is big too), and the stream txns with a run record, for
+    // the RUNS stream pass
+    uint32_t *blist = ctx->get<uint32_t>("v3_blist", n), *rlist = ctx->get<uint32_t>("v3_rlist", n);
+    launch(ctx, "v3_lists", k_v3_lists, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, (const uint64_t *)flagw,
+           (const uint64_t *)fpos, blist, rlist);
+    // ---- E (dependency entries), the two list lengths and the 9-16-key flag reach the host here
+    ACC_HIP(hipMemcpyAsync(ctx->pinned, tot, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    ctx->read_mark();
+    // The lean stream pass needs nothing of that read-back: its grid follows from n, its inputs are the size scan's
+    // offsets, bigflag and the records. Only the arena's size, P + E, is not known yet. So where the context holds an
+    // arena already, a leading share of the pass (ACC_AHEAD_DIV) is enqueued here, behind the copy, and runs while the
+    // host waits for the sizes and enqueues the side-stream kernels; it reads E from tot[0] itself and leaves without a
+    // store when P + E is beyond what the buffer holds (the host sees the same E below, grows the buffer and runs the
+    // whole pass in its old place). The rest of the pass follows in its old place, behind the side-stream launches.
+    const uint64_t arena_cap = ctx->buf_cap("arena") / sizeof(int32_t);
+    bool ahead = arena_cap != 0 && !(ctx->flags & ACC_OPT_KD_NO_STREAM_AHEAD);
+#ifdef ACC_PHASE_PROF
+    ahead = false;   // the tuning build reads each pass's counter rows back behind it: the old order
+#endif
     uint64_t *u_off = ctx->get<uint64_t>("u_off", (size_t)n + 1);
     uint64_t *u_cnt = ctx->get<uint64_t>("u_cnt", n);
+    uint32_t *dep_st = ctx->get<uint32_t>("v3_dep_stream", (size_t)n * ST_SLOT);   // stream txns' TxnIds, slot t * ST_SLOT
+    uint32_t *const key_idx = ctx->get<uint32_t>("key_idx", P);
+    // ---- stream pass: the stream txns' KeyDeps (a grid over every txn, 16 lanes per txn), TxnIds to scratch;
+    // 256-thread workgroups co-schedule best with the 512-thread block tier
+    constexpr int st_nt = 256;
+    const uint32_t tt = (uint32_t)st_nt / ST_G;
+    const uint32_t nblocks = (n + tt - 1) / tt;
+    const uint32_t ntiles = nblocks * (uint32_t)(st_nt / 64);   // waves (phase-profile rows)
+    V3Stream sp;
+    sp.v = vv; sp.err = gstat + 5;
+    sp.key_off = key_off; sp.bigflag = bigflag; sp.list = nullptr; sp.txn_of_rank = txn_of_rank;
+    sp.rec = rec; sp.irec = ro.irec;
+    sp.arena_off = arena_off; sp.kd_off = kd_off; sp.u_cnt_out = u_cnt; sp.arena = nullptr; sp.key_idx = key_idx;
+    sp.dep_scr = dep_st; sp.t0 = 0; sp.n = n; sp.ntiles = ntiles;
+    sp.e_dev = nullptr; sp.pairs = P; sp.arena_cap = arena_cap;
+    // the lean pass over the txns [t0, t0 + cnt), t0 a multiple of the tile
+    auto lean_pass = [&](uint32_t t0, uint32_t cnt) {
+        V3Stream a = sp;
+        a.t0 = t0; a.n = cnt;
+        const uint32_t nb = (cnt + tt - 1) / tt;
+        if (rbits <= 28) launch(ctx, "v3_stream", k_v3_stream<uint32_t, st_nt, ST_G, ST_N2, false, false>, dim3(nb), dim3(st_nt), 0, a);
+        else launch(ctx, "v3_stream", k_v3_stream<uint64_t, st_nt, ST_G, ST_N2, false, false>, dim3(nb), dim3(st_nt), 0, a);
+    };
+    const uint32_t n_ahead = ahead ? n / ACC_AHEAD_DIV / tt * tt : 0u;
+    if (ahead) {
+        sp.arena = static_cast<int32_t *>(const_cast<void *>(ctx->buf_ptr("arena")));
+        sp.e_dev = tot;
+        lean_pass(0, n_ahead);
+    }
+    ctx->read_wait();
+    const uint64_t E = ctx->pinned[0];
+    const uint32_t nbig = (uint32_t)(ctx->pinned[1] & 0xFFFFFFFFu);
+    const uint32_t nrun = (uint32_t)(ctx->pinned[1] >> 32);
+    const bool any16 = ctx->pinned[2] != 0;
+    if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 dependency entries in one batch");
+    const bool redo = ahead && P + E > arena_cap;
+    if (redo) {
+        // the guard tripped: no wave of the pass stored anything. The stream is drained before the arena is replaced,
+        // and every pointer to it is taken again below.
+        ctx->sync();
+        ahead = false;
+    }
+    ctx->stat("keydeps.stream_ahead", ahead ? 1 : 0);
+    ctx->stat("keydeps.stream_ahead_redo", redo ? 1 : 0);
     uint64_t *vdep_off = nullptr;
     uint32_t *dep_scr = nullptr;
     uint64_t nfb = 0, efb = 0, nmed = 0, nbig2 = 0;
@@ -3190,9 +3265,8 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
         launch(ctx, "v2_write_huge", k_v2_write_big<HUGE_E, 1024>, tier_grid(nbig, 64), dim3(1024), 0,
                (const uint32_t *)wo.huge_list, vv, (const uint64_t *)vcnt, wo);
     };
-    uint32_t *dep_st = ctx->get<uint32_t>("v3_dep_stream", (size_t)n * ST_SLOT);   // stream txns' TxnIds, slot t * ST_SLOT
-    int32_t *const arena = ctx->get<int32_t>("arena", P + E);
-    uint32_t *const key_idx = ctx->get<uint32_t>("key_idx", P);
+    int32_t *const arena = ctx->get<int32_t>("arena", P + E);   // (ahead: it fits, the buffer the lean pass writes)
+    sp.arena = arena; sp.e_dev = nullptr;
     uint32_t *const dep_txn = ctx->get<uint32_t>("dep_txn", std::max<uint64_t>(E, 1));
     // ---- big txns' arena / keys into place, TxnId offsets and compaction. With global-path txns (known only after
     // the tiers ran) this is redone once they are written, so the common case pays one host sync here.
@@ -3217,6 +3291,11 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
         ACC_HIP(hipMemcpyAsync(ctx->pinned, gstat, (GSTAT_N + 6) * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         ctx->sync();
     };
+    // Side streams: aux[0] the big txns' tiers, aux[1] the RUNS stream pass. With the lean pass ahead they rest on the
+    // read-back's event, not on the context stream's tail (fork would queue them behind the lean pass), and routing and
+    // bigfill go to aux[0] too.
+    const int nside = nrun ? 2 : nbig ? 1 : 0;
+    if (ahead) ctx->fork_at_read(nside);
     // ---- big txns: v2 tiers, headers / key indices / entries into the final arrays, TxnIds into scratch
     if (nbig) {
         const unsigned gB = (nbig + WAVES - 1) / WAVES;
@@ -3232,17 +3311,26 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
         bg.vdep_off = vdep_off; bg.vcnt = vcnt; bg.vcnz = vcnz; bg.u_cnt = u_cnt; bg.arena = arena; bg.key_idx = key_idx;
         const bool big_ok = rbits + 6 <= 31;
         win_ok = big_ok && !(ctx->flags & ACC_OPT_NO_WINDOW_TIER);   // (testing: the sorting tiers instead)
+        if (ahead) ctx->launch_stream = ctx->aux[0];
         launch(ctx, "v3_route", k_v3_route, dim3(grid_for(nbig, BLOCK)), dim3(BLOCK), 0, nbig, (const uint32_t *)blist,
                key_off, (const uint64_t *)eb, (int)big_ok, (int)win_ok, med_list, big_list, fb_list,
                ctx->get<uint32_t>("v2_w8_list", nbig), ctx->get<uint32_t>("v2_w16_list", nbig), gstat);
         launch(ctx, "v3_bigfill", k_v3_bigfill, dim3(gB), dim3(BLOCK), 0, nbig, bg);
+        if (ahead) {
+            // The tier's first kernel is next in its queue behind bigfill; the stream passes become ready at the same
+            // point but across queues, so the tier's blocks are placed first, as they were when the context stream
+            // ran bigfill ahead of the fork (placed behind the stream passes' blocks the tier ran 0.66 against 0.56 ms).
+            ctx->lane_mark();
+            ctx->lane_wait();
+            if (nrun) ACC_HIP(hipStreamWaitEvent(ctx->aux[1], ctx->lane_ev, 0));
+        }
         wo.key_off = key_off; wo.dep_off = vdep_off; wo.arena_off = arena_off; wo.cnz = vcnz; wo.txn_of_rank = txn_of_rank;
         wo.arena = arena; wo.dep_scratch = dep_scr; wo.u_cnt = u_cnt; wo.gstat = gstat;
         wo.rec = rec; wo.irec32 = vv.irec32; wo.med_list = med_list; wo.big_list = big_list; wo.fb_list = fb_list;
         wo.huge_list = ctx->get<uint32_t>("v2_huge_list", nbig);
         // persistent grids over device-side list counts (routing happened after the last host sync); the tiers run on a
-        // side stream, concurrently with the stream pass (it needs only the big txns' sizes, set by bigfill)
-        ctx->fork(nrun ? 2 : 1);
+        // side stream, concurrently with the stream passes
+        if (!ahead) ctx->fork(nside);
         ctx->launch_stream = ctx->aux[0];
         if (win_ok) {
 #ifdef ACC_PHASE_PROF
@@ -3268,18 +3356,7 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
         ctx->launch_stream = nullptr;
     }
     {
-        // ---- stream pass: the stream txns' KeyDeps (a grid over every txn, 16 lanes per txn), TxnIds to scratch;
-        // 256-thread workgroups co-schedule best with the 512-thread block tier
-        constexpr int st_nt = 256;
-        const uint32_t tt = (uint32_t)st_nt / ST_G;
-        const uint32_t nblocks = (n + tt - 1) / tt;
-        const uint32_t ntiles = nblocks * (uint32_t)(st_nt / 64);   // waves (phase-profile rows)
-        V3Stream sp;
-        sp.v = vv; sp.err = gstat + 5;
-        sp.key_off = key_off; sp.bigflag = bigflag; sp.list = nullptr; sp.txn_of_rank = txn_of_rank;
-        sp.rec = rec; sp.irec = ro.irec;
-        sp.arena_off = arena_off; sp.kd_off = kd_off; sp.u_cnt_out = u_cnt; sp.arena = arena; sp.key_idx = key_idx;
-        sp.dep_scr = dep_st; sp.n = n; sp.ntiles = ntiles;
+        // ---- the stream passes (sp above)
 #ifdef ACC_PHASE_PROF
         const size_t prof_rows = (size_t)ntiles;
         unsigned long long *prof_buf = prof_arm(ctx, "v3_prof", HIP_SYMBOL(g_st_prof), 8 * prof_rows, st);
@@ -3288,7 +3365,7 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
             // the stream txns with a run record on side stream 1, concurrently with the lean pass below (their gathers
             // kept out of the lean pass: registers and a wave-uniform loop in every wave that holds one; config 2: 25%
             // of the txns)
-            if (!nbig) ctx->fork(2);
+            if (!nbig && !ahead) ctx->fork(2);
             V3Stream sr = sp;
             sr.list = rlist; sr.n = nrun;
             const uint32_t rblocks = (nrun + tt - 1) / tt;
@@ -3301,8 +3378,8 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
             else launch(ctx, "v3_stream_runs", k_v3_stream<uint64_t, st_nt, ST_G, ST_N2, true, true>, dim3(rblocks), dim3(st_nt), 0, sr);
             ctx->launch_stream = nullptr;
         }
-        if (rbits <= 28) launch(ctx, "v3_stream", k_v3_stream<uint32_t, st_nt, ST_G, ST_N2, false, false>, dim3(nblocks), dim3(st_nt), 0, sp);
-        else launch(ctx, "v3_stream", k_v3_stream<uint64_t, st_nt, ST_G, ST_N2, false, false>, dim3(nblocks), dim3(st_nt), 0, sp);
+        // (ahead: the txns below n_ahead have been running since the size read-back was enqueued)
+        lean_pass(ahead ? n_ahead : 0u, ahead ? n - n_ahead : n);
 #ifdef ACC_PHASE_PROF
         {
             const std::vector<unsigned long long> h = prof_read(prof_buf, 8 * prof_rows, st);
@@ -3319,7 +3396,7 @@ static void keydeps_runs(acc_ctx *ctx, CfkBuild &cb, acc_keydeps_view *view)
         }
 #endif
     }
-    if (nbig || nrun) ctx->join(nrun ? 2 : 1);
+    if (nside) ctx->join(nside);
 #ifdef ACC_PHASE_PROF
     if (nbig && win_ok) {
         const std::vector<unsigned long long> h = prof_read(win_buf, 10, st);

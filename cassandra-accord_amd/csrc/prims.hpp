@@ -229,7 +229,7 @@ __device__ __forceinline__ uint64_t scan_status_load(const uint64_t *p)
 
 // Up to SCAN_MAXA independent arrays per launch (one launch instead of one per array): tickets run over the arrays'
 // tiles in order, so every tile's look-back finds only tiles of its own array that took lower tickets.
-constexpr int SCAN_MAXA = 4;
+constexpr int SCAN_MAXA = 5;
 template <class T>
 struct ScanArgs {
     const T *in[SCAN_MAXA];

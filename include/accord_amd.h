@@ -123,6 +123,8 @@ typedef struct acc_rlist {
 #define ACC_OPT_TIER_GRID(n) ((uint32_t)(n) << ACC_OPT_TIER_GRID_SHIFT)
 #define ACC_OPT_PD_SERIAL 0x10u      /* acc_partial_deps_batch: both halves in order on this context (one buffer set:
                                         less device memory, no overlap) */
+#define ACC_OPT_KD_NO_STREAM_AHEAD 0x20u /* KeyDeps: the lean stream pass behind the size read-back, with the other write
+                                            kernels, never ahead of it (testing) */
 
 /* levelise walk (acc_opts.lv_tier); AUTO picks the whole-graph LDS walk up to 65,535 txns, the windowed walk beyond */
 #define ACC_LV_AUTO     0u
