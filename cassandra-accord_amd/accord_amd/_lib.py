@@ -51,7 +51,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_deps_from_json", "acc_deps_to_json",
            "acc_cfk_create", "acc_cfk_destroy", "acc_cfk_update", "acc_cfk_view", "acc_cfk_apply", "acc_cfk_snap_to_batch",
            "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed",
-           "acc_cfk_map_reduce_full", "acc_max_conflicts",
+           "acc_cfk_map_reduce_full", "acc_cfk_redundant_before", "acc_cfk_redundant_view", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
@@ -316,6 +316,16 @@ class CfkRecoveryIn(C.Structure):
                 ("test_status", C.c_uint8), ("flags", C.c_uint8), ("test_kinds", C.c_int32)]
 
 
+class CfkRedundantIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_ranges", C.c_uint32), ("end_inclusive", C.c_uint32),
+                ("rng_start", C.c_void_p), ("rng_end", C.c_void_p), ("bound", TsCols)]
+
+
+class CfkRedundantMap(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("end_inclusive", C.c_uint32), ("st", C.c_void_p), ("en", C.c_void_p),
+                ("bound", TsCols)]
+
+
 ACC_RCMD_ERASED = 1
 
 
@@ -554,6 +564,10 @@ def load():
         L.acc_cfk_keydeps_mixed.restype = C.c_int
         L.acc_cfk_map_reduce_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRecoveryIn), C.POINTER(KeydepsView)]
         L.acc_cfk_map_reduce_full.restype = C.c_int
+        L.acc_cfk_redundant_before.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantIn)]
+        L.acc_cfk_redundant_before.restype = C.c_int
+        L.acc_cfk_redundant_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantMap)]
+        L.acc_cfk_redundant_view.restype = C.c_int
         L.acc_maxconflicts_create.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]
         L.acc_maxconflicts_create.restype = C.c_int
         L.acc_maxconflicts_destroy.argtypes = [C.c_void_p]

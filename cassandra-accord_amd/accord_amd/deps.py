@@ -1143,6 +1143,32 @@ class CfkStore:
         self.ctx.check(self.ctx._lib.acc_cfk_map_reduce_full(self.ctx.handle, self._h, C.byref(ri), C.byref(view)))
         return self.ctx.copy_out(view, None)
 
+    def redundant_before(self, ranges: dict, end_inclusive: int = 1):
+        """Advance the store's RedundantBefore (acc_cfk_redundant_before; CommandsForKey.withRedundantBefore,
+        local/CommandsForKey.java:1654-1684): ranges = dict(rng_start, rng_end: sorted, non-overlapping, start < end;
+        msb, lsb, node: the shardRedundantBefore TxnId of each range), (s, e] when end_inclusive else [s, e). The map
+        takes the pointwise max; every stored key whose bound rose drops its entries below the bound and trims the
+        missing[] of the rest; the view and the missing[] indices are rebuilt. Later apply_deps calls ignore deps below
+        a key's bound."""
+        a = dict(rs=np.ascontiguousarray(ranges["rng_start"], dtype=np.uint64),
+                 re=np.ascontiguousarray(ranges["rng_end"], dtype=np.uint64),
+                 bm=np.ascontiguousarray(ranges["msb"], dtype=np.uint64), bl=np.ascontiguousarray(ranges["lsb"], dtype=np.uint64),
+                 bn=np.ascontiguousarray(ranges["node"], dtype=np.int32))
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ri = L.CfkRedundantIn(L.ACC_MEM_HOST, len(a["rs"]), int(end_inclusive), p("rs"), p("re"),
+                              L.TsCols(p("bm"), p("bl"), p("bn")))
+        self.ctx.check(self.ctx._lib.acc_cfk_redundant_before(self.ctx.handle, self._h, C.byref(ri)))
+
+    def redundant_map(self) -> dict:
+        """Host copy of the store's RedundantBefore map (acc_cfk_redundant_view): dict(end_inclusive; st, en: closed
+        intervals over the key codes, ascending and disjoint; msb, lsb, node: each interval's shardRedundantBefore)."""
+        m = L.CfkRedundantMap()
+        self.ctx.check(self.ctx._lib.acc_cfk_redundant_view(self.ctx.handle, self._h, C.byref(m)))
+        n = int(m.n)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, n, dt)  # noqa: E731
+        return dict(end_inclusive=int(m.end_inclusive), st=g(m.st, np.uint64), en=g(m.en, np.uint64),
+                    msb=g(m.bound.msb, np.uint64), lsb=g(m.bound.lsb, np.uint64), node=g(m.bound.node, np.int32))
+
     def missing_view(self) -> "L.CfkBatchView":
         """The store's txn-major view with each pair's missing[] as txn indices (device), for cfk_map_reduce_full."""
         bv = L.CfkBatchView()
@@ -1440,6 +1466,11 @@ class ReplicaStore:
             r = self.rcmd.map_reduce_full(queries, sa, td, ts, executes_after=after)
             out[name] = np.diff(np.asarray(r.u_off).astype(np.int64)) > 0 if name.startswith("has_") else r
         return out
+
+    def mark_shard_redundant(self, ranges: dict):
+        """CommandStore.setRedundantBefore / markShardDurable for this store's CommandsForKey: ranges as
+        CfkStore.redundant_before takes them, with the store's Range bound type."""
+        self.cfk.redundant_before(ranges, self.end_inclusive)
 
     def close(self):
         self.cfk.close()

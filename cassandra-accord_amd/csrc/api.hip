@@ -36,6 +36,8 @@ void mc_get(acc_ctx *ctx, const acc_maxconflicts *m, const acc_preaccept_in *q, 
 void cfk_view(acc_cfk *cfk, acc_batch_in *out);
 void cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *up);
 void cfk_state(acc_cfk *cfk, acc_cfk_snap *out);
+void cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant_in *in);
+void cfk_redundant_view(acc_cfk *cfk, acc_cfk_redundant_map *out);
 void cfk_missing(acc_cfk *cfk, acc_cfk_batch_view *out);
 void cfk_free(acc_cfk *cfk);
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
@@ -301,6 +303,21 @@ int acc_cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *update
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_apply_deps(ctx, cfk, updates);
     });
+}
+
+int acc_cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant_in *in)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_redundant_before(ctx, cfk, in);
+    });
+}
+
+int acc_cfk_redundant_view(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_redundant_map *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] { acc::cfk_redundant_view(cfk, out); });
 }
 
 int acc_cfk_state(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_snap *out)

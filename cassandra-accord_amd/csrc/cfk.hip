@@ -15,6 +15,7 @@
 //   4. key offsets by one scan, then every column is written once into the other buffer set, and the sets swap.
 #include "dict.hpp"
 #include "cfkquery.hpp"
+#include "cfkredundant.hpp"
 
 struct acc_cfk {
     int device = 0;
@@ -49,6 +50,9 @@ struct acc_cfk {
     uint32_t *bmiss_off = nullptr, *bmiss_txn = nullptr;   // [P + 1], [bnm]
     uint64_t bnm = 0;
     size_t bytes_bmo = 0, bytes_bmt = 0;
+    // acc_cfk_redundant_before: the store's RedundantBefore map (key code -> shardRedundantBefore), created by the first
+    // call, which also fixes its Range bound type
+    acc_maxconflicts *rb = nullptr;
 };
 
 namespace acc {
@@ -381,6 +385,7 @@ void cfk_free(acc_cfk *cfk)
                      (void *)k.en, (void *)k.xn, (void *)k.mn, (void *)k.st, (void *)k.ent_off, (void *)k.miss_off,
                      (void *)cfk->bmiss_off, (void *)cfk->bmiss_txn })
         (void)hipFree(p);
+    mc_free(cfk->rb);
     delete cfk;
 }
 
@@ -397,44 +402,12 @@ acc_cfk_snap km_snap(acc_cfk *cfk)
                          acc_ts_cols{ k.xm, k.xl, k.xn }, k.st, k.miss_off, acc_ts_cols{ k.mm, k.ml, k.mn } };
 }
 
-}  // namespace
-
-// CommandsForKey.update with the command's deps on the store itself (local/CommandsForKey.java:657-1149 per key, as
-// SafeCommandStore.updateCommandsForKey calls it, local/SafeCommandStore.java:217-240): acc_cfk_apply over the store's
-// key-major state, then the txn-major view and its per-pair missing[] indices rebuilt from the result
-// (acc_cfk_snap_to_batch), both copied into the store only when both succeeded — a rejected batch (stale status, bad
-// offsets, a TxnId whose keys disagree on its status) leaves the store as it was.
-void cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *up)
+// A call's results become the store's arrays: the context's result buffers (acc_cfk_apply's or the prune's cd_o*,
+// acc_cfk_snap_to_batch's cb_*) and the store's previous arrays trade places (no copies; the context writes its next
+// results into the old arrays). Used by acc_cfk_apply_deps and acc_cfk_redundant_before.
+void adopt_result(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_snap_view &v, const acc_cfk_batch_view &bv)
 {
-    if (!cfk || !up) fail(ACC_E_ARG, "null argument");
-    if (!cfk->deps && cfk->n)
-        fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): missing[] is maintained from an empty store");
     acc_cfk::KeyMajor &k = cfk->km;
-    if (!k.ent_off) {   // empty state: offsets [0]
-        realloc_dev(k.ent_off, 1);
-        realloc_dev(k.miss_off, 1);
-        k.bytes[1] = k.bytes[9] = 4;
-        ACC_HIP(hipMemsetAsync(k.ent_off, 0, 4, ctx->stream));
-        ACC_HIP(hipMemsetAsync(k.miss_off, 0, 4, ctx->stream));
-    }
-    const acc_cfk_snap prev = km_snap(cfk);
-    acc_cfk_snap_view v{};
-    // stream time of the two halves (stats cfk.apply_us / cfk.view_us: the steady-state bench's view step)
-    hipEvent_t ev[3] = { ctx->take_event(), ctx->take_event(), ctx->take_event() };
-    struct Give {
-        acc_ctx *c; hipEvent_t *e;
-        ~Give() { for (int i = 0; i < 3; ++i) c->event_pool.push_back(e[i]); }
-    } give{ ctx, ev };
-    ACC_HIP(hipEventRecord(ev[0], ctx->stream));
-    cfk_apply(ctx, &prev, up, &v);
-    ACC_HIP(hipEventRecord(ev[1], ctx->stream));
-    const acc_cfk_snap next{ ACC_MEM_DEVICE, v.n_keys, v.n_entries, v.n_missing, v.key, v.ent_off, v.txn_id, v.execute_at,
-                             v.status, v.miss_off, v.missing };
-    acc_cfk_batch_view bv{};
-    cfk_snap_to_batch(ctx, &next, &bv, true);
-    ACC_HIP(hipEventRecord(ev[2], ctx->stream));
-    // ---- both results become the store's arrays: the context's result buffers and the store's previous arrays trade
-    // places (no copies; the context writes its next results into the old arrays)
     auto adopt = [&](const char *name, auto *&p, size_t &bytes) {
         void *v = p;
         ctx->swap_buf(name, v, bytes);
@@ -468,15 +441,132 @@ void cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *up)
     adopt("cb_mo", cfk->bmiss_off, cfk->bytes_bmo);
     adopt("cb_mt", cfk->bmiss_txn, cfk->bytes_bmt);
     cfk->bnm = bv.n_missing;
+    cfk->n = n;
+    cfk->P = P;
+}
+
+}  // namespace
+
+// CommandsForKey.update with the command's deps on the store itself (local/CommandsForKey.java:657-1149 per key, as
+// SafeCommandStore.updateCommandsForKey calls it, local/SafeCommandStore.java:217-240): acc_cfk_apply over the store's
+// key-major state, then the txn-major view and its per-pair missing[] indices rebuilt from the result
+// (acc_cfk_snap_to_batch), both copied into the store only when both succeeded — a rejected batch (stale status, bad
+// offsets, a TxnId whose keys disagree on its status) leaves the store as it was.
+void cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *up)
+{
+    if (!cfk || !up) fail(ACC_E_ARG, "null argument");
+    if (!cfk->deps && cfk->n)
+        fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): missing[] is maintained from an empty store");
+    acc_cfk::KeyMajor &k = cfk->km;
+    if (!k.ent_off) {   // empty state: offsets [0]
+        realloc_dev(k.ent_off, 1);
+        realloc_dev(k.miss_off, 1);
+        k.bytes[1] = k.bytes[9] = 4;
+        ACC_HIP(hipMemsetAsync(k.ent_off, 0, 4, ctx->stream));
+        ACC_HIP(hipMemsetAsync(k.miss_off, 0, 4, ctx->stream));
+    }
+    const acc_cfk_snap prev = km_snap(cfk);
+    acc_cfk_snap_view v{};
+    // stream time of the two halves (stats cfk.apply_us / cfk.view_us: the steady-state bench's view step)
+    hipEvent_t ev[3] = { ctx->take_event(), ctx->take_event(), ctx->take_event() };
+    struct Give {
+        acc_ctx *c; hipEvent_t *e;
+        ~Give() { for (int i = 0; i < 3; ++i) c->event_pool.push_back(e[i]); }
+    } give{ ctx, ev };
+    ACC_HIP(hipEventRecord(ev[0], ctx->stream));
+    // deps below a key's shardRedundantBefore take no part in the update (:1088-1089): with a non-empty map they are
+    // compacted away on the device first, and acc_cfk_apply sees the rest
+    acc_cfk_updates trimmed{};
+    uint64_t ntrim = 0;
+    if (cfk->rb && cfk->rb->nv) {
+        ntrim = rb_trim_deps(ctx, cfk->rb, up, &trimmed);
+        up = &trimmed;
+    }
+    cfk_apply(ctx, &prev, up, &v);
+    ACC_HIP(hipEventRecord(ev[1], ctx->stream));
+    const acc_cfk_snap next{ ACC_MEM_DEVICE, v.n_keys, v.n_entries, v.n_missing, v.key, v.ent_off, v.txn_id, v.execute_at,
+                             v.status, v.miss_off, v.missing };
+    acc_cfk_batch_view bv{};
+    cfk_snap_to_batch(ctx, &next, &bv, true);
+    ACC_HIP(hipEventRecord(ev[2], ctx->stream));
+    adopt_result(ctx, cfk, v, bv);
     ctx->sync();
     float ms_a = 0, ms_v = 0;
     ACC_HIP(hipEventElapsedTime(&ms_a, ev[0], ev[1]));
     ACC_HIP(hipEventElapsedTime(&ms_v, ev[1], ev[2]));
     ctx->stat("cfk.apply_us", (uint64_t)(ms_a * 1000.0f));
     ctx->stat("cfk.view_us", (uint64_t)(ms_v * 1000.0f));
-    cfk->n = n;
-    cfk->P = P;
+    ctx->stat("cfk.deps_trimmed", ntrim);
     cfk->deps = true;
+}
+
+// RedundantBefore.merge of the input into the store's map, then CommandsForKey.withRedundantBefore
+// (local/CommandsForKey.java:1654-1684) on every stored key whose shardRedundantBefore rose, as
+// SafeCommandStore.maybeTruncate does on access (local/SafeCommandStore.java:158-164); the txn-major view and the
+// per-pair missing[] indices rebuilt from the result as acc_cfk_apply_deps rebuilds them.
+void cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant_in *in)
+{
+    if (!cfk || !in) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
+    if (cfk->rb && cfk->rb->end_inclusive != in->end_inclusive)
+        fail(ACC_E_ARG, "end_inclusive differs from the store's RedundantBefore map's");
+    if (!cfk->deps && cfk->n)
+        fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): there is no key-major state to prune");
+    for (const char *z : { "cfk.redundant_keys_advanced", "cfk.redundant_entries_dropped", "cfk.redundant_missing_dropped" })
+        ctx->stat(z, 0);
+    if (in->n_ranges == 0) return;
+    hipEvent_t ev[3] = { ctx->take_event(), ctx->take_event(), ctx->take_event() };
+    struct Give {
+        acc_ctx *c; hipEvent_t *e;
+        ~Give() { for (int i = 0; i < 3; ++i) c->event_pool.push_back(e[i]); }
+    } give{ ctx, ev };
+    const acc_cfk::KeyMajor &k = cfk->km;
+    CfkResident s = cfk_resident(cfk);
+    if (!cfk->deps) s.nk = 0;
+    // a first call whose ranges are rejected leaves the store without a map
+    acc_maxconflicts *fresh = cfk->rb ? nullptr : mc_new(cfk->device, in->end_inclusive);
+    try {
+        rb_merge_map(ctx, cfk->rb ? cfk->rb : fresh, in, s);
+    } catch (...) {
+        mc_free(fresh);
+        throw;
+    }
+    if (fresh) cfk->rb = fresh;
+    if (s.nk == 0) return;   // an empty store records the map
+    ACC_HIP(hipEventRecord(ev[0], ctx->stream));
+    acc_cfk_snap_view v{};
+    const RbPruned r = rb_prune(ctx, cfk->rb, s, k.ne, k.nm, &v);
+    ACC_HIP(hipEventRecord(ev[1], ctx->stream));
+    ctx->stat("cfk.redundant_keys_advanced", r.advanced);
+    if (r.advanced == 0) return;   // no stored key's bound rose: no array is rewritten, the views stay valid
+    const uint64_t ne0 = k.ne, nm0 = k.nm;
+    const acc_cfk_snap next{ ACC_MEM_DEVICE, v.n_keys, v.n_entries, v.n_missing, v.key, v.ent_off, v.txn_id, v.execute_at,
+                             v.status, v.miss_off, v.missing };
+    acc_cfk_batch_view bv{};
+    cfk_snap_to_batch(ctx, &next, &bv, true);
+    ACC_HIP(hipEventRecord(ev[2], ctx->stream));
+    adopt_result(ctx, cfk, v, bv);
+    ctx->sync();
+    float ms_p = 0, ms_v = 0;
+    ACC_HIP(hipEventElapsedTime(&ms_p, ev[0], ev[1]));
+    ACC_HIP(hipEventElapsedTime(&ms_v, ev[1], ev[2]));
+    ctx->stat("cfk.redundant_prune_us", (uint64_t)(ms_p * 1000.0f));
+    ctx->stat("cfk.redundant_view_us", (uint64_t)(ms_v * 1000.0f));
+    ctx->stat("cfk.redundant_entries_dropped", ne0 - r.ne);
+    ctx->stat("cfk.redundant_missing_dropped", nm0 - r.nm);
+}
+
+void cfk_redundant_view(acc_cfk *cfk, acc_cfk_redundant_map *out)
+{
+    if (!cfk || !out) fail(ACC_E_ARG, "null argument");
+    *out = acc_cfk_redundant_map{};
+    out->end_inclusive = 1;
+    if (const acc_maxconflicts *m = cfk->rb) {
+        out->n = m->nv; out->end_inclusive = m->end_inclusive;
+        out->st = m->st; out->en = m->en;
+        out->bound = acc_ts_cols{ m->vm, m->vl, m->vn };
+    }
 }
 
 void cfk_state(acc_cfk *cfk, acc_cfk_snap *out)

@@ -20,20 +20,9 @@
 //     part intersects, their max through the block maxima; the wave folds the lanes' maxima under Timestamp.compareTo
 //     and sets the fast-path bit txnId.compareTo(minNonConflicting) >= 0 (CommandStore.preaccept :320-345).
 // acc_max_conflicts (every update and every query of a store in one call) is create + update + get.
-#include "dict.hpp"
+#include "conflicts.hpp"
 
 #include <algorithm>
-
-struct acc_maxconflicts {
-    int device = 0;
-    uint32_t end_inclusive = 1;
-    uint64_t nv = 0, cap = 0;                         // intervals, allocated capacity
-    uint64_t *st = nullptr, *en = nullptr;            // [cap] closed interval bounds
-    uint64_t *vm = nullptr, *vl = nullptr;            // [cap] values (msb, lsb)
-    int32_t *vn = nullptr;                            // [cap] values (node)
-    uint64_t *bm = nullptr, *bl = nullptr;            // [cap / MC_BLK + 1] block maxima
-    int32_t *bn = nullptr;
-};
 
 namespace acc {
 namespace mc {
@@ -42,11 +31,6 @@ constexpr uint32_t MC_BLK = 256;
 constexpr uint64_t MAXC = ~0ull;
 enum : uint64_t { E_OFF = 1, E_SORT = 2, E_RANGE = 4 };
 
-struct Ts {
-    uint64_t m, l;
-    int32_t n;
-};
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
 __device__ __forceinline__ Ts tmax(const Ts &a, const Ts &b) { return cmp(a, b) >= 0 ? a : b; }   // Timestamp.max
 
 struct Upd {
@@ -219,12 +203,6 @@ __global__ __launch_bounds__(BLOCK) void k_mc_blockmax(uint64_t nv, const uint64
     bm[b] = best.m; bl[b] = best.l; bn[b] = best.n;
 }
 
-struct Map {
-    const uint64_t *st, *en, *vm, *vl, *bm, *bl;
-    const int32_t *vn, *bn;
-    uint64_t nv;
-    int ei;
-};
 struct Qs {
     const uint64_t *qm, *ql, *ps, *pe;
     const int32_t *qn;
@@ -236,13 +214,6 @@ struct Qs {
     int32_t *on;
     uint8_t *fast;
 };
-
-__device__ __forceinline__ uint64_t lower64(const uint64_t *a, uint64_t n, uint64_t v)   // first index with a[i] >= v
-{
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
 
 // one wave per query, a lane per part: the intervals [i0, i1] the part's closed interval [a, b] intersects (first with
 // en >= a, last with st <= b), their max through the block maxima
@@ -473,7 +444,7 @@ void mc_get(acc_ctx *ctx, const acc_maxconflicts *M, const acc_preaccept_in *qi,
     q.ol = host_out ? ctx->get<uint64_t>("mc_ol", nq) : out->max_lsb;
     q.on = host_out ? ctx->get<int32_t>("mc_on", nq) : out->max_node;
     q.fast = host_out ? ctx->get<uint8_t>("mc_fast", nq) : out->fast_path;
-    Map mp{ M->st, M->en, M->vm, M->vl, M->bm, M->bl, M->vn, M->bn, M->nv, (int)M->end_inclusive };
+    const Map mp = mc_map(M);
     uint64_t *errs = ctx->get<uint64_t>("mc_errs", 1);
     ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
     launch(ctx, "mc_query", k_mc_query, dim3((nq + WAVES - 1) / WAVES), dim3(BLOCK), 0, q, mp, errs);

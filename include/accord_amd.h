@@ -907,6 +907,54 @@ int  acc_cfk_apply_deps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_updates *updat
 int  acc_cfk_state(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_snap *out);
 int  acc_cfk_missing(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_batch_view *out);
 
+/* RedundantBefore on the resident store: the prune that keeps it a steady-state store. A CommandStore advances its
+ * RedundantBefore as sync points apply (local/RedundantBefore.java: a ReducingRangeMap of Entries merged with max), and
+ * every CommandsForKey follows on its next access (SafeCommandStore.maybeTruncate, local/SafeCommandStore.java:158-164 ->
+ * CommandsForKey.withRedundantBefore, local/CommandsForKey.java:1654-1684). An Entry is modelled by its
+ * shardRedundantBefore alone: the store owns one map RB, key code -> TxnId, all zero (TxnId.NONE) where nothing is set.
+ * acc_cfk_redundant_before first replaces RB by the pointwise Timestamp.compareTo maximum of RB and the input
+ * (RedundantBefore.merge: a lower bound is absorbed, never an error); range j covers the key codes (s, e] with
+ * end_inclusive = 1, [s, e) with 0, and holds bound[j]. Then every stored key k with RB_new(k) > RB_old(k) = b is
+ * pruned: pos = the lower bound of b among the key's TxnIds (insertPos(0, b); an entry whose TxnId compares equal to b
+ * stays), the entries [0, pos) are dropped, and if pos != 0 every surviving entry's missing[] loses its prefix below b
+ * (Arrays.binarySearch(missing, b); an id equal to b stays). A key whose bound did not rise is unchanged even if it
+ * holds entries below its bound (the newRedundantBefore.equals(redundantBefore) early return: update inserts entries
+ * without looking at the bound, and they stay until the bound next rises). A key left without entries leaves the state
+ * (the "keys without entries dropped" convention of acc_cfk_apply). The txn-major view (acc_cfk_view) and the per-pair
+ * missing[] indices (acc_cfk_missing) are rebuilt from the result exactly as acc_cfk_apply_deps rebuilds them, and the
+ * new arrays adopted the same way: a TxnId dropped from all its keys leaves the view, and later dep_txn indices refer to
+ * the new view. If no stored key's bound rises, no array is rewritten and every view stays valid.
+ * Under a non-empty map acc_cfk_apply_deps ignores, per (update, key) pair, the deps below RB(key)
+ * (deps.find(redundantBefore.shardRedundantBefore()), :1088-1089): they create no TRANSITIVELY_KNOWN entries and play
+ * no part in the missing merge. The scans (acc_cfk_keydeps*, acc_cfk_map_reduce_full) do not consult the bound, as in
+ * the reference (:553-650): they read the pruned state.
+ * Errors, store and map unchanged: ranges unsorted, overlapping (rng_end[j-1] > rng_start[j]) or with start >= end,
+ * end_inclusive > 1, end_inclusive differing from an earlier call's: ACC_E_ARG; a non-empty status-only store
+ * (acc_cfk_update): ACC_E_STATE. An empty store records the map, and keys that appear later honour it (maybeTruncate on
+ * a fresh CFK). n_ranges == 0 is a no-op.
+ * Stats: cfk.redundant_keys_advanced, cfk.redundant_entries_dropped, cfk.redundant_missing_dropped; cfk.deps_trimmed
+ * (set by acc_cfk_apply_deps); cfk.redundant_prune_us / cfk.redundant_view_us (stream time of the prune passes and of
+ * the view rebuild).
+ * Out of scope: RedundantBefore.collectDeps (:418-421: the (range, bound) range deps added to PreAccept results), the
+ * locally-redundant, bootstrap and stale fields of an Entry, registerHistorical, and pruning of the range-command store
+ * (its commands leave through ACC_RCMD_ERASED).
+ * acc_cfk_redundant_view describes the map: closed intervals over the key codes, ascending and disjoint (adjacent
+ * intervals with equal bounds are one), with the bound of each. */
+typedef struct acc_cfk_redundant_in {
+    uint32_t mem, n_ranges;          /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint32_t end_inclusive;          /* the store's Range bound type, as acc_cfk_mixed_queries */
+    const uint64_t *rng_start, *rng_end;   /* [n_ranges] sorted, non-overlapping, start < end */
+    acc_ts_cols bound;               /* [n_ranges] shardRedundantBefore (a TxnId) of each range */
+} acc_cfk_redundant_in;
+int  acc_cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant_in *in);
+
+typedef struct acc_cfk_redundant_map {   /* DEVICE pointers, valid until the next acc_cfk_redundant_before */
+    uint64_t n;  uint32_t end_inclusive;
+    const uint64_t *st, *en;         /* closed intervals over the key codes, ascending, disjoint */
+    acc_ts_cols bound;
+} acc_cfk_redundant_map;
+int  acc_cfk_redundant_view(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_redundant_map *out);
+
 /* PreAccept.calculatePartialDeps' key half for a batch of queries against a resident store: query q runs
  * CommandsForKey.mapReduceActive (local/CommandsForKey.java:614-650) on the CFK of each of its keys with
  * startedBefore = execute_at[q], testKind = txn_id[q].kind().witnesses(), and txn_id[q] itself never emitted.
