@@ -1,10 +1,13 @@
 """Properties of the RedundantBefore model (cfk_redundant_model.py) that the GPU tests of acc_cfk_redundant_before rest
 on (no GPU): idempotence, a bound below everything, missing[] closed over the key's entries after a prune, and the
-hand-worked case of CommandsForKey.withRedundantBefore (local/CommandsForKey.java:1654-1684)."""
+hand-worked case of CommandsForKey.withRedundantBefore (local/CommandsForKey.java:1654-1684); and what the case builders
+of cfk_redundant_cases.py must give (sizes past a scan tile, keys that leave, ids equal to a bound, the hand-worked
+order edges), so a parameter set that stops giving it fails here."""
 import numpy as np
 import pytest
 
 import cfk_cases as CC
+import cfk_redundant_cases as RCS
 import cfk_redundant_model as M
 import oracle
 
@@ -91,3 +94,55 @@ def test_trim_deps_keeps_a_dep_equal_to_the_bound():
              for u in range(len(out["msb"])) for j in range(int(out["key_off"][u]), int(out["key_off"][u + 1]))}
     assert pairs[(16, 200)] == [] and pairs[(20, 200)] == [12]
     assert pairs[(16, 100)] == [4] and pairs[(20, 300)] == [4, 12]
+
+
+# ---------------------------------------------------------------- the case builders of cfk_redundant_cases.py
+
+def test_call_map_agrees_with_bound_map():
+    """CallMap (bisection per call) against BoundMap (every update walked): lookups at every range edge and beside it,
+    and the intervals, over two overlapping calls of the scale chain's shape and a call with a tie"""
+    edge = list(range(0, 6001, 10))
+    call = lambda b: M.ranges_of([(edge[r], edge[r + 1], M.ts(4 * (100 * b + r % 7) + 4, node=1 + r % 3))  # noqa: E731
+                                  for r in range(600) if r % 2 == b % 2 or r % 5 == 0])
+    slow, fast = M.BoundMap(1), RCS.CallMap(1)
+    for ranges in (call(0), call(1), M.ranges_of([(95, 205, M.ts(4 * 103 + 4, flags=(1 << 1) | RCS.FLAG, node=1))])):
+        slow.add(ranges)
+        fast.add(ranges)
+        keys = sorted({e + d for e in edge[:80] + edge[-40:] for d in (-1, 0, 1, 2)})
+        assert [fast.get(k) for k in keys] == [slow.get(k) for k in keys]
+        assert fast.copy().intervals() == slow.intervals()
+    assert len(fast.intervals()) > RCS.MC_BLK
+
+
+@pytest.mark.parametrize("dist", ["uniform", "zipf"])
+def test_scale_chain_meets_its_conditions(dist):
+    RCS.scale_conditions(RCS.scale_chain(dist), dist)
+
+
+def test_replica_case_meets_its_conditions():
+    RCS.replica_conditions(RCS.replica_case())
+
+
+def test_order_edges_by_hand():
+    """the hand-written states and counts of cfk_redundant_cases.order_edges are what the model and the C restatement
+    give; the ids are ordered as the comments there say"""
+    I = RCS.EDGE_IDS
+    names = ["P", "N", "Q", "E1", "E2", "T", "U"]
+    assert [M.order(I[a]) < M.order(I[b]) for a, b in zip(names, names[1:])] == [True] * 6
+    assert I["N"][:2] == I["Q"][:2] and (I["N"][2], I["Q"][2]) == (-1, 2)
+    assert I["E1"][1:] == I["E2"][1:] and I["E1"][0] != I["E2"][0]
+    assert RCS.E1F != I["E1"] and M.order(RCS.E1F) == M.order(I["E1"]) and M.order(RCS.QF) == M.order(I["Q"])
+    steps = RCS.order_edges_model()
+    assert [len(st["key"]) for _, _, st, _ in steps] == [3] * 5
+    assert [len(st["status"]) for _, _, st, _ in steps] == [18, 12, 12, 9, 12]
+
+
+def test_small_script_runs_on_the_model():
+    m, state = M.BoundMap(1), CC.empty_snapshot()
+    dropped = trimmed = 0
+    for op, arg in RCS.small_script():
+        step, state = (RCS.apply_step if op == "apply" else RCS.prune_step)(state, m, arg)
+        CC.snap_as_batch(state)
+        dropped += step["counts"]["entries_dropped"] if op == "prune" else 0
+        trimmed += step["trimmed"] if op == "apply" else 0
+    assert dropped > 0 and trimmed > 0 and len(state["key"]) > 0
