@@ -48,6 +48,7 @@
 // Results live in cq_* buffers only: acc_cfk_apply_deps trades the context's cd_* / cb_* buffers with the store.
 #include "keydeps.hpp"
 #include "cfkquery.hpp"
+#include "recovery_pred.hpp"
 
 namespace acc {
 
@@ -726,13 +727,15 @@ struct Located {
     uint64_t *chunks;
     uint8_t *lane;          // null: no lane tier (acc_cfk_keydeps, ACC_CFQ_LANE_NONE)
     uint32_t *lane_w;
+    uint64_t *nlane;        // the lane tier's pairs, counted on the device; null: acc_cfk_keydeps
 };
 
 static Located located_bufs(acc_ctx *ctx, uint32_t Qp, bool lanes)
 {
     return Located{ ctx->get<uint32_t>("cq_pair_q", Qp), ctx->get<uint32_t>("cq_pair_a", Qp), ctx->get<uint32_t>("cq_pair_w", Qp),
                     ctx->get<uint8_t>("cq_pair_t0", Qp), ctx->get<uint64_t>("cq_chunks", Qp),
-                    lanes ? ctx->get<uint8_t>("cq_pair_lane", Qp) : nullptr, lanes ? ctx->get<uint32_t>("cq_lane_w", Qp) : nullptr };
+                    lanes ? ctx->get<uint8_t>("cq_pair_lane", Qp) : nullptr, lanes ? ctx->get<uint32_t>("cq_lane_w", Qp) : nullptr,
+                    nullptr };
 }
 
 static CfkResident resident_checked(acc_cfk *cfk, uint32_t mem)
@@ -776,7 +779,7 @@ static void stage_ids(acc_ctx *ctx, Queries &Q, const acc_ts_cols &txn_id, const
     }
 }
 
-static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view);
+static uint64_t scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view);
 
 // the caller's participants of a call over both domains (acc_cfk_mixed_queries, acc_cfk_recovery_in)
 struct Parts {
@@ -811,9 +814,10 @@ static uint64_t expand_queries(acc_ctx *ctx, const CfkResident &s, Queries &Q, R
     // ---- validate
     ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
     launch(ctx, "cq_rvalidate", k_cq_rvalidate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, kinds, errs);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_cq_errors(ctx->pinned[0]);
+    ReadBack rb_valid(ctx);
+    const auto h_errs = rb_valid.u64(errs);
+    rb_valid.wait();
+    check_cq_errors(h_errs);
 
     // ---- bounds: the store keys every range covers, the expanded pair offsets
     uint32_t *rlo = ctx->get<uint32_t>("cq_rlo", NR);
@@ -831,10 +835,10 @@ static uint64_t expand_queries(acc_ctx *ctx, const CfkResident &s, Queries &Q, R
     uint64_t *xoff64 = ctx->get<uint64_t>("cq_xoff64", (size_t)nq + 1);
     launch(ctx, "cq_rcount", k_cq_rcount, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, R, qcnt);
     scan<uint64_t, OpAdd<uint64_t>>(ctx, qcnt, xoff64, nq, true, xoff64 + nq);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, xoff64 + nq, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, rcum + NR, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t X = ctx->pinned[0], covered = ctx->pinned[1];
+    ReadBack rb_pairs(ctx);
+    const auto h_x = rb_pairs.u64(xoff64 + nq), h_covered = rb_pairs.u64(rcum + NR);
+    rb_pairs.wait();
+    const uint64_t X = h_x, covered = h_covered;
     if (X >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs after expanding the ranges (>= 2^32 - 1)");
     const uint32_t Xp = (uint32_t)X;
     uint32_t *xoff = ctx->get<uint32_t>("cq_xoff", (size_t)nq + 1);
@@ -871,9 +875,10 @@ void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *in, acc_keyd
     uint64_t *errs = ctx->get<uint64_t>("cq_errs", 1);
     ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
     launch(ctx, "cq_validate", k_cq_validate, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, errs);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_cq_errors(ctx->pinned[0]);
+    ReadBack rb_valid(ctx);
+    const auto h_errs = rb_valid.u64(errs);
+    rb_valid.wait();
+    check_cq_errors(h_errs);
 
     // ---- locate: prefixes and chunks
     const Located L = located_bufs(ctx, Qp, false);
@@ -915,26 +920,27 @@ void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *
     // ---- expand: every pair's query, key and segment; the lane tier's pairs
     uint64_t *nlane = ctx->get<uint64_t>("cq_nlane", 1);
     ACC_HIP(hipMemsetAsync(nlane, 0, 8, st));
-    const Located L = located_bufs(ctx, Xp, lane_seg != 0);   // ACC_CFQ_LANE_NONE: every pair takes the chunk path
+    Located L = located_bufs(ctx, Xp, lane_seg != 0);   // ACC_CFQ_LANE_NONE: every pair takes the chunk path
+    L.nlane = nlane;
     if (Xp)
         launch(ctx, "cq_rexpand", k_cq_rexpand, dim3(grid_for(Xp, BLOCK)), dim3(BLOCK), 0, Q, R, s, lane_seg, xkey, L.pair_q, L.pair_a,
                L.pair_w, L.pair_t0, L.chunks, L.lane, L.lane_w, nlane);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 8, nlane, 8, hipMemcpyDeviceToHost, st));   // read at the scan's first sync
-    scan_located(ctx, s, Q, L, errs, view);
+    const uint64_t lane_pairs = scan_located(ctx, s, Q, L, errs, view);
     ctx->stat("cfq.range_pairs", covered);
-    ctx->stat("cfq.lane_pairs", ctx->pinned[8]);
+    ctx->stat("cfq.lane_pairs", lane_pairs);
 }
 
-// The pairs' chunk offsets, the chunk total (the one host read) and the chunk -> pair map
-static uint64_t chunk_layout(acc_ctx *ctx, uint32_t Qp, const uint64_t *chunks, uint64_t *&chunk_off, uint32_t *&chunk_item)
+// The pairs' chunk offsets, the chunk total (the one host read: rb's sync, which completes what the caller queued on rb
+// before) and the chunk -> pair map
+static uint64_t chunk_layout(acc_ctx *ctx, ReadBack &rb, uint32_t Qp, const uint64_t *chunks, uint64_t *&chunk_off, uint32_t *&chunk_item)
 {
     hipStream_t st = ctx->stream;
     chunk_off = ctx->get<uint64_t>("cq_chunk_off", (size_t)Qp + 1);
     if (Qp) scan<uint64_t, OpAdd<uint64_t>>(ctx, chunks, chunk_off, Qp, true, chunk_off + Qp);
     else ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_off + Qp, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t NC = ctx->pinned[0];
+    const auto h_nc = rb.u64(chunk_off + Qp);
+    rb.wait();
+    const uint64_t NC = h_nc;
     if (NC >= (1ull << 33)) fail(ACC_E_CAP, "the queries read too many segment entries in one call (>= 2^41)");
     chunk_item = ctx->get<uint32_t>("cq_chunk_item", NC);
     if (NC) launch(ctx, "cq_items", k_cq_items, dim3(grid_for(Qp, BLOCK)), dim3(BLOCK), 0, Qp, (const uint64_t *)chunk_off, chunk_item);
@@ -983,13 +989,11 @@ static Built build_keydeps(acc_ctx *ctx, const CfkResident &s, const Queries &Q,
     launch(ctx, "cq_qoff", k_cq_qoff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)kpos,
            (const uint64_t *)epos, cap, arena_off, kd_off, gcnt);
     scan<uint64_t, OpAdd<uint64_t>>(ctx, gcnt, goff, nq, true, goff + nq);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, chunk_eoff + NC, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 2, kpos + Qp, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 3, goff + nq, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_cq_errors(ctx->pinned[0]);
-    const uint64_t E = ctx->pinned[1], TK = ctx->pinned[2], G = ctx->pinned[3];
+    ReadBack rb_sizes(ctx);
+    const auto h_errs = rb_sizes.u64(errs), h_e = rb_sizes.u64(chunk_eoff + NC), h_tk = rb_sizes.u64(kpos + Qp), h_g = rb_sizes.u64(goff + nq);
+    rb_sizes.wait();
+    check_cq_errors(h_errs);
+    const uint64_t E = h_e, TK = h_tk, G = h_g;
     if (TK + E >= 0x7FFFFFFFull) fail(ACC_E_CAP, "more than 2^31-1 KeyDeps ints in one call");
 
     // ---- emit
@@ -1030,9 +1034,10 @@ static Built build_keydeps(acc_ctx *ctx, const CfkResident &s, const Queries &Q,
                (const uint32_t *)upos, dep_txn);
         launch(ctx, "cq_uoff", k_cq_uoff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq, Q.off, (const uint64_t *)epos,
                (const uint32_t *)upos, u_off);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, upos + E, 4, hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        TU = ctx->pinned[0] & 0xFFFFFFFFull;
+        ReadBack rb_uniq(ctx);
+        const auto h_tu = rb_uniq.u32(upos + E);
+        rb_uniq.wait();
+        TU = h_tu;
     } else {
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
         ctx->sync();
@@ -1043,14 +1048,19 @@ static Built build_keydeps(acc_ctx *ctx, const CfkResident &s, const Queries &Q,
     return Built{ E, G };
 }
 
-// From the located pairs on: chunk offsets, M and the tie count, the count pass, then emit and KeyDeps.Builder
-static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
+// From the located pairs on: chunk offsets, M and the tie count, the count pass, then emit and KeyDeps.Builder. Returns
+// the lane tier's pairs (L.nlane, read back at the chunk layout's sync).
+static uint64_t scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, const Located &L, uint64_t *errs, acc_keydeps_view *view)
 {
     const uint64_t wl0 = ctx->wave_launches;
     const uint32_t Qp = Q.Qp;
     uint64_t *chunk_off = nullptr;
     uint32_t *chunk_item = nullptr;
-    const uint64_t NC = chunk_layout(ctx, Qp, L.chunks, chunk_off, chunk_item);
+    ReadBack rb_chunks(ctx);
+    ReadBack::Word<uint64_t> h_lane;
+    if (L.nlane) h_lane = rb_chunks.u64(L.nlane);
+    const uint64_t NC = chunk_layout(ctx, rb_chunks, Qp, L.chunks, chunk_off, chunk_item);
+    const uint64_t lane_pairs = h_lane;
     const Pairs P{ L.pair_q, L.pair_a, L.pair_w, chunk_off, chunk_item, Qp };
     const Lanes lanes{ L.lane, L.lane_w };
 
@@ -1076,6 +1086,7 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
     ctx->stat("cfq.hits", b.hits);
     ctx->stat("cfq.sorted_hits", b.sorted_hits);
     ctx->stat("cfq.wave_launches", ctx->wave_launches - wl0);
+    return lane_pairs;
 }
 
 // ================================================================ acc_cfk_map_reduce_full: the recovery scans
@@ -1085,20 +1096,16 @@ static void scan_located(acc_ctx *ctx, const CfkResident &s, const Queries &Q, c
 //   window   per pair: pos = the lower bound of X = testTxnId among the segment's TxnIds, isKnown = the entry there
 //            compares equal to X; the window TestStartedAt admits ([start, pos), [pos, end) or the segment; nothing for
 //            WITH when X is no member), its 256-entry chunks. Every pair takes the chunk path.
-//   count    one wave per chunk, four entries per lane: the per-entry tests, cheapest first (kind, status, hasInfo,
-//            executeAt > X), and only for WITH / WITHOUT entries that passed them the binary search of X in the
-//            entry's missing[] (raw TxnIds, read in place; divergent per lane by nature)
-//   emit     the same walk, compacting in position order; each entry as its store-view index (view_index)
+//   count    one wave per chunk, four entries per lane: the per-entry tests (cfk_entry_passes, recovery_pred.hpp, over
+//            cr::View), cheapest first (status, hasInfo, kind, executeAt > X), and only for WITH / WITHOUT entries that
+//            passed them the binary search of X in the entry's missing[] (raw TxnIds, read in place; divergent per lane
+//            by nature)
+//   emit     the same walk (k_cr_scan<true>), compacting in position order; each entry as its store-view index (view_index)
 //   build    build_keydeps. No M pass and no tie rule.
 
 namespace cr {
 
-struct Params {
-    uint32_t started_at, test_dep, test_status, exec_after;
-    int32_t test_kinds;
-};
-
-__global__ __launch_bounds__(BLOCK) void k_cr_window(Queries Q, Ranges R, CfkResident s, Params p, uint64_t *__restrict__ x_key,
+__global__ __launch_bounds__(BLOCK) void k_cr_window(Queries Q, Ranges R, CfkResident s, RcParams p, uint64_t *__restrict__ x_key,
                                                      uint32_t *__restrict__ pair_q, uint32_t *__restrict__ pair_a,
                                                      uint32_t *__restrict__ pair_w, uint64_t *__restrict__ chunks)
 {
@@ -1139,7 +1146,7 @@ struct Scan {
     int32_t Xn;
 };
 
-__device__ __forceinline__ Scan scan_ctx(uint64_t cw, const Queries &Q, const Pairs &P, const Params &p)
+__device__ __forceinline__ Scan scan_ctx(uint64_t cw, const Queries &Q, const Pairs &P, const RcParams &p)
 {
     Scan c;
     const uint32_t item = P.item[cw];
@@ -1152,73 +1159,72 @@ __device__ __forceinline__ Scan scan_ctx(uint64_t cw, const Queries &Q, const Pa
     return c;
 }
 
-// the per-entry tests of CommandsForKey.mapReduceFull (:577-607) plus the optional executeAt > testTxnId map filter
-__device__ __forceinline__ bool visited(const CfkResident &s, const Params &p, const Scan &c, uint32_t e)
-{
-    // the status byte first: it alone refuses most entries of a steady-state segment, whose TxnId word is then not read
-    const uint32_t st = s.st[e];
-    switch (p.test_status) {
-    case ACC_STATUS_IS_PROPOSED: if (st != ACC_ST_ACCEPTED && st != ACC_ST_COMMITTED) return false; break;
-    case ACC_STATUS_IS_STABLE:   if (st < ACC_ST_STABLE || st >= ACC_ST_INVALID_OR_TRUNCATED) return false; break;
-    default:                     if (st == ACC_ST_TRANSITIVELY_KNOWN) return false; break;
+// one chunk's query against the resident segments, as cfk_entry_passes reads them: the status byte, the TxnId word's
+// kind bits, the raw executeAt and missing[] columns
+struct View {
+    const CfkResident &s;
+    const Scan &c;
+    uint32_t mask;
+    __device__ __forceinline__ uint32_t status(uint32_t e) const { return s.st[e]; }
+    __device__ __forceinline__ uint32_t kind(uint32_t e) const { return (uint32_t)(s.el[e] >> 1) & 7u; }
+    __device__ __forceinline__ bool executes_after_x(uint32_t e) const
+    {
+        return ts_cmp(s.xm[e], s.xl[e], s.xn[e], c.Xm, c.Xl, c.Xn) > 0;
     }
-    const bool dep = p.test_dep != ACC_DEP_ANY;
-    if (dep && (st < ACC_ST_ACCEPTED || st > ACC_ST_APPLIED)) return false;   // !InternalStatus.hasInfo
-    if (!((c.mask >> ((uint32_t)(s.el[e] >> 1) & 7u)) & 1u)) return false;
-    if ((dep || p.exec_after) && ts_cmp(s.xm[e], s.xl[e], s.xn[e], c.Xm, c.Xl, c.Xn) <= 0) return false;
-    if (dep) {
+    __device__ __forceinline__ bool x_in_missing(uint32_t e) const
+    {
         uint32_t lo = s.miss_off[e], hi = s.miss_off[e + 1];
-        bool in_missing = false;
         while (lo < hi) {
             const uint32_t m = (lo + hi) >> 1;
             const int d = ts_cmp(s.mm[m], s.ml[m], s.mn[m], c.Xm, c.Xl, c.Xn);
-            if (d < 0) lo = m + 1; else if (d > 0) hi = m; else { in_missing = true; break; }
+            if (d < 0) lo = m + 1; else if (d > 0) hi = m; else return true;
         }
-        if (in_missing == (p.test_dep == ACC_DEP_WITH)) return false;        // hasAsDep != (testDep == WITH)
+        return false;
     }
-    return true;
-}
+};
 
-__global__ __launch_bounds__(BLOCK) void k_cr_count(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Params p,
-                                                    uint64_t *__restrict__ chunk_cnt)
+// one wave per chunk evaluates the entry predicate. Count: the chunk's matches. Emit: the same walk, compacting in
+// position order, each entry as its store-view index (and its (query, index) key when the query sorts)
+template <bool EMIT>
+__global__ __launch_bounds__(BLOCK) void k_cr_scan(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, RcParams p,
+                                                   uint64_t *__restrict__ chunk_cnt, const uint64_t *__restrict__ chunk_eoff,
+                                                   const uint64_t *__restrict__ epos, const uint64_t *__restrict__ gcnt,
+                                                   const uint64_t *__restrict__ goff, int tb, uint32_t *__restrict__ hit,
+                                                   uint64_t *__restrict__ gkey)
 {
     const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
     const Scan c = scan_ctx(cw, Q, P, p);
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < CH / 64; ++u) {
-        const uint32_t e = c.base + u * 64 + lane_id();
-        cnt += (uint32_t)__popcll(__ballot(e < c.end && visited(s, p, c, e)));
-    }
-    if (lane_id() == 0) chunk_cnt[cw] = cnt;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_cr_emit(uint64_t first, uint64_t nchunks, Queries Q, CfkResident s, Pairs P, Params p,
-                                                   const uint64_t *__restrict__ chunk_eoff, const uint64_t *__restrict__ epos,
-                                                   const uint64_t *__restrict__ gcnt, const uint64_t *__restrict__ goff, int tb,
-                                                   uint32_t *__restrict__ hit, uint64_t *__restrict__ gkey)
-{
-    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (cw >= nchunks) return;
-    const Scan c = scan_ctx(cw, Q, P, p);
+    const View v{ s, c, c.mask };
     const uint64_t lt = (1ull << lane_id()) - 1;
-    uint64_t out = chunk_eoff[cw];
-    if (chunk_eoff[cw + 1] == out) return;
-    const bool big = gcnt[c.q] != 0;
-    const uint64_t gbase = big ? goff[c.q] - epos[Q.off[c.q]] : 0;   // hit slot -> slot among the sorting tier's hits
+    uint32_t cnt = 0;
+    uint64_t out = 0, gbase = 0;
+    bool big = false;
+    if constexpr (EMIT) {
+        out = chunk_eoff[cw];
+        if (chunk_eoff[cw + 1] == out) return;
+        big = gcnt[c.q] != 0;
+        gbase = big ? goff[c.q] - epos[Q.off[c.q]] : 0;   // hit slot -> slot among the sorting tier's hits
+    }
 #pragma unroll
     for (uint32_t u = 0; u < CH / 64; ++u) {
         const uint32_t e = c.base + u * 64 + lane_id();
-        const bool m = e < c.end && visited(s, p, c, e);
+        const bool m = e < c.end && cfk_entry_passes(v, p, e);
         const uint64_t bal = __ballot(m);
-        if (m) {
-            const uint32_t lo = view_index(s, e);
-            const uint64_t o = out + (uint64_t)__popcll(bal & lt);
-            hit[o] = lo;
-            if (big) gkey[gbase + o] = ((uint64_t)c.q << tb) | lo;
+        if constexpr (EMIT) {
+            if (m) {
+                const uint32_t lo = view_index(s, e);
+                const uint64_t o = out + (uint64_t)__popcll(bal & lt);
+                hit[o] = lo;
+                if (big) gkey[gbase + o] = ((uint64_t)c.q << tb) | lo;
+            }
+            out += (uint64_t)__popcll(bal);
+        } else {
+            cnt += (uint32_t)__popcll(bal);
         }
-        out += (uint64_t)__popcll(bal);
+    }
+    if constexpr (!EMIT) {
+        if (lane_id() == 0) chunk_cnt[cw] = cnt;
     }
 }
 
@@ -1229,10 +1235,7 @@ void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *
     if (!cfk || !in || !view) fail(ACC_E_ARG, "null argument");
     const CfkResident s = resident_checked(cfk, in->mem);
     if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
-    if (in->started_at > 2 || in->test_dep > 2 || in->test_status > 2)
-        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
-    if (in->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
-    if (in->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
+    const RcParams prm = recovery_params(in->started_at, in->test_dep, in->test_status, in->flags, in->test_kinds);
     if (in->n_pairs >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many (query, key) pairs in one call (>= 2^32 - 1)");
     if (in->n_ranges >= 0xFFFFFFFFull) fail(ACC_E_CAP, "too many ranges in one call (>= 2^32 - 1)");
     const uint64_t wl0 = ctx->wave_launches;
@@ -1244,8 +1247,6 @@ void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *
         empty_result(ctx, view);
         return;
     }
-    const cr::Params prm{ in->started_at, in->test_dep, in->test_status, (uint32_t)(in->flags & ACC_FULL_EXECUTES_AFTER),
-                          in->test_kinds < 0 ? -1 : in->test_kinds };
 
     Queries Q{};
     Q.nq = nq;
@@ -1267,14 +1268,17 @@ void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *
                chunks);
     uint64_t *chunk_off = nullptr;
     uint32_t *chunk_item = nullptr;
-    const uint64_t NC = chunk_layout(ctx, Qp, chunks, chunk_off, chunk_item);
+    ReadBack rb_chunks(ctx);
+    const uint64_t NC = chunk_layout(ctx, rb_chunks, Qp, chunks, chunk_off, chunk_item);
     const Pairs P{ pair_q, pair_a, pair_w, chunk_off, chunk_item, Qp };
 
     // ---- count, then emit and KeyDeps.Builder
     uint64_t *chunk_cnt = ctx->get<uint64_t>("cq_chunk_cnt", NC);
-    if (NC) launch_waves(ctx, "cr_count", cr::k_cr_count, NC, NC, Q, s, P, prm, chunk_cnt);
+    const uint64_t *none = nullptr;   // the emit pass's arguments
+    if (NC) launch_waves(ctx, "cr_count", cr::k_cr_scan<false>, NC, NC, Q, s, P, prm, chunk_cnt, none, none, none, none, 0, (uint32_t *)nullptr, (uint64_t *)nullptr);
     const Built b = build_keydeps(ctx, s, Q, pair_q, chunk_off, chunk_cnt, NC, errs, view, [&](const EmitArgs &e) {
-        launch_waves(ctx, "cr_emit", cr::k_cr_emit, NC, NC, Q, s, P, prm, e.chunk_eoff, e.epos, e.gcnt, e.goff, e.tb, e.hit, e.gkey);
+        launch_waves(ctx, "cr_emit", cr::k_cr_scan<true>, NC, NC, Q, s, P, prm, (uint64_t *)nullptr, e.chunk_eoff, e.epos, e.gcnt,
+                     e.goff, e.tb, e.hit, e.gkey);
     });
     ctx->stat("cfr.pairs", Qp);
     ctx->stat("cfr.chunks", NC);

@@ -1,5 +1,6 @@
 // ctx.hpp — acc_ctx: one HIP stream, a grow-only device arena keyed by buffer name, per-kernel
-// HIP-event timing, and the exception -> error-code plumbing behind the C ABI (include/accord_amd.h).
+// HIP-event timing, the read-back of device scalars through its pinned staging (ReadBack), and the exception ->
+// error-code plumbing behind the C ABI (include/accord_amd.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -385,6 +386,44 @@ inline const T *stage_in(acc_ctx *ctx, const char *name, const T *src, size_t co
     ACC_HIP(hipMemcpyAsync(d, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
     return d;
 }
+
+// Read-back of device scalars through the context's pinned staging. Each u32 / u64 (or words) call enqueues one
+// hipMemcpyAsync on the context stream into the next free 8-byte word(s); wait() syncs the context once; the handles
+// then give the values. A handle that was never queued reads 0 (a count of an empty array). One ReadBack per sync:
+// every one starts at word 0, so its values are taken before the next one is made.
+class ReadBack {
+public:
+    template <class T>
+    struct Word {
+        const uint64_t *w = nullptr;
+        T operator[](size_t i) const
+        {
+            T v = 0;
+            if (w) memcpy(&v, reinterpret_cast<const char *>(w) + i * sizeof(T), sizeof(T));
+            return v;
+        }
+        operator T() const { return (*this)[0]; }
+    };
+    explicit ReadBack(acc_ctx *c) : ctx(c) {}
+    Word<uint32_t> u32(const uint32_t *dev) { return words(dev, 1); }
+    Word<uint64_t> u64(const uint64_t *dev) { return words(dev, 1); }
+    // count values in one copy, packed from the next free word
+    template <class T>
+    Word<T> words(const T *dev, size_t count)
+    {
+        static_assert(sizeof(T) == 4 || sizeof(T) == 8, "u32 or u64 values");
+        uint64_t *w = ctx->pinned + used;
+        used += (count * sizeof(T) + 7) / 8;
+        if (used > acc_ctx::PINNED_SLOTS) fail(ACC_E_STATE, "internal: read-back past the pinned staging words");
+        ACC_HIP(hipMemcpyAsync(w, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
+        return Word<T>{ w };
+    }
+    void wait() { ctx->sync(); }
+
+private:
+    acc_ctx *ctx;
+    size_t used = 0;
+};
 
 }  // namespace acc
 

@@ -1,7 +1,7 @@
 // rangedeps.hpp — what the RangeDeps translation units share (rangedeps.hip: prepare, stored-range dictionary and the
 // driver; rangedeps_stab.hip: the queries and the stabbing pass; rangedeps_build.hip: the per-txn build and the
 // compaction): the constants, the records the kernels take by value (QRec, View, Out), the record of one batch's
-// pipeline (RdBuild) with its stage entry points, and the read-back of device scalars (ReadBack).
+// pipeline (RdBuild) with its stage entry points. (The read-back of device scalars, ReadBack, is ctx.hpp's.)
 #pragma once
 
 #include "dict.hpp"
@@ -73,44 +73,6 @@ struct Out {
 };
 
 }  // namespace rd
-
-// Read-back of device scalars through the context's pinned staging. Each u32 / u64 (or words) call enqueues one
-// hipMemcpyAsync on the context stream into the next free 8-byte word(s); wait() syncs the context once; the handles
-// then give the values. A handle that was never queued reads 0 (a count of an empty array). One ReadBack per sync:
-// every one starts at word 0, so its values are taken before the next one is made.
-class ReadBack {
-public:
-    template <class T>
-    struct Word {
-        const uint64_t *w = nullptr;
-        T operator[](size_t i) const
-        {
-            T v = 0;
-            if (w) memcpy(&v, reinterpret_cast<const char *>(w) + i * sizeof(T), sizeof(T));
-            return v;
-        }
-        operator T() const { return (*this)[0]; }
-    };
-    explicit ReadBack(acc_ctx *c) : ctx(c) {}
-    Word<uint32_t> u32(const uint32_t *dev) { return words(dev, 1); }
-    Word<uint64_t> u64(const uint64_t *dev) { return words(dev, 1); }
-    // count values in one copy, packed from the next free word
-    template <class T>
-    Word<T> words(const T *dev, size_t count)
-    {
-        static_assert(sizeof(T) == 4 || sizeof(T) == 8, "u32 or u64 values");
-        uint64_t *w = ctx->pinned + used;
-        used += (count * sizeof(T) + 7) / 8;
-        if (used > acc_ctx::PINNED_SLOTS) fail(ACC_E_STATE, "internal: read-back past the pinned staging words");
-        ACC_HIP(hipMemcpyAsync(w, dev, count * sizeof(T), hipMemcpyDeviceToHost, ctx->stream));
-        return Word<T>{ w };
-    }
-    void wait() { ctx->sync(); }
-
-private:
-    acc_ctx *ctx;
-    size_t used = 0;
-};
 
 // One batch's RangeDeps pipeline: rangedeps_batch sets the sizes, each stage fills its part in turn and only reads the
 // parts before it. Device pointers are owned by the context and valid until its next compute call.

@@ -495,7 +495,7 @@ __global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, int test
                 if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, l, xn) <= 0) lo = m + 1; else hi = m;
             }
             const uint32_t upper = lo;
-            const uint32_t lim = started_at == 0 ? lower : started_at == 1 ? s.n - upper : s.n;
+            const uint32_t lim = started_at == ACC_STARTED_BEFORE ? lower : started_at == ACC_STARTED_AFTER ? s.n - upper : s.n;
             tinfo[q] = make_uint4(lim, NONE, mask, range ? 1u : 0u);
         } else {
             // lim: first stored TxnId >= S; tpos: first stored TxnId >= the query's own, when equal
@@ -892,61 +892,70 @@ static void rcmd_check_query_errors(uint64_t e)
     if (e & E_ORDER) fail(ACC_E_ARG, "ranges of a query must be sorted and deoverlapped (Ranges.ofSortedAndDeoverlapped)");
 }
 
-void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *in, acc_rangedeps_view *view)
+// ---- the front end and the tail acc_rcmd_rangedeps and acc_rcmd_map_reduce_full share: what differs between them (the
+// prep kernel's instantiation, the recovery route's kind errors, mirror and filter, the stats) stays in the entries
+
+static void check_query_bounds(const acc_rcmd *store, uint32_t end_inclusive, uint64_t n_pairs, uint64_t n_ranges)
 {
-    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
-    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
-    if (in->end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
-    if (in->n_pairs + in->n_ranges >= 0xFFFFFFFFull || in->n_pairs >= 0xFFFFFFFFull || in->n_ranges >= 0xFFFFFFFFull)
+    if (end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
+    if (end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
+    if (n_pairs + n_ranges >= 0xFFFFFFFFull || n_pairs >= 0xFFFFFFFFull || n_ranges >= 0xFFFFFFFFull)
         fail(ACC_E_ARG, "n_pairs + n_ranges must be < 2^32");
-    hipStream_t st = ctx->stream;
+}
+
+// the build record of nq queries over the store's table, sized, with its three offset buffers; no query admits no
+// participants
+static RdBuild begin_query(acc_ctx *ctx, const acc_rcmd *store, uint32_t nq, uint64_t n_pairs, uint64_t n_ranges)
+{
     ctx->rd_valid = false;
-    const uint32_t nq = in->n_query, mem = in->mem;
     RdBuild b;
     b.n = nq;
     b.npos = store->n;
-    b.P = (size_t)in->n_pairs;
-    b.R = (size_t)in->n_ranges;
+    b.P = (size_t)n_pairs;
+    b.R = (size_t)n_ranges;
     b.Q = (uint32_t)(b.P + b.R);
     b.end_inclusive = (int)store->end_inclusive;
     b.arena_off = ctx->get<uint64_t>("rd_arena_off", (size_t)nq + 1);
     b.rd_off = ctx->get<uint64_t>("rd_rd_off", (size_t)nq + 1);
     b.u_off = ctx->get<uint64_t>("rd_u_off", (size_t)nq + 1);
-    // the dictionary of the view (placeholders while the store has none)
+    if (nq == 0 && b.P) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
+    if (nq == 0 && b.R) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
+    return b;
+}
+
+// the view of a call that stabs nothing: every query empty, the store's dictionary (placeholders while it has none).
+// The caller records its stats and syncs.
+static void publish_empty(acc_ctx *ctx, const acc_rcmd *store, const RdBuild &b, acc_rangedeps_view *view)
+{
+    hipStream_t st = ctx->stream;
+    const uint32_t nq = b.n;
     const uint64_t *dict_s = store->dict_s ? store->dict_s : ctx->get<uint64_t>("rc_dict0", 2);
     const uint64_t *dict_e = store->dict_e ? store->dict_e : ctx->get<uint64_t>("rc_dict0", 2);
-    auto empty = [&] {
-        ACC_HIP(hipMemsetAsync(b.arena_off, 0, ((size_t)nq + 1) * 8, st));
-        ACC_HIP(hipMemsetAsync(b.rd_off, 0, ((size_t)nq + 1) * 8, st));
-        ACC_HIP(hipMemsetAsync(b.u_off, 0, ((size_t)nq + 1) * 8, st));
-        *view = acc_rangedeps_view{ nq, store->n_dict, 0, 0, 0, 0, dict_s, dict_e, b.arena_off, ctx->get<int32_t>("rd_arena", 1),
-                                    b.rd_off, ctx->get<uint32_t>("rd_range_id", 1), b.u_off, ctx->get<uint32_t>("rd_dep_txn", 1) };
-        ctx->rd_view = *view;
-        ctx->rd_valid = true;
-        ctx->stat("rangedeps.entries", store->NE);
-        ctx->stat("rangedeps.stored_ranges", store->n_dict);
-        ctx->stat("rangedeps.queries", b.Q);
-        ctx->stat("rangedeps.raw_entries", 0);
-        ctx->sync();
-    };
-    if (nq == 0) {
-        if (b.P) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
-        if (b.R) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
-        empty();
-        return;
-    }
+    ACC_HIP(hipMemsetAsync(b.arena_off, 0, ((size_t)nq + 1) * 8, st));
+    ACC_HIP(hipMemsetAsync(b.rd_off, 0, ((size_t)nq + 1) * 8, st));
+    ACC_HIP(hipMemsetAsync(b.u_off, 0, ((size_t)nq + 1) * 8, st));
+    *view = acc_rangedeps_view{ nq, store->n_dict, 0, 0, 0, 0, dict_s, dict_e, b.arena_off, ctx->get<int32_t>("rd_arena", 1),
+                                b.rd_off, ctx->get<uint32_t>("rd_range_id", 1), b.u_off, ctx->get<uint32_t>("rd_dep_txn", 1) };
+    ctx->rd_view = *view;
+    ctx->rd_valid = true;
+}
 
-    // ---- stage and validate; the per-query rows
+// stages the queries of `in` (ids their TxnIds, execute_at their bounds or null: the TxnIds) and allocates what the prep
+// kernel writes: b.tinfo, owner, b.rowner and the zeroed words g ([0] errors, [1] low-bound mask, from [4] the entry's)
+template <class In>
+static Queries stage_queries(acc_ctx *ctx, RdBuild &b, const In *in, const acc_ts_cols &ids, const acc_ts_cols *execute_at,
+                             uint32_t *&owner, uint64_t *&g)
+{
+    const uint32_t nq = b.n, mem = in->mem;
     Queries Q{};
     Q.nq = nq; Q.P = (uint32_t)b.P; Q.R = (uint32_t)b.R;
-    Q.tm = stage_in(ctx, "rc_q_tm", in->txn_id.msb, nq, mem);
-    Q.tl = stage_in(ctx, "rc_q_tl", in->txn_id.lsb, nq, mem);
-    Q.tn = stage_in(ctx, "rc_q_tn", in->txn_id.node, nq, mem);
-    if (in->execute_at.msb) {
-        Q.xm = stage_in(ctx, "rc_q_xm", in->execute_at.msb, nq, mem);
-        Q.xl = stage_in(ctx, "rc_q_xl", in->execute_at.lsb, nq, mem);
-        Q.xn = stage_in(ctx, "rc_q_xn", in->execute_at.node, nq, mem);
+    Q.tm = stage_in(ctx, "rc_q_tm", ids.msb, nq, mem);
+    Q.tl = stage_in(ctx, "rc_q_tl", ids.lsb, nq, mem);
+    Q.tn = stage_in(ctx, "rc_q_tn", ids.node, nq, mem);
+    if (execute_at && execute_at->msb) {
+        Q.xm = stage_in(ctx, "rc_q_xm", execute_at->msb, nq, mem);
+        Q.xl = stage_in(ctx, "rc_q_xl", execute_at->lsb, nq, mem);
+        Q.xn = stage_in(ctx, "rc_q_xn", execute_at->node, nq, mem);
     } else {
         Q.xm = Q.tm; Q.xl = Q.tl; Q.xn = Q.tn;
     }
@@ -955,26 +964,27 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
     Q.rng_off = stage_in(ctx, "rc_q_roff", in->rng_off, (size_t)nq + 1, mem);
     Q.rs = stage_in(ctx, "rc_q_rs", in->rng_start, b.R, mem);
     Q.re = stage_in(ctx, "rc_q_re", in->rng_end, b.R, mem);
-    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
-    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
+    g = ctx->get<uint64_t>("rc_g", 8);
+    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), ctx->stream));
     b.tinfo = ctx->get<uint4>("rd_tinfo", nq);
-    uint32_t *owner = ctx->get<uint32_t>("owner", b.P);
+    owner = ctx->get<uint32_t>("owner", b.P);
     b.rowner = ctx->get<uint32_t>("rd_rowner", b.R);
-    launch(ctx, "rc_qprep", k_rc_qprep<false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), 0, 0u, b.tinfo, owner,
-           b.rowner, g);
-    {
-        ReadBack rb(ctx);
-        const auto hg = rb.words((const uint64_t *)g, 2);
-        rb.wait();
-        rcmd_check_query_errors(hg[0]);
-        b.mask_lo = hg[1];
-    }
-    if (store->NE == 0) {   // nothing to stab: no commands, or none with ranges that is not erased
-        empty();
-        return;
-    }
+    return Q;
+}
 
-    // ---- the reused stages over the store's index
+// the prep kernel's words: the low-bound mask into b; returns the error bits
+static uint64_t read_prep(acc_ctx *ctx, const uint64_t *g, RdBuild &b)
+{
+    ReadBack rb(ctx);
+    const auto hg = rb.words(g, 2);
+    rb.wait();
+    b.mask_lo = hg[1];
+    return hg[0];
+}
+
+// the reused stages (rd_stab_queries, rd_build_txns) read the staged queries and the store's index
+static void bind_store_index(RdBuild &b, const acc_rcmd *store, const Queries &Q, const uint32_t *owner)
+{
     b.key_off = Q.key_off; b.rng_off = Q.rng_off;
     b.key_code = Q.key; b.rs = Q.rs; b.re = Q.re;
     b.tl = Q.tl;
@@ -984,6 +994,44 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
     b.dict_s = store->dict_s; b.dict_e = store->dict_e; b.dincl = store->dincl;
     b.cs_s = store->cs_s; b.cs_e = store->cs_e; b.cs_info = store->cs_info; b.cs_kind = store->cs_kind;
     b.class_off = store->cls + (rd::NCLS + 1);
+}
+
+static void publish_view(acc_ctx *ctx, const RdBuild &b, acc_rangedeps_view *view)
+{
+    *view = acc_rangedeps_view{ b.n, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
+                                b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
+    ctx->rd_view = *view;
+    ctx->rd_valid = true;
+}
+
+void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *in, acc_rangedeps_view *view)
+{
+    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    check_query_bounds(store, in->end_inclusive, in->n_pairs, in->n_ranges);
+    const uint32_t nq = in->n_query;
+    RdBuild b = begin_query(ctx, store, nq, in->n_pairs, in->n_ranges);
+    auto empty = [&] {
+        publish_empty(ctx, store, b, view);
+        ctx->stat("rangedeps.entries", store->NE);
+        ctx->stat("rangedeps.stored_ranges", store->n_dict);
+        ctx->stat("rangedeps.queries", b.Q);
+        ctx->stat("rangedeps.raw_entries", 0);
+        ctx->sync();
+    };
+    if (nq == 0) return empty();
+
+    // ---- stage and validate; the per-query rows
+    uint32_t *owner = nullptr;
+    uint64_t *g = nullptr;
+    const Queries Q = stage_queries(ctx, b, in, in->txn_id, &in->execute_at, owner, g);
+    launch(ctx, "rc_qprep", k_rc_qprep<false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), 0, 0u, b.tinfo, owner,
+           b.rowner, g);
+    rcmd_check_query_errors(read_prep(ctx, g, b));
+    if (store->NE == 0) return empty();   // nothing to stab: no commands, or none with ranges that is not erased
+
+    // ---- the reused stages over the store's index
+    bind_store_index(b, store, Q, owner);
     rd_stab_queries(ctx, b);
     rd_build_txns(ctx, b);
 
@@ -998,40 +1046,18 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
     ctx->stat("rangedeps.block_txns", b.block_txns);
     ctx->stat("rangedeps.global_txns", b.tier_txns[10]);
     ctx->sync();
-    *view = acc_rangedeps_view{ nq, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
-                                b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
-    ctx->rd_view = *view;
-    ctx->rd_valid = true;
+    publish_view(ctx, b, view);
 }
 
 void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *in, acc_rangedeps_view *view)
 {
     if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
     if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    if (in->started_at > 2 || in->test_dep > 2 || in->test_status > 2)
-        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
-    if (in->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
-    if (in->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
-    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
-    if (in->end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
-    if (in->n_pairs + in->n_ranges >= 0xFFFFFFFFull || in->n_pairs >= 0xFFFFFFFFull || in->n_ranges >= 0xFFFFFFFFull)
-        fail(ACC_E_ARG, "n_pairs + n_ranges must be < 2^32");
-    hipStream_t st = ctx->stream;
+    const RcParams prm = recovery_params(in->started_at, in->test_dep, in->test_status, in->flags, in->test_kinds);
+    check_query_bounds(store, in->end_inclusive, in->n_pairs, in->n_ranges);
     const uint64_t wl0 = ctx->wave_launches;
-    ctx->rd_valid = false;
-    const uint32_t nq = in->n_query, mem = in->mem, n = store->n;
-    RdBuild b;
-    b.n = nq;
-    b.npos = n;
-    b.P = (size_t)in->n_pairs;
-    b.R = (size_t)in->n_ranges;
-    b.Q = (uint32_t)(b.P + b.R);
-    b.end_inclusive = (int)store->end_inclusive;
-    b.arena_off = ctx->get<uint64_t>("rd_arena_off", (size_t)nq + 1);
-    b.rd_off = ctx->get<uint64_t>("rd_rd_off", (size_t)nq + 1);
-    b.u_off = ctx->get<uint64_t>("rd_u_off", (size_t)nq + 1);
-    const uint64_t *dict_s = store->dict_s ? store->dict_s : ctx->get<uint64_t>("rc_dict0", 2);
-    const uint64_t *dict_e = store->dict_e ? store->dict_e : ctx->get<uint64_t>("rc_dict0", 2);
+    const uint32_t nq = in->n_query, n = store->n;
+    RdBuild b = begin_query(ctx, store, nq, in->n_pairs, in->n_ranges);
     auto stats = [&](uint64_t raw, uint64_t kept, uint64_t probes) {
         ctx->stat("rcr.queries", b.Q);
         ctx->stat("rcr.raw_entries", raw);
@@ -1039,69 +1065,24 @@ void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_
         ctx->stat("rcr.dep_probes", probes);
         ctx->stat("rcr.wave_launches", ctx->wave_launches - wl0);
     };
-    auto empty = [&] {
-        ACC_HIP(hipMemsetAsync(b.arena_off, 0, ((size_t)nq + 1) * 8, st));
-        ACC_HIP(hipMemsetAsync(b.rd_off, 0, ((size_t)nq + 1) * 8, st));
-        ACC_HIP(hipMemsetAsync(b.u_off, 0, ((size_t)nq + 1) * 8, st));
-        *view = acc_rangedeps_view{ nq, store->n_dict, 0, 0, 0, 0, dict_s, dict_e, b.arena_off, ctx->get<int32_t>("rd_arena", 1),
-                                    b.rd_off, ctx->get<uint32_t>("rd_range_id", 1), b.u_off, ctx->get<uint32_t>("rd_dep_txn", 1) };
-        ctx->rd_view = *view;
-        ctx->rd_valid = true;
-        stats(0, 0, 0);
-        ctx->sync();
-    };
-    if (nq == 0) {
-        if (b.P) fail(ACC_E_ARG, "query key_off must start at 0, be non-decreasing and end at n_pairs");
-        if (b.R) fail(ACC_E_ARG, "query rng_off must start at 0, be non-decreasing and end at n_ranges");
-        empty();
-        return;
-    }
+    auto empty = [&] { publish_empty(ctx, store, b, view); stats(0, 0, 0); ctx->sync(); };
+    if (nq == 0) return empty();
 
     // ---- stage and validate; the per-query rows
-    Queries Q{};
-    Q.nq = nq; Q.P = (uint32_t)b.P; Q.R = (uint32_t)b.R;
-    Q.tm = stage_in(ctx, "rc_q_tm", in->test_txn.msb, nq, mem);
-    Q.tl = stage_in(ctx, "rc_q_tl", in->test_txn.lsb, nq, mem);
-    Q.tn = stage_in(ctx, "rc_q_tn", in->test_txn.node, nq, mem);
-    Q.xm = Q.tm; Q.xl = Q.tl; Q.xn = Q.tn;
-    Q.key_off = stage_in(ctx, "rc_q_koff", in->key_off, (size_t)nq + 1, mem);
-    Q.key = stage_in(ctx, "rc_q_key", in->key_code, b.P, mem);
-    Q.rng_off = stage_in(ctx, "rc_q_roff", in->rng_off, (size_t)nq + 1, mem);
-    Q.rs = stage_in(ctx, "rc_q_rs", in->rng_start, b.R, mem);
-    Q.re = stage_in(ctx, "rc_q_re", in->rng_end, b.R, mem);
-    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
-    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
-    b.tinfo = ctx->get<uint4>("rd_tinfo", nq);
-    uint32_t *owner = ctx->get<uint32_t>("owner", b.P);
-    b.rowner = ctx->get<uint32_t>("rd_rowner", b.R);
-    launch(ctx, "rcr_qprep", k_rc_qprep<true>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), (int)in->test_kinds,
-           (uint32_t)in->started_at, b.tinfo, owner, b.rowner, g);
-    {
-        ReadBack rb(ctx);
-        const auto hg = rb.words((const uint64_t *)g, 2);
-        rb.wait();
-        const uint64_t e = hg[0];
-        if (e & E_Q_KIND_STATE) fail(ACC_E_STATE, "Kind.witnessedBy(): unhandled kind LocalOnly (AssertionError)");
-        if (e & E_Q_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in a testTxnId");
-        rcmd_check_query_errors(e);
-        b.mask_lo = hg[1];
-    }
-    if (store->NE == 0 || b.Q == 0) {   // nothing to stab, or nothing to stab with
-        empty();
-        return;
-    }
+    uint32_t *owner = nullptr;
+    uint64_t *g = nullptr;
+    const Queries Q = stage_queries(ctx, b, in, in->test_txn, nullptr, owner, g);
+    launch(ctx, "rcr_qprep", k_rc_qprep<true>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), (int)prm.test_kinds,
+           prm.started_at, b.tinfo, owner, b.rowner, g);
+    const uint64_t e = read_prep(ctx, g, b);
+    if (e & E_Q_KIND_STATE) fail(ACC_E_STATE, "Kind.witnessedBy(): unhandled kind LocalOnly (AssertionError)");
+    if (e & E_Q_KIND_ARG) fail(ACC_E_ARG, "Kind.ofOrdinal: invalid kind ordinal in a testTxnId");
+    rcmd_check_query_errors(e);
+    if (store->NE == 0 || b.Q == 0) return empty();   // nothing to stab, or nothing to stab with
 
     // ---- the stabbing pass as it is, over the store's index (STARTED_AFTER: positions counted from the top)
-    b.key_off = Q.key_off; b.rng_off = Q.rng_off;
-    b.key_code = Q.key; b.rs = Q.rs; b.re = Q.re;
-    b.tl = Q.tl;
-    b.owner = owner;
-    b.dict.batch_sorted = true;   // tpos is the table index: no txn_of_tpos
-    b.NE = store->NE;
-    b.dict_s = store->dict_s; b.dict_e = store->dict_e; b.dincl = store->dincl;
-    b.cs_s = store->cs_s; b.cs_e = store->cs_e; b.cs_info = store->cs_info; b.cs_kind = store->cs_kind;
-    b.class_off = store->cls + (rd::NCLS + 1);
-    const bool mirror = in->started_at == 1;
+    bind_store_index(b, store, Q, owner);
+    const bool mirror = prm.started_at == ACC_STARTED_AFTER;
     if (mirror) {
         uint2 *mi = ctx->get<uint2>("rcr_info", store->NE);
         launch(ctx, "rcr_mirror", k_rcr_mirror, dim3(grid_for(store->NE, BLOCK)), dim3(BLOCK), 0, store->NE, n,
@@ -1111,27 +1092,19 @@ void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_
     rd_stab_queries(ctx, b);
 
     // ---- the command tests on the candidates alone
-    const RcParams prm{ in->started_at, in->test_dep, in->test_status, (uint32_t)(in->flags & ACC_FULL_EXECUTES_AFTER) };
     const StateCols c{ store->tm, store->tl, store->em, store->el, store->tn, store->en, store->status, store->flags, store->rng_off,
                        store->rs, store->re, store->dep_off, store->dm, store->dl, store->dn, store->ds, store->de, store->dk,
                        store->end_inclusive };
-    uint64_t *fst = g + 4;   // zeroed above; the prep kernel writes g[0], g[1]
+    uint64_t *fst = g + 4;   // zeroed with g; the prep kernel writes g[0], g[1]
     if (b.E)
         launch_waves(ctx, "rcr_filter", k_rcr_filter, (uint64_t)b.Q, (uint64_t)b.Q, (uint32_t)b.P, (const uint32_t *)owner,
                      (const uint32_t *)b.rowner, c, Q.tm, Q.tl, Q.tn, (const uint4 *)b.tinfo, prm, mirror ? n : 0u, b.v.q_out, b.v.ent, fst);
     rd_build_txns(ctx, b);
-    uint64_t kept, probes;
-    {
-        ReadBack rb(ctx);
-        const auto hs = rb.words((const uint64_t *)fst, 2);
-        rb.wait();
-        kept = hs[0]; probes = hs[1];
-    }
-    stats(b.E, kept, probes);
-    *view = acc_rangedeps_view{ nq, b.n_dict, b.tot_arena, b.tot_rd, b.tot_u, b.tot_arena - b.tot_rd, b.dict_s, b.dict_e, b.arena_off,
-                                b.o.arena, b.rd_off, b.o.range_id, b.u_off, b.o.dep_txn };
-    ctx->rd_view = *view;
-    ctx->rd_valid = true;
+    ReadBack rb(ctx);
+    const auto hs = rb.words((const uint64_t *)fst, 2);
+    rb.wait();
+    stats(b.E, hs[0], hs[1]);
+    publish_view(ctx, b, view);
 }
 
 }  // namespace acc

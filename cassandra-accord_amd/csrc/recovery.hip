@@ -12,8 +12,8 @@
 //                     "executeAt <= X" is exec rank < lo + eq.
 //   2. items          per (query, key): its segment (binary search of the sorted segment keys), the binarySearch
 //                     insert position of X among the segment's TxnId ranks, the window, its 256-entry chunks.
-//   3. count / emit   one wave per chunk evaluates the entry predicate (kind, status, hasInfo, executeAt, missing[]
-//                     membership by binary search over TxnId ranks) and compacts matches in position order, so each
+//   3. count / emit   one wave per chunk evaluates the entry predicate (cfk_entry_passes, recovery_pred.hpp: status,
+//                     hasInfo, kind, executeAt, missing[] by binary search over TxnId ranks) and compacts matches in position order, so each
 //                     query's entries come out key by key in TxnId order (the map visiting order).
 //   4. build          Deps.Builder: keys with >= 1 entry, one (query, TxnId rank) radix sort for the sorted unique
 //                     TxnIds and each entry's index, the Java keysToTxnIds layout.
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(BLOCK) void k_rc_query(uint32_t nq, const uint64_t 
     int mask = test_kinds;
     if (mask < 0) {
         mask = witnessed_by(kind);
-        if (mask < 0) e |= kind == 5 ? RC_ERR_KIND_STATE : RC_ERR_KIND_ARG;   // LocalOnly: AssertionError; > 5: ofOrdinal
+        if (mask < 0) e |= kind == ACC_KIND_LOCAL_ONLY ? RC_ERR_KIND_STATE : RC_ERR_KIND_ARG;   // LocalOnly: AssertionError; beyond: ofOrdinal
     }
     qmask[q] = (uint8_t)(mask < 0 ? 0 : mask);
     const uint32_t k0 = qoff[q], k1 = qoff[q + 1];
@@ -150,9 +150,9 @@ __global__ __launch_bounds__(BLOCK) void k_rc_items(uint32_t Qp, uint32_t nq, co
         // Arrays.binarySearch(txns, testTxnId): found <=> X is a member; insertPos = its index or the insert point
         const uint32_t pos = rc_lower<uint32_t>(c.s_rank, sb, se, x);
         const bool known = qeq[q] && pos < se && c.s_rank[pos] == x;
-        if (known || p.test_dep != 0) {
-            const uint32_t start = p.started_at == 1 ? pos : sb;
-            const uint32_t end = p.started_at == 0 ? pos : se;
+        if (known || p.test_dep != ACC_DEP_WITH) {
+            const uint32_t start = p.started_at == ACC_STARTED_AFTER ? pos : sb;
+            const uint32_t end = p.started_at == ACC_STARTED_BEFORE ? pos : se;
             a = start;
             w = end - start;
         }
@@ -162,38 +162,6 @@ __global__ __launch_bounds__(BLOCK) void k_rc_items(uint32_t Qp, uint32_t nq, co
     item_chunks[i] = (w + RC_CH - 1) / RC_CH;
 }
 
-// the per-entry tests of CommandsForKey.mapReduceFull (:577-607) plus the optional executeAt > testTxnId map filter
-__device__ __forceinline__ bool rc_match(const RcCfk &c, const RcParams &p, uint32_t e, uint32_t mask, uint32_t x, bool eq)
-{
-    const uint32_t info = c.s_info[e];
-    const uint32_t status = info & 7u, kind = info >> 3;
-    if (!((mask >> kind) & 1u)) return false;
-    switch (p.test_status) {
-    case 1: if (status != 3 && status != 4) return false; break;   // IS_PROPOSED: ACCEPTED, COMMITTED
-    case 2: if (status < 5 || status >= 7) return false; break;    // IS_STABLE: STABLE <= s < INVALID_OR_TRUNCATED
-    default: if (status == 0) return false; break;                 // ANY_STATUS: not TRANSITIVELY_KNOWN
-    }
-    const uint32_t ex = c.s_exec[e];
-    const bool exec_after = ex >= x + (eq ? 1u : 0u);             // executeAt > testTxnId
-    if (p.test_dep != 2) {
-        if (status < 3 || status > 6) return false;               // !InternalStatus.hasInfo
-        if (!exec_after) return false;
-        bool in_missing = false;
-        if (eq) {                                                 // only a batch member can be in missing[]
-            const uint32_t j = c.perm[e];
-            uint32_t lo = c.miss_off[j], hi = c.miss_off[j + 1];
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                const uint32_t r = c.rank[c.miss_txn[m]];
-                if (r < x) lo = m + 1; else if (r > x) hi = m; else { in_missing = true; break; }
-            }
-        }
-        if (in_missing == (p.test_dep == 0)) return false;        // hasAsDep != (testDep == WITH)
-    }
-    if (p.exec_after && !exec_after) return false;
-    return true;
-}
-
 struct RcChunks {
     const uint64_t *chunk_off;   // [Qp+1] exclusive scan of item_chunks
     const uint32_t *item_q, *item_a, *item_w, *qlo;
@@ -201,32 +169,34 @@ struct RcChunks {
     uint32_t Qp;
 };
 
-// one wave per chunk: match count (and its item's running total)
-__global__ __launch_bounds__(BLOCK) void k_rc_count(uint64_t first, uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
-                                                    uint32_t *__restrict__ chunk_cnt, unsigned long long *__restrict__ item_cnt)
-{
-    const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (cw >= nchunks) return;
-    const uint32_t item = rc_upper64(ch.chunk_off, ch.Qp + 1, cw) - 1;
-    const uint32_t q = ch.item_q[item];
-    const uint32_t base = ch.item_a[item] + (uint32_t)(cw - ch.chunk_off[item]) * RC_CH;
-    const uint32_t end = ch.item_a[item] + ch.item_w[item];
-    const uint32_t x = ch.qlo[q], mask = ch.qmask[q];
-    const bool eq = ch.qeq[q] != 0;
-    uint32_t cnt = 0;
-#pragma unroll
-    for (uint32_t u = 0; u < RC_CH / 64; ++u) {
-        const uint32_t e = base + u * 64 + lane_id();
-        cnt += (uint32_t)__popcll(__ballot(e < end && rc_match(c, p, e, mask, x, eq)));
+// one query against the snapshot, as cfk_entry_passes reads it: x = #dictionary timestamps below testTxnId, eq = it is
+// one of them, so "executeAt > X" is exec rank >= x + eq, and X can be in a missing[] only when eq
+struct RcView {
+    const RcCfk &c;
+    uint32_t x, mask;
+    bool eq;
+    __device__ __forceinline__ uint32_t status(uint32_t e) const { return c.s_info[e] & 7u; }
+    __device__ __forceinline__ uint32_t kind(uint32_t e) const { return c.s_info[e] >> 3; }
+    __device__ __forceinline__ bool executes_after_x(uint32_t e) const { return c.s_exec[e] >= x + (eq ? 1u : 0u); }
+    __device__ __forceinline__ bool x_in_missing(uint32_t e) const
+    {
+        if (!eq) return false;   // only a batch member can be in missing[]
+        const uint32_t j = c.perm[e];
+        uint32_t lo = c.miss_off[j], hi = c.miss_off[j + 1];
+        while (lo < hi) {
+            const uint32_t m = (lo + hi) >> 1;
+            const uint32_t r = c.rank[c.miss_txn[m]];
+            if (r < x) lo = m + 1; else if (r > x) hi = m; else return true;
+        }
+        return false;
     }
-    if (lane_id() == 0) {
-        chunk_cnt[cw] = cnt;
-        if (cnt) atomicAdd(&item_cnt[item], (unsigned long long)cnt);
-    }
-}
+};
 
+// one wave per chunk evaluates the entry predicate. Count: the chunk's matches (and its item's running total). Emit:
 // the same walk, compacting matches in position order: (query << rbits | TxnId rank) per emitted entry
-__global__ __launch_bounds__(BLOCK) void k_rc_emit(uint64_t first, uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
+template <bool EMIT>
+__global__ __launch_bounds__(BLOCK) void k_rc_scan(uint64_t first, uint64_t nchunks, RcCfk c, RcParams p, RcChunks ch,
+                                                   uint32_t *__restrict__ chunk_cnt, unsigned long long *__restrict__ item_cnt,
                                                    const uint64_t *__restrict__ chunk_eoff, int rbits, uint64_t *__restrict__ ent)
 {
     const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
@@ -235,17 +205,28 @@ __global__ __launch_bounds__(BLOCK) void k_rc_emit(uint64_t first, uint64_t nchu
     const uint32_t q = ch.item_q[item];
     const uint32_t base = ch.item_a[item] + (uint32_t)(cw - ch.chunk_off[item]) * RC_CH;
     const uint32_t end = ch.item_a[item] + ch.item_w[item];
-    const uint32_t x = ch.qlo[q], mask = ch.qmask[q];
-    const bool eq = ch.qeq[q] != 0;
+    const RcView v{ c, ch.qlo[q], ch.qmask[q], ch.qeq[q] != 0 };
     const uint64_t lt = (1ull << lane_id()) - 1;
-    uint64_t out = chunk_eoff[cw];
+    uint32_t cnt = 0;
+    uint64_t out = 0;
+    if constexpr (EMIT) out = chunk_eoff[cw];
 #pragma unroll
     for (uint32_t u = 0; u < RC_CH / 64; ++u) {
         const uint32_t e = base + u * 64 + lane_id();
-        const bool m = e < end && rc_match(c, p, e, mask, x, eq);
+        const bool m = e < end && cfk_entry_passes(v, p, e);
         const uint64_t bal = __ballot(m);
-        if (m) ent[out + (uint64_t)__popcll(bal & lt)] = ((uint64_t)q << rbits) | c.s_rank[e];
-        out += (uint64_t)__popcll(bal);
+        if constexpr (EMIT) {
+            if (m) ent[out + (uint64_t)__popcll(bal & lt)] = ((uint64_t)q << rbits) | c.s_rank[e];
+            out += (uint64_t)__popcll(bal);
+        } else {
+            cnt += (uint32_t)__popcll(bal);
+        }
+    }
+    if constexpr (!EMIT) {
+        if (lane_id() == 0) {
+            chunk_cnt[cw] = cnt;
+            if (cnt) atomicAdd(&item_cnt[item], (unsigned long long)cnt);
+        }
     }
 }
 
@@ -329,10 +310,7 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
 {
     if (!in || !rq || !view) fail(ACC_E_ARG, "null argument");
     if (rq->mem != ACC_MEM_HOST && rq->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    if (rq->started_at > 2 || rq->test_dep > 2 || rq->test_status > 2)
-        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
-    if (rq->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
-    if (rq->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
+    const RcParams prm = recovery_params(rq->started_at, rq->test_dep, rq->test_status, rq->flags, rq->test_kinds);
     hipStream_t st = ctx->stream;
     const uint64_t wl0 = ctx->wave_launches;
     ctx->kd_valid = false;
@@ -342,9 +320,10 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     const uint32_t mem = rq->mem;
 
     const uint32_t *qoff = stage_in(ctx, "rc_qoff", rq->key_off, (size_t)nq + 1, mem);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, qoff + nq, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint32_t Qp = (uint32_t)(ctx->pinned[0] & 0xFFFFFFFFu);
+    ReadBack rb_pairs(ctx);
+    const auto h_qp = rb_pairs.u32(qoff + nq);
+    rb_pairs.wait();
+    const uint32_t Qp = h_qp;
     const uint64_t *qm = stage_in(ctx, "rc_qm", rq->test_txn.msb, nq, mem);
     const uint64_t *ql = stage_in(ctx, "rc_ql", rq->test_txn.lsb, nq, mem);
     const int32_t *qn = stage_in(ctx, "rc_qn", rq->test_txn.node, nq, mem);
@@ -369,9 +348,8 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     uint8_t *qeq = ctx->get<uint8_t>("rc_qeq", nq);
     uint8_t *qmask = ctx->get<uint8_t>("rc_qmask", nq);
     launch(ctx, "rc_query", k_rc_query, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, nq, qm, ql, qn, qoff, qkey, rs,
-           (int)rq->test_kinds, qlo, qeq, qmask, errs);
+           (int)prm.test_kinds, qlo, qeq, qmask, errs);
 
-    const RcParams prm{ rq->started_at, rq->test_dep, rq->test_status, (uint32_t)(rq->flags & ACC_FULL_EXECUTES_AFTER) };
     RcCfk c{ s.seg_key, s.seg_start, s.s_rank, s.s_exec, s.perm, s.dict.rank, moff, mtxn, s.s_info, s.cfk ? s.nseg : 0u,
              (uint32_t)P };
     uint32_t *item_q = ctx->get<uint32_t>("rc_item_q", Qp);
@@ -386,11 +364,11 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     } else {
         ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
     }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, chunk_off + Qp, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_rc_errors(ctx->pinned[0]);
-    const uint64_t NC = ctx->pinned[1];
+    ReadBack rb_chunks(ctx);
+    const auto h_errs = rb_chunks.u64(errs), h_nc = rb_chunks.u64(chunk_off + Qp);
+    rb_chunks.wait();
+    check_rc_errors(h_errs);
+    const uint64_t NC = h_nc;
 
     // ---- count, scan, emit
     unsigned long long *item_cnt = ctx->get<unsigned long long>("rc_item_cnt", Qp);
@@ -400,7 +378,8 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     ACC_HIP(hipMemsetAsync(item_cnt, 0, (size_t)Qp * 8, st));
     RcChunks chs{ chunk_off, item_q, item_a, item_w, qlo, qeq, qmask, Qp };
     if (NC) {
-        launch_waves(ctx, "rc_count", k_rc_count, NC, NC, c, prm, chs, chunk_cnt, item_cnt);
+        launch_waves(ctx, "rc_count", k_rc_scan<false>, NC, NC, c, prm, chs, chunk_cnt, item_cnt, (const uint64_t *)nullptr, 0,
+                     (uint64_t *)nullptr);
         launch(ctx, "rc_widen", k_widen_u32, dim3(grid_for(NC, BLOCK)), dim3(BLOCK), 0, (size_t)NC, (const uint32_t *)chunk_cnt, chunk_cnt64);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, chunk_cnt64, chunk_eoff, NC, true, chunk_eoff + NC);
     } else {
@@ -417,16 +396,17 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
         ACC_HIP(hipMemsetAsync(kpos, 0, 8, st));
         ACC_HIP(hipMemsetAsync(epos, 0, 8, st));
     }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_eoff + NC, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, kpos + Qp, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t E = ctx->pinned[0], TK = ctx->pinned[1];
+    ReadBack rb_sizes(ctx);
+    const auto h_e = rb_sizes.u64(chunk_eoff + NC), h_tk = rb_sizes.u64(kpos + Qp);
+    rb_sizes.wait();
+    const uint64_t E = h_e, TK = h_tk;
     if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 recovery-scan entries in one call");
     const int rbits = s.dict.rbits;
     const int qbits = bits_for(nq ? nq - 1 : 0);
     if (E && qbits + rbits > 64) fail(ACC_E_CAP, "too many queries for the (query, TxnId rank) composite key");
     uint64_t *ent = ctx->get<uint64_t>("rc_ent", E);
-    if (E) launch_waves(ctx, "rc_emit", k_rc_emit, NC, NC, c, prm, chs, (const uint64_t *)chunk_eoff, rbits, ent);
+    if (E) launch_waves(ctx, "rc_emit", k_rc_scan<true>, NC, NC, c, prm, chs, (uint32_t *)nullptr, (unsigned long long *)nullptr,
+                        (const uint64_t *)chunk_eoff, rbits, ent);
 
     // ---- Deps.Builder layout
     uint64_t *arena_off = ctx->get<uint64_t>("rc_arena_off", (size_t)nq + 1);
@@ -456,9 +436,10 @@ void map_reduce_full(acc_ctx *ctx, const acc_batch_in *in, const acc_recovery_in
     } else {
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
     }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, u_off + nq, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t TU = ctx->pinned[0];
+    ReadBack rb_uniq(ctx);
+    const auto h_tu = rb_uniq.u64(u_off + nq);
+    rb_uniq.wait();
+    const uint64_t TU = h_tu;
     ctx->stat("recovery.items", Qp);
     ctx->stat("recovery.chunks", NC);
     ctx->stat("recovery.entries", E);
@@ -522,7 +503,8 @@ __global__ __launch_bounds__(BLOCK) void k_rr_check(RrCmds c, uint32_t *__restri
         if (prev > 0) e |= RR_ERR_ORDER;
     }
     tflag[i] = prev != 0 ? 1u : 0u;
-    if (c.status[i] > 10 || (c.flags[i] & ~7u)) e |= RR_ERR_STATUS;
+    if (c.status[i] > RR_ST_INVALIDATED || (c.flags[i] & ~(ACC_RCMD_ERASED | ACC_RCMD_HAS_DEPS | ACC_RCMD_HISTORICAL)))
+        e |= RR_ERR_STATUS;
     const uint32_t r0 = c.roff[i], r1 = c.roff[i + 1];
     if (r1 < r0 || r1 > c.R || (i == 0 && r0 != 0) || (i == c.n - 1 && r1 != c.R)) e |= RR_ERR_OFF;
     else
@@ -582,7 +564,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
     int mask = test_kinds;
     if (mask < 0) {
         mask = witnessed_by((uint32_t)(xl >> 1) & 7u);
-        if (mask < 0) e |= ((xl >> 1) & 7u) == 5 ? RR_ERR_KIND_STATE : RR_ERR_KIND_ARG;
+        if (mask < 0) e |= ((xl >> 1) & 7u) == ACC_KIND_LOCAL_ONLY ? RR_ERR_KIND_STATE : RR_ERR_KIND_ARG;
     }
     qmask[q] = (uint8_t)(mask < 0 ? 0 : mask);
     const uint32_t p0 = Q.poff[q], p1 = Q.poff[q + 1];
@@ -602,8 +584,8 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
     while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) <= 0) lo = m + 1; else hi = m; }
     const uint32_t upper = lo;
     uint32_t a = 0, w = c.n;
-    if (started_at == 0) w = lower;                     // STARTED_BEFORE: txnId < X (:897-898)
-    else if (started_at == 1) { a = upper; w = c.n - upper; }   // STARTED_AFTER: txnId > X (:894-896)
+    if (started_at == ACC_STARTED_BEFORE) w = lower;                                // txnId < X (:897-898)
+    else if (started_at == ACC_STARTED_AFTER) { a = upper; w = c.n - upper; }       // txnId > X (:894-896)
     qa[q] = a;
     qw[q] = w;
     qchunks[q] = (w + 63) / 64;
@@ -764,10 +746,7 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     if (!ci || !ri || !view) fail(ACC_E_ARG, "null argument");
     for (uint32_t m : { ci->mem, ri->mem })
         if (m != ACC_MEM_HOST && m != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
-    if (ri->started_at > 2 || ri->test_dep > 2 || ri->test_status > 2)
-        fail(ACC_E_ARG, "started_at / test_dep / test_status must be TestStartedAt / TestDep / TestStatus ordinals");
-    if (ri->flags & ~ACC_FULL_EXECUTES_AFTER) fail(ACC_E_ARG, "unknown flags");
-    if (ri->test_kinds > 0x3F) fail(ACC_E_ARG, "test_kinds must be a mask over the six Kind ordinals, or -1");
+    const RcParams prm = recovery_params(ri->started_at, ri->test_dep, ri->test_status, ri->flags, ri->test_kinds);
     if (ci->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 or 1");
     hipStream_t st = ctx->stream;
     const uint64_t wl0 = ctx->wave_launches;
@@ -779,12 +758,10 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     const uint32_t *roff = stage_in(ctx, "rr_roff", ci->rng_off, (size_t)n + 1, cm);
     const uint32_t *doff = stage_in(ctx, "rr_doff", ci->dep_off, (size_t)n + 1, cm);
     const uint32_t *poff = stage_in(ctx, "rr_poff", ri->part_off, (size_t)nq + 1, qmem);
-    uint32_t *tot = reinterpret_cast<uint32_t *>(ctx->pinned);
-    ACC_HIP(hipMemcpyAsync(tot + 0, roff + n, 4, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(tot + 1, doff + n, 4, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(tot + 2, poff + nq, 4, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t R = tot[0], D = tot[1], NP = tot[2];
+    ReadBack rb_tot(ctx);
+    const auto h_r = rb_tot.u32(roff + n), h_d = rb_tot.u32(doff + n), h_np = rb_tot.u32(poff + nq);
+    rb_tot.wait();
+    const uint64_t R = h_r, D = h_d, NP = h_np;
 
     RrCmds c{};
     c.tm = stage_in(ctx, "rr_tm", ci->txn_id.msb, n, cm);
@@ -858,24 +835,22 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     uint64_t *qchunks = ctx->get<uint64_t>("rr_qchunks", nq);
     uint64_t *chunk_off = ctx->get<uint64_t>("rr_chunk_off", (size_t)nq + 1);
     if (nq) {
-        launch(ctx, "rr_query", k_rr_query, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, c, (int)ri->test_kinds,
-               (uint32_t)ri->started_at, qmask, qa, qw, qchunks, errs);
+        launch(ctx, "rr_query", k_rr_query, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, c, (int)prm.test_kinds, prm.started_at,
+               qmask, qa, qw, qchunks, errs);
         scan<uint64_t, OpAdd<uint64_t>>(ctx, qchunks, chunk_off, nq, true, chunk_off + nq);
     } else {
         ACC_HIP(hipMemsetAsync(chunk_off, 0, 8, st));
     }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 1, chunk_off + nq, 8, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(ctx->pinned + 2, n ? (const void *)(tincl + n - 1) : (const void *)errs, 4, hipMemcpyDeviceToHost, st));
-    ACC_HIP(hipMemcpyAsync(reinterpret_cast<uint32_t *>(ctx->pinned + 2) + 1, R ? (const void *)(dincl + R - 1) : (const void *)errs,
-                           4, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    check_rr_errors(ctx->pinned[0]);
-    const uint64_t NC = ctx->pinned[1];
-    const uint32_t NT = n ? reinterpret_cast<uint32_t *>(ctx->pinned + 2)[0] : 0u;
-    const uint32_t ND = R ? reinterpret_cast<uint32_t *>(ctx->pinned + 2)[1] : 0u;
+    ReadBack rb_chunks(ctx);
+    const auto h_errs = rb_chunks.u64(errs), h_nc = rb_chunks.u64(chunk_off + nq);
+    ReadBack::Word<uint32_t> h_nt, h_nd;   // distinct TxnIds and distinct ranges of the table: never queued = 0, an empty array
+    if (n) h_nt = rb_chunks.u32(tincl + n - 1);
+    if (R) h_nd = rb_chunks.u32(dincl + R - 1);
+    rb_chunks.wait();
+    check_rr_errors(h_errs);
+    const uint64_t NC = h_nc;
+    const uint32_t NT = h_nt, ND = h_nd;
     const int qb = bits_for(nq ? nq - 1 : 0), rb = std::max(1, bits_for(ND ? ND - 1 : 0)), tb = std::max(1, bits_for(NT ? NT - 1 : 0));
-    const RcParams prm{ ri->started_at, ri->test_dep, ri->test_status, (uint32_t)(ri->flags & ACC_FULL_EXECUTES_AFTER) };
     if (NC && qb + rb + tb > 64) fail(ACC_E_CAP, "too many queries / ranges / TxnIds for the (query, range, TxnId) key");
 
     // ---- 3. count / emit
@@ -891,9 +866,10 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     } else {
         ACC_HIP(hipMemsetAsync(chunk_eoff, 0, 8, st));
     }
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, chunk_eoff + NC, 8, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t E = ctx->pinned[0];
+    ReadBack rb_ent(ctx);
+    const auto h_e = rb_ent.u64(chunk_eoff + NC);
+    rb_ent.wait();
+    const uint64_t E = h_e;
     if (E >= 0xFFFFFFFFull) fail(ACC_E_CAP, "more than 2^32-1 range recovery-scan entries in one call");
     uint64_t *ent = ctx->get<uint64_t>("rr_ent", E);
     if (E) launch_waves(ctx, "rr_emit", k_rr_scan<true>, NC, NC, c, Q, prm, ch, (uint32_t *)nullptr,
@@ -908,9 +884,10 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
         uint32_t *fi = ctx->get<uint32_t>("rr_efi", E);
         launch(ctx, "rr_uniq", k_rr_uniq, dim3(grid_for(E, BLOCK)), dim3(BLOCK), 0, E, (const uint64_t *)so.keys, f);
         scan<uint32_t, OpAdd<uint32_t>>(ctx, f, fi, E, false);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, fi + E - 1, 4, hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        U = reinterpret_cast<uint32_t *>(ctx->pinned)[0];
+        ReadBack rb_uniq(ctx);
+        const auto h_u = rb_uniq.u32(fi + E - 1);
+        rb_uniq.wait();
+        U = h_u;
         uint64_t *ukw = ctx->get<uint64_t>("rr_uk", U);
         launch(ctx, "rr_compact", k_rr_compact, dim3(grid_for(E, BLOCK)), dim3(BLOCK), 0, E, (const uint64_t *)so.keys,
                (const uint32_t *)f, (const uint32_t *)fi, ukw);
@@ -930,9 +907,10 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
     }
     launch(ctx, "rr_qoff", k_rr_qoff, dim3(grid_for((size_t)nq + 1, BLOCK)), dim3(BLOCK), 0, nq, U, uk, rb + tb,
            (const uint32_t *)gexcl, eoff, rd_off, arena_off);
-    ACC_HIP(hipMemcpyAsync(ctx->pinned, gexcl + U, 4, hipMemcpyDeviceToHost, st));
-    ctx->sync();
-    const uint64_t G = reinterpret_cast<uint32_t *>(ctx->pinned)[0];
+    ReadBack rb_groups(ctx);
+    const auto h_g = rb_groups.u32(gexcl + U);
+    rb_groups.wait();
+    const uint64_t G = h_g;
     int32_t *arena = ctx->get<int32_t>("rr_arena", G + U);
     uint32_t *range_id = ctx->get<uint32_t>("rr_range_id", G);
     uint32_t *dep_txn = ctx->get<uint32_t>("rr_dep_txn", U);
@@ -953,9 +931,10 @@ void map_reduce_full_ranges(acc_ctx *ctx, const acc_range_cmds_in *ci, const acc
                (const uint32_t *)s2.vals, tb, (const uint32_t *)uf, (const uint32_t *)ux, (const uint64_t *)eoff,
                (const uint64_t *)rd_off, (const uint64_t *)arena_off, (const uint64_t *)u_off, (const uint32_t *)first_of, arena,
                dep_txn);
-        ACC_HIP(hipMemcpyAsync(ctx->pinned, ux + U, 4, hipMemcpyDeviceToHost, st));
-        ctx->sync();
-        TU = reinterpret_cast<uint32_t *>(ctx->pinned)[0];
+        ReadBack rb_txns(ctx);
+        const auto h_tu = rb_txns.u32(ux + U);
+        rb_txns.wait();
+        TU = h_tu;
     } else {
         ACC_HIP(hipMemsetAsync(u_off, 0, ((size_t)nq + 1) * 8, st));
     }
