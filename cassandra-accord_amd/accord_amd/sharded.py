@@ -36,11 +36,9 @@ def shard_batch(batch: Batch, bounds: np.ndarray, rank: int) -> Batch:
     lo, hi = np.uint64(bounds[rank]), np.uint64(bounds[rank + 1])
     kc = batch.key_code
     keep = (kc >= lo) & (kc < hi)
-    counts = np.add.reduceat(keep.astype(np.int64), batch.key_off[:-1].astype(np.int64)) if len(kc) else \
-        np.zeros(batch.n_txn, np.int64)
-    # reduceat misbehaves on empty segments: fix them
-    empty = np.diff(batch.key_off.astype(np.int64)) == 0
-    counts[empty] = 0
+    # (a prefix sum, not reduceat: txns without keys are empty segments, and trailing ones index past the end)
+    kept = np.concatenate([[0], np.cumsum(keep, dtype=np.int64)])
+    counts = np.diff(kept[batch.key_off.astype(np.int64)])
     off = np.zeros(batch.n_txn + 1, dtype=np.uint32)
     np.cumsum(counts, out=off[1:])
     return Batch(batch.txn_msb, batch.txn_lsb, batch.txn_node, batch.exe_msb, batch.exe_lsb, batch.exe_node,
@@ -463,31 +461,51 @@ class Comm:
         return cls(ctx, h)
 
     @classmethod
-    def host(cls, ctx, world: int, rank: int, group=None):
+    def host_fn(cls, ctx, world: int, rank: int, fn):
+        """The host transport over a Python callable: fn(send, send_bytes, recv_bytes) -> the received bytes, or None
+        for a transport failure (the C callback then returns 1 and the reduce ends with ACC_E_STATE, as it does when fn
+        raises or returns another length than sum(recv_bytes)). send: a uint8 array owned by the call, send_bytes[d]
+        bytes for each rank d in rank order; recv_bytes[s]: the bytes expected from each rank s; the result holds them
+        in rank order. A reduce calls it twice: the size exchange, then the data."""
         import ctypes as C
-        import torch
-        import torch.distributed as dist
         from . import _lib as L
 
         def a2av(user, send, send_bytes, recv, recv_bytes):
             try:
                 sb = [int(send_bytes[i]) for i in range(world)]
                 rbytes = [int(recv_bytes[i]) for i in range(world)]
-                src = np.ctypeslib.as_array((C.c_uint8 * max(sum(sb), 1)).from_address(send)) if sum(sb) else \
+                src = np.ctypeslib.as_array((C.c_uint8 * sum(sb)).from_address(send)).copy() if sum(sb) else \
                     np.zeros(0, np.uint8)
-                out = torch.empty(sum(rbytes), dtype=torch.uint8)
-                dist.all_to_all_single(out, torch.from_numpy(src[:sum(sb)].copy()), output_split_sizes=rbytes,
-                                       input_split_sizes=sb, group=group)
+                out = fn(src, sb, rbytes)
+                if out is None:
+                    return 1
+                out = np.ascontiguousarray(out).view(np.uint8).reshape(-1) if isinstance(out, np.ndarray) else \
+                    np.frombuffer(out, dtype=np.uint8)
+                if len(out) != sum(rbytes):
+                    return 1
                 if sum(rbytes):
-                    C.memmove(recv, out.numpy().ctypes.data, sum(rbytes))
+                    C.memmove(recv, out.ctypes.data, sum(rbytes))
                 return 0
             except Exception:  # noqa: BLE001 - reported to the library as a transport failure
                 return 1
 
-        fn = L.AllToAllvFn(a2av)
+        cb = L.AllToAllvFn(a2av)
         h = C.c_void_p()
-        ctx.check(ctx._lib.acc_comm_init_host(ctx.handle, world, rank, fn, None, C.byref(h)))
-        return cls(ctx, h, keep=fn)
+        ctx.check(ctx._lib.acc_comm_init_host(ctx.handle, world, rank, cb, None, C.byref(h)))
+        return cls(ctx, h, keep=cb)
+
+    @classmethod
+    def host(cls, ctx, world: int, rank: int, group=None):
+        import torch
+        import torch.distributed as dist
+
+        def a2av(send, sb, rbytes):
+            out = torch.empty(sum(rbytes), dtype=torch.uint8)
+            dist.all_to_all_single(out, torch.from_numpy(send), output_split_sizes=rbytes, input_split_sizes=sb,
+                                   group=group)
+            return out.numpy()
+
+        return cls.host_fn(ctx, world, rank, a2av)
 
     def close(self):
         if self.handle:

@@ -237,6 +237,23 @@ static void add_key_streams(acc_ctx *ctx, const acc_batch_in *in, const uint32_t
     S.ns = 1;
 }
 
+// A store's placement must stay below n_global: the slot bitmap of a message (fragwire.hip) and the dest-major slot
+// tables of range_pack / covering_pack are sized from n_global and indexed by txn_global[i]. The placement is increasing
+// (a store's txns are a TxnId-ordered subsequence; acc_shard_pack relies on that too), so its last entry bounds them all.
+static void check_placement(acc_ctx *ctx, const uint32_t *txn_global, uint32_t n, uint32_t mem, uint32_t n_global)
+{
+    if (!txn_global || !n) return;
+    if (mem != ACC_MEM_DEVICE && mem != ACC_MEM_HOST) fail(ACC_E_ARG, "bad mem");
+    uint32_t last = 0;
+    if (mem == ACC_MEM_HOST) last = txn_global[n - 1];
+    else {
+        ACC_HIP(hipMemcpyAsync(ctx->pinned, txn_global + (n - 1), 4, hipMemcpyDeviceToHost, ctx->stream));
+        ctx->sync();
+        memcpy(&last, ctx->pinned, 4);
+    }
+    if (last >= n_global) fail(ACC_E_ARG, "txn_global holds an index that is not below n_global");
+}
+
 static void merge_key_streams(acc_ctx *ctx, acc_comm *c, uint32_t n_global, const Streams &S, acc_merge_view *view)
 {
     acc_frag_recv fr{};
@@ -251,6 +268,7 @@ void shard_reduce(acc_ctx *ctx, acc_comm *c, const acc_batch_in *in, const uint3
     if (!c || !in || !view) fail(ACC_E_ARG, "null argument");
     if (c->ctx != ctx) fail(ACC_E_ARG, "communicator belongs to another context");
     if (!txn_global && n_global < in->n_txn) fail(ACC_E_ARG, "n_global must be >= n_txn when txn_global is null");
+    check_placement(ctx, txn_global, in->n_txn, in->mem, n_global);
     Streams S;
     add_key_streams(ctx, in, txn_global, c->world, n_global, S);
     exchange_streams(c, S);
@@ -280,6 +298,7 @@ void partial_deps_reduce(acc_ctx *ctx, acc_comm *c, const acc_range_batch_in *in
     // without a placement the batch index is the global index: one check for every call form (with or without a
     // covering), so the key / range results never depend on whether a covering is passed
     if (!txn_global && n_global < in->n_txn) fail(ACC_E_ARG, "n_global must be >= n_txn when txn_global is null");
+    check_placement(ctx, txn_global, in->n_txn, in->mem, n_global);
     const acc_batch_in kin{ in->n_txn, in->mem, in->n_pairs, in->txn_id, in->execute_at, in->status, in->key_off, in->key_code };
     Streams S;
     add_key_streams(ctx, &kin, txn_global, c->world, n_global, S);

@@ -16,6 +16,22 @@
 //     subset of the txn's TxnIds, RelationMultiMap), omitted for one key (its list is every TxnId).
 // A message (one per destination) = a 64-B header, then the sections slots / counts / keys / TxnIds / key bits, each
 // 8-B aligned. The receiver rebuilds acc_shard_pack's four streams in source order and runs acc_shard_merge on them.
+//
+// The header, 16 little-endian u32 words:
+//   word 0      magic 0x4B464341 (the bytes "ACFK")
+//   word 1      flags: bit 0 F_SLOT_LIST (slots are a u32 list, ascending, one per fragment; clear: a bitmap of G bits,
+//               bit g of the section = bit g % 32 of its u32 word g / 32), bit 1 F_WIDE_CNT (counts are u32 triples;
+//               clear: u16), bit 2 F_WIDE_KEY (keys are u64 codes; clear: u32 offsets from kbase); other bits are zero
+//   word 2      nfrag, the fragments in the message
+//   word 3      G = ceil(max(n_global, 1) / world), the slots of one home rank
+//   words 4-5   kbase (low word first): the message's smallest key code, 0 without keys
+//   words 6-15  the byte sizes of the five sections as u64 (low word first), each a multiple of 8: slots (the list or
+//               the bitmap's ceil(G / 32) words; empty without fragments), counts (nk, nv, TxnId bytes per fragment),
+//               keys (all fragments', fragment order), TxnIds (each fragment's varints, back to back), key bits (each
+//               fragment's nk x nv matrix, bit k * nv + e = bit (k * nv + e) % 8 of its byte (k * nv + e) / 8, padded
+//               to whole bytes per fragment)
+// Fragments are in ascending slot order. The receiver checks what a header alone can tell (magic, flags, G, the slot
+// and count section sizes against nfrag, the sizes against the message length) on the host before it launches anything.
 #include "prims.hpp"
 
 #include <vector>
@@ -481,6 +497,7 @@ void frag_decode(acc_ctx *ctx, uint32_t W, uint32_t rank, uint32_t n_global, con
     ctx->sync();
     std::vector<Msg> msg(W);
     uint64_t F = 0, NW = 0;
+    const uint32_t G = (std::max(n_global, 1u) + W - 1) / W;   // as the senders derive it (acc_shard_reduce)
     for (uint32_t s = 0; s < W; ++s) {
         const uint32_t *hw = ph + (size_t)s * HDR_WORDS;
         if (hw[0] != MAGIC) fail(ACC_E_STATE, "not a fragment message");
@@ -488,11 +505,19 @@ void frag_decode(acc_ctx *ctx, uint32_t W, uint32_t rank, uint32_t n_global, con
         m.flags = hw[1]; m.nfrag = hw[2]; m.G = hw[3];
         m.kbase = hw[4] | ((uint64_t)hw[5] << 32);
         uint64_t sz[5];
-        for (int q = 0; q < 5; ++q) sz[q] = hw[6 + 2 * q] | ((uint64_t)hw[7 + 2 * q] << 32);
+        for (int q = 0; q < 5; ++q) {
+            sz[q] = hw[6 + 2 * q] | ((uint64_t)hw[7 + 2 * q] << 32);
+            if (sz[q] > nb[s]) fail(ACC_E_STATE, "fragment message size does not match its header");   // (no wrapped sum)
+        }
         m.base = rb[s];
         m.slot = HDR_WORDS * 4; m.cnt = m.slot + sz[0]; m.key = m.cnt + sz[1]; m.val = m.key + sz[2]; m.kbm = m.val + sz[3];
         m.end = m.kbm + sz[4];
         if (m.end != nb[s]) fail(ACC_E_STATE, "fragment message size does not match its header");
+        if (m.flags & ~(uint32_t)(F_SLOT_LIST | F_WIDE_CNT | F_WIDE_KEY)) fail(ACC_E_STATE, "fragment message with unknown flags");
+        if (m.G != G) fail(ACC_E_STATE, "fragment message for another global txn count");
+        const uint64_t slots = !m.nfrag ? 0 : (m.flags & F_SLOT_LIST) ? 4ull * m.nfrag : 4ull * ((G + 31) / 32);
+        if (sz[0] != al8(slots) || sz[1] != al8((uint64_t)m.nfrag * ((m.flags & F_WIDE_CNT) ? 12 : 6)))
+            fail(ACC_E_STATE, "fragment message sections do not match its fragment count");
         m.f0 = F;
         m.w0 = NW;
         F += m.nfrag;

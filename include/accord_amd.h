@@ -565,7 +565,9 @@ int acc_shard_merge(acc_ctx *ctx, const acc_frag_recv *in, acc_merge_view *out_v
  * acc_shard_reduce: PreAccept.reduce of the store KeyDeps (messages/PreAccept.java:141-156, PartialDeps.with) for the
  * last acc_keydeps_batch on ctx over `in` (the same batch): acc_shard_pack, one exchange of the element counts, one
  * all-to-all(v) of the four fragment streams, acc_shard_merge; every rank calls it (collective). txn_global / n_global
- * as acc_frag_streams.txn_global and the global txn count; the result is acc_shard_merge's view. */
+ * as acc_frag_streams.txn_global and the global txn count; the result is acc_shard_merge's view. Every txn_global entry
+ * must be below n_global (the placement is increasing, so its last entry is checked): ACC_E_ARG otherwise, here and in
+ * acc_partial_deps_reduce, before anything is sent. */
 #define ACC_COMM_ID_BYTES 128
 typedef struct acc_comm acc_comm;
 typedef int (*acc_alltoallv_fn)(void *user, const void *send, const uint64_t *send_bytes, void *recv,
