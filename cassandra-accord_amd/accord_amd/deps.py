@@ -546,6 +546,23 @@ def _rmm_in(half, keep: list) -> "L.RmmIn":
                    p("k2v_off"), p("k2v"))
 
 
+def _rmm_in_device(half) -> "L.RmmIn":
+    """acc_rmm_in over one half whose arrays are already on the context's device: the fields of _rmm_in as tensors
+    (anything with data_ptr() and element_size(), e.g. torch tensors), which the caller keeps alive over the call."""
+    if half is None:
+        return L.RmmIn()
+
+    def p(k):
+        t = half.get(k)
+        if t is None:
+            return None
+        if t.element_size() != np.dtype(dict(RMM_FIELDS)[k]).itemsize:
+            raise TypeError(f"device array {k}: {t.element_size()}-byte elements")
+        return t.data_ptr() or None
+    return L.RmmIn(p("key_off"), p("key_a"), p("key_b"), p("val_off"), L.TsCols(p("msb"), p("lsb"), p("node")),
+                   p("k2v_off"), p("k2v"))
+
+
 def rmm_copy_out(ctx: Context, n_groups: int, view: "L.RmmView", with_b: bool) -> dict:
     """Host copy of one acc_rmm_view (acc_rmm_copy_out, two-call sizing)."""
     out = L.RmmOut()
@@ -725,11 +742,12 @@ def rangedeps_stab(ctx: Context, m: dict, grp, q_start, q_end=None, end_inclusiv
 # ---------------------------------------------------------------- LatestDeps (recovery merge)
 
 def latest_deps_merge(ctx: Context, groups, key_objs: dict | None, range_objs: dict | None, end_inclusive: bool = True,
-                      commit: bool = False, txn_ids=None, execute_ats=None) -> dict:
+                      commit: bool = False, txn_ids=None, execute_ats=None, deps_on_device: bool = False) -> dict:
     """LatestDeps.mergeProposal / mergeCommit (primitives/LatestDeps.java:306-326) for every recovering txn
     (acc_latest_deps_merge). groups[g] = the replies, each a list of intervals (start, end, KnownDeps ordinal,
     ballot (msb, lsb, node), coordinatedDeps id, localDeps id) with ids into the deps objects (-1 = null); key_objs /
-    range_objs = the objects' halves in the Deps.merge layout (one slot per id). Returns dict(key=..., range=...,
+    range_objs = the objects' halves in the Deps.merge layout (one slot per id); with deps_on_device their arrays are
+    device tensors and go in as they are (deps_mem = ACC_MEM_DEVICE). Returns dict(key=..., range=...,
     sufficient=[[(start, end)...] per group])."""
     keep = []
     grp_off, iv_off = [0], [0]
@@ -755,8 +773,10 @@ def latest_deps_merge(ctx: Context, groups, key_objs: dict | None, range_objs: d
     nd = max(len(key_objs["key_off"]) - 1 if key_objs else 0, len(range_objs["key_off"]) - 1 if range_objs else 0)
     li = L.LatestIn(ng, L.ACC_LATEST_COMMIT if commit else L.ACC_LATEST_PROPOSAL, p(a["grp"]), p(a["ivo"]), p(a["s"]),
                     p(a["e"]), p(a["known"]), L.TsCols(p(a["bm"]), p(a["bl"]), p(a["bn"])), p(a["cd"]), p(a["ld"]),
-                    L.TsCols(*(p(x) for x in tid)), L.TsCols(*(p(x) for x in exe)), int(end_inclusive), L.ACC_MEM_HOST,
-                    nd, _rmm_in(key_objs, keep), _rmm_in(range_objs, keep))
+                    L.TsCols(*(p(x) for x in tid)), L.TsCols(*(p(x) for x in exe)), int(end_inclusive),
+                    L.ACC_MEM_DEVICE if deps_on_device else L.ACC_MEM_HOST, nd,
+                    _rmm_in_device(key_objs) if deps_on_device else _rmm_in(key_objs, keep),
+                    _rmm_in_device(range_objs) if deps_on_device else _rmm_in(range_objs, keep))
     v = L.LatestView()
     ctx.check(ctx._lib.acc_latest_deps_merge(ctx.handle, C.byref(li), C.byref(v)))
     ns = int(v.total_sufficient)

@@ -229,10 +229,26 @@ def _slice_half(objs, items, is_range, end_inclusive):
     return h
 
 
+def _empty_objects(nd, is_range):
+    """nd deps objects without keys or TxnIds: what a null half (every Deps' KeyDeps / RangeDeps NONE) stands for"""
+    z = np.zeros(nd + 1, np.uint64)
+    h = dict(key_off=z, key_a=np.zeros(0, np.uint64), val_off=z, msb=np.zeros(0, np.uint64), lsb=np.zeros(0, np.uint64),
+             node=np.zeros(0, np.int32), k2v_off=z, k2v=np.zeros(0, np.int32))
+    if is_range:
+        h["key_b"] = np.zeros(0, np.uint64)
+    return h
+
+
 def latest_deps_merge(groups, key_objs, range_objs, end_inclusive=True, commit=False, use_local=None):
     """groups: per recovering txn the replies (lists of intervals, see fold_group); key_objs / range_objs: the deps
-    objects' halves (merge-half dicts, one slot per deps id). use_local[g] = txnId.equals(executeAt) (commit).
+    objects' halves (merge-half dicts, one slot per deps id; None = a half of empty objects). use_local[g] =
+    txnId.equals(executeAt) (commit).
     Returns dict(key=merged half, range=merged half, sufficient=[[(s, e)...] per group], items=[[...] per group])."""
+    nd = max(len(h["key_off"]) - 1 if h is not None else 0 for h in (key_objs, range_objs))
+    if key_objs is None:
+        key_objs = _empty_objects(nd, False)
+    if range_objs is None:
+        range_objs = _empty_objects(nd, True)
     all_items, grp_off, suff, per = [], [0], [], []
     for g, replies in enumerate(groups):
         its, sf = items_of(fold_group(replies), commit, bool(use_local[g]) if commit else False)
