@@ -1170,13 +1170,8 @@ class CfkStore:
         takes the pointwise max; every stored key whose bound rose drops its entries below the bound and trims the
         missing[] of the rest; the view and the missing[] indices are rebuilt. Later apply_deps calls ignore deps below
         a key's bound."""
-        a = dict(rs=np.ascontiguousarray(ranges["rng_start"], dtype=np.uint64),
-                 re=np.ascontiguousarray(ranges["rng_end"], dtype=np.uint64),
-                 bm=np.ascontiguousarray(ranges["msb"], dtype=np.uint64), bl=np.ascontiguousarray(ranges["lsb"], dtype=np.uint64),
-                 bn=np.ascontiguousarray(ranges["node"], dtype=np.int32))
-        p = lambda k: a[k].ctypes.data  # noqa: E731
-        ri = L.CfkRedundantIn(L.ACC_MEM_HOST, len(a["rs"]), int(end_inclusive), p("rs"), p("re"),
-                              L.TsCols(p("bm"), p("bl"), p("bn")))
+        keep = []
+        ri = _redundant_in(ranges, end_inclusive, keep)
         self.ctx.check(self.ctx._lib.acc_cfk_redundant_before(self.ctx.handle, self._h, C.byref(ri)))
 
     def redundant_map(self) -> dict:
@@ -1184,16 +1179,32 @@ class CfkStore:
         intervals over the key codes, ascending and disjoint; msb, lsb, node: each interval's shardRedundantBefore)."""
         m = L.CfkRedundantMap()
         self.ctx.check(self.ctx._lib.acc_cfk_redundant_view(self.ctx.handle, self._h, C.byref(m)))
-        n = int(m.n)
-        g = lambda ptr, dt: device_array(self.ctx, ptr, n, dt)  # noqa: E731
-        return dict(end_inclusive=int(m.end_inclusive), st=g(m.st, np.uint64), en=g(m.en, np.uint64),
-                    msb=g(m.bound.msb, np.uint64), lsb=g(m.bound.lsb, np.uint64), node=g(m.bound.node, np.int32))
+        return _redundant_map_out(self.ctx, m)
 
     def missing_view(self) -> "L.CfkBatchView":
         """The store's txn-major view with each pair's missing[] as txn indices (device), for cfk_map_reduce_full."""
         bv = L.CfkBatchView()
         self.ctx.check(self.ctx._lib.acc_cfk_missing(self.ctx.handle, self._h, C.byref(bv)))
         return bv
+
+
+def _redundant_in(ranges: dict, end_inclusive: int, keep: list) -> "L.CfkRedundantIn":
+    """The redundant_before dict as an acc_cfk_redundant_in of host arrays (kept alive in keep)."""
+    a = dict(rs=np.ascontiguousarray(ranges["rng_start"], dtype=np.uint64),
+             re=np.ascontiguousarray(ranges["rng_end"], dtype=np.uint64),
+             bm=np.ascontiguousarray(ranges["msb"], dtype=np.uint64), bl=np.ascontiguousarray(ranges["lsb"], dtype=np.uint64),
+             bn=np.ascontiguousarray(ranges["node"], dtype=np.int32))
+    p = lambda k: a[k].ctypes.data  # noqa: E731
+    keep.append(a)
+    return L.CfkRedundantIn(L.ACC_MEM_HOST, len(a["rs"]), int(end_inclusive), p("rs"), p("re"), L.TsCols(p("bm"), p("bl"), p("bn")))
+
+
+def _redundant_map_out(ctx: Context, m: "L.CfkRedundantMap") -> dict:
+    """Host copy of an acc_cfk_redundant_map."""
+    n = int(m.n)
+    g = lambda ptr, dt: device_array(ctx, ptr, n, dt) if n else np.zeros(0, dt)  # noqa: E731
+    return dict(end_inclusive=int(m.end_inclusive), st=g(m.st, np.uint64), en=g(m.en, np.uint64),
+                msb=g(m.bound.msb, np.uint64), lsb=g(m.bound.lsb, np.uint64), node=g(m.bound.node, np.int32))
 
 
 def _mixed_queries_in(q: dict, end_inclusive: int, lane_seg: int, keep: list) -> "L.CfkMixedQueries":
@@ -1324,8 +1335,24 @@ class RangeCmdStore:
         self.ctx.check(self.ctx._lib.acc_rcmd_map_reduce_full(self.ctx.handle, self._h, C.byref(ri), C.byref(view)))
         return self.ctx.copy_out_range(view)
 
+    def redundant_before(self, ranges: dict):
+        """Advance the store's RedundantBefore (acc_rcmd_redundant_before; InMemoryCommandStore.markShardDurable,
+        impl/InMemoryCommandStore.java:346-370): ranges = the dict CfkStore.redundant_before takes, by the store's own
+        bound type. The map takes the pointwise max; every non-erased command below a range's bound loses that range
+        from its ranges, and leaves the table when none is left. Later updates register only what the map's bounds
+        above their TxnId leave of their ranges."""
+        keep = []
+        ri = _redundant_in(ranges, self.end_inclusive, keep)
+        self.ctx.check(self.ctx._lib.acc_rcmd_redundant_before(self.ctx.handle, self._h, C.byref(ri)))
+
+    def redundant_map(self) -> dict:
+        """Host copy of the store's RedundantBefore map (acc_rcmd_redundant_view), as CfkStore.redundant_map gives it."""
+        m = L.CfkRedundantMap()
+        self.ctx.check(self.ctx._lib.acc_rcmd_redundant_view(self.ctx.handle, self._h, C.byref(m)))
+        return _redundant_map_out(self.ctx, m)
+
     def view(self) -> "L.RcmdTable":
-        """The table as device pointers (acc_rcmd_view; valid until the next update)."""
+        """The table as device pointers (acc_rcmd_view; valid until the next update or prune that rewrites it)."""
         v = L.RcmdTable()
         self.ctx.check(self.ctx._lib.acc_rcmd_view(self.ctx.handle, self._h, C.byref(v)))
         return v
@@ -1491,6 +1518,13 @@ class ReplicaStore:
         """CommandStore.setRedundantBefore / markShardDurable for this store's CommandsForKey: ranges as
         CfkStore.redundant_before takes them, with the store's Range bound type."""
         self.cfk.redundant_before(ranges, self.end_inclusive)
+
+    def mark_shard_durable(self, ranges: dict):
+        """CommandStore.markShardDurable for both halves of the store (local/CommandStore.java:520-528 ->
+        impl/InMemoryCommandStore.java:346-370): ranges as CfkStore.redundant_before takes them, with the store's Range
+        bound type; the CommandsForKey store is pruned first, then the range-command store."""
+        self.cfk.redundant_before(ranges, self.end_inclusive)
+        self.rcmd.redundant_before(ranges)
 
     def close(self):
         self.cfk.close()

@@ -52,6 +52,8 @@ void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *
 void rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *in);
 void rcmd_state(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out);
 void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *view);
+void rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in);
+void rcmd_redundant_view(acc_rcmd *store, acc_cfk_redundant_map *out);
 }  // namespace acc
 
 namespace {
@@ -420,6 +422,21 @@ int acc_rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recove
         ACC_HIP(hipSetDevice(ctx->device));
         acc::rcmd_map_reduce_full(ctx, store, q, out_view);
     });
+}
+
+int acc_rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_redundant_before(ctx, store, in);
+    });
+}
+
+int acc_rcmd_redundant_view(acc_ctx *ctx, acc_rcmd *store, acc_cfk_redundant_map *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] { acc::rcmd_redundant_view(store, out); });
 }
 
 int acc_keydeps_copy_out(acc_ctx *ctx, acc_keydeps_out *out)

@@ -148,17 +148,6 @@ __global__ __launch_bounds__(BLOCK) void k_rb_keys_out(uint32_t nk, const uint64
     if (i + 1 == nk) oent_off[kidx[nk]] = keo[nk];
 }
 
-// Columns that move together: up to four u64, two i32 and one u8 column, element i of each to element i's destination.
-struct Cols {
-    const uint64_t *s64[4];
-    uint64_t *d64[4];
-    const int32_t *s32[2];
-    int32_t *d32[2];
-    const uint8_t *s8;
-    uint8_t *d8;
-    int n64, n32;
-};
-
 constexpr uint32_t RB_VEC = 4;   // destination elements per lane
 
 template <class T>
@@ -244,13 +233,18 @@ __global__ __launch_bounds__(BLOCK) void k_rb_segcopy(Cols c, const uint32_t *__
     }
 }
 
+}  // namespace rb
+
 // n_cap: a host-side upper bound of *n_dev (sizes the launch)
-void segcopy(acc_ctx *ctx, const char *name, const Cols &c, uint64_t n_cap, const uint32_t *n_dev, uint32_t ns, const uint32_t *doff,
-             const uint32_t *sstart)
+void rb_segcopy(acc_ctx *ctx, const char *name, const rb::Cols &c, uint64_t n_cap, const uint32_t *n_dev, uint32_t ns,
+                const uint32_t *doff, const uint32_t *sstart)
 {
+    using namespace rb;
     if (n_cap == 0 || ns == 0) return;
     launch(ctx, name, k_rb_segcopy, dim3(grid_for((n_cap + RB_VEC - 1) / RB_VEC, BLOCK)), dim3(BLOCK), 0, c, n_dev, ns, doff, sstart);
 }
+
+namespace rb {
 
 // per (update, key) pair: offsets and order validated as acc_cfk_apply does, the lower bound of RB(key) in its deps
 __global__ __launch_bounds__(BLOCK) void k_rb_dep_cut(Map mp, uint64_t NP, uint64_t ND, const uint64_t *__restrict__ key,
@@ -286,21 +280,43 @@ __global__ __launch_bounds__(BLOCK) void k_rb_dep_cut(Map mp, uint64_t NP, uint6
 
 using namespace rb;
 
-void rb_merge_map(acc_ctx *ctx, acc_maxconflicts *rb, const acc_cfk_redundant_in *in, const CfkResident &s)
+RbInput rb_stage_ranges(acc_ctx *ctx, const acc_cfk_redundant_in *in)
 {
     hipStream_t st = ctx->stream;
     const uint32_t n = in->n_ranges;
-    const uint64_t *rs = stage_in(ctx, "rb_rs", in->rng_start, n, in->mem);
-    const uint64_t *re = stage_in(ctx, "rb_re", in->rng_end, n, in->mem);
-    const uint64_t *bm = stage_in(ctx, "rb_inm", in->bound.msb, n, in->mem);
-    const uint64_t *bl = stage_in(ctx, "rb_inl", in->bound.lsb, n, in->mem);
-    const int32_t *bn = stage_in(ctx, "rb_inn", in->bound.node, n, in->mem);
+    RbInput r;
+    r.n = n;
+    r.rs = stage_in(ctx, "rb_rs", in->rng_start, n, in->mem);
+    r.re = stage_in(ctx, "rb_re", in->rng_end, n, in->mem);
+    r.bm = stage_in(ctx, "rb_inm", in->bound.msb, n, in->mem);
+    r.bl = stage_in(ctx, "rb_inl", in->bound.lsb, n, in->mem);
+    r.bn = stage_in(ctx, "rb_inn", in->bound.node, n, in->mem);
     uint64_t *errs = ctx->get<uint64_t>("rb_errs", 1);
     ACC_HIP(hipMemsetAsync(errs, 0, 8, st));
-    launch(ctx, "rb_ranges", k_rb_ranges, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, rs, re, errs);
+    launch(ctx, "rb_ranges", k_rb_ranges, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, r.rs, r.re, errs);
     ACC_HIP(hipMemcpyAsync(ctx->pinned, errs, 8, hipMemcpyDeviceToHost, st));
     ctx->sync();
     if (ctx->pinned[0] & E_RANGE) fail(ACC_E_ARG, "ranges must be sorted, non-overlapping, start < end");
+    return r;
+}
+
+void rb_merge_staged(acc_ctx *ctx, acc_maxconflicts *rb, const RbInput &r)
+{
+    const uint32_t n = r.n;
+    uint32_t *ko = ctx->get<uint32_t>("rb_uko", (size_t)n + 1), *ro = ctx->get<uint32_t>("rb_uro", (size_t)n + 1);
+    launch(ctx, "rb_mkupd", k_rb_mkupd, dim3(grid_for((size_t)n + 1, BLOCK)), dim3(BLOCK), 0, n, ko, ro);
+    acc_conflicts_in ci{};
+    ci.mem = ACC_MEM_DEVICE; ci.n_upd = n; ci.end_inclusive = rb->end_inclusive;
+    ci.n_keys = 0; ci.n_ranges = n;
+    ci.execute_at = acc_ts_cols{ r.bm, r.bl, r.bn };
+    ci.key_off = ko; ci.key = nullptr; ci.rng_off = ro; ci.rng_start = r.rs; ci.rng_end = r.re;
+    mc_update(ctx, rb, &ci);
+}
+
+void rb_merge_map(acc_ctx *ctx, acc_maxconflicts *rb, const acc_cfk_redundant_in *in, const CfkResident &s)
+{
+    hipStream_t st = ctx->stream;
+    const RbInput r = rb_stage_ranges(ctx, in);
     if (s.nk) {   // RB_old of every stored key, before the map moves
         uint64_t *om = ctx->get<uint64_t>("rb_kbm", s.nk), *ol = ctx->get<uint64_t>("rb_kbl", s.nk);
         int32_t *on = ctx->get<int32_t>("rb_kbn", s.nk);
@@ -312,14 +328,7 @@ void rb_merge_map(acc_ctx *ctx, acc_maxconflicts *rb, const acc_cfk_redundant_in
             ACC_HIP(hipMemsetAsync(on, 0, (size_t)s.nk * 4, st));
         }
     }
-    uint32_t *ko = ctx->get<uint32_t>("rb_uko", (size_t)n + 1), *ro = ctx->get<uint32_t>("rb_uro", (size_t)n + 1);
-    launch(ctx, "rb_mkupd", k_rb_mkupd, dim3(grid_for((size_t)n + 1, BLOCK)), dim3(BLOCK), 0, n, ko, ro);
-    acc_conflicts_in ci{};
-    ci.mem = ACC_MEM_DEVICE; ci.n_upd = n; ci.end_inclusive = rb->end_inclusive;
-    ci.n_keys = 0; ci.n_ranges = n;
-    ci.execute_at = acc_ts_cols{ bm, bl, bn };
-    ci.key_off = ko; ci.key = nullptr; ci.rng_off = ro; ci.rng_start = rs; ci.rng_end = re;
-    mc_update(ctx, rb, &ci);
+    rb_merge_staged(ctx, rb, r);
 }
 
 RbPruned rb_prune(acc_ctx *ctx, const acc_maxconflicts *rb, const CfkResident &s, uint64_t ne, uint64_t nm, acc_cfk_snap_view *view)
@@ -381,12 +390,12 @@ RbPruned rb_prune(acc_ctx *ctx, const acc_maxconflicts *rb, const CfkResident &s
     ce.s32[0] = s.en; ce.s32[1] = s.xn; ce.d32[0] = oen; ce.d32[1] = oxn;
     ce.s8 = s.st; ce.d8 = ost;
     ce.n64 = 4; ce.n32 = 2;
-    segcopy(ctx, "rb_copy_ent", ce, r.ne, keo + nk, r.nk, oeo, osrc);
+    rb_segcopy(ctx, "rb_copy_ent", ce, r.ne, keo + nk, r.nk, oeo, osrc);
     Cols cm{};
     cm.s64[0] = s.mm; cm.s64[1] = s.ml; cm.d64[0] = omm; cm.d64[1] = oml;
     cm.s32[0] = s.mn; cm.d32[0] = omn;
     cm.n64 = 2; cm.n32 = 1;
-    segcopy(ctx, "rb_copy_miss", cm, r.nm, omoff + ne, (uint32_t)r.ne, omoff, msrc);
+    rb_segcopy(ctx, "rb_copy_miss", cm, r.nm, omoff + ne, (uint32_t)r.ne, omoff, msrc);
     view->n_keys = r.nk; view->n_entries = r.ne; view->n_missing = r.nm;
     view->key = okey; view->ent_off = oeo;
     view->txn_id = acc_ts_cols{ oem, oel, oen };
@@ -441,7 +450,7 @@ uint64_t rb_trim_deps(acc_ctx *ctx, const acc_maxconflicts *rb, const acc_cfk_up
     c.s64[0] = d.deps.msb; c.s64[1] = d.deps.lsb; c.d64[0] = ndm; c.d64[1] = ndl;
     c.s32[0] = d.deps.node; c.d32[0] = ndn;
     c.n64 = 2; c.n32 = 1;
-    segcopy(ctx, "rb_copy_deps", c, nd2, ndoff + NP, (uint32_t)NP, ndoff, cut);
+    rb_segcopy(ctx, "rb_copy_deps", c, nd2, ndoff + NP, (uint32_t)NP, ndoff, cut);
     out->n_deps = nd2;
     out->dep_off = ndoff;
     out->deps = acc_ts_cols{ ndm, ndl, ndn };

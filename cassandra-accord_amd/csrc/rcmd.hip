@@ -39,8 +39,25 @@
 // candidates of each participant; k_rcr_filter, a wave per participant, tests each candidate's command (recovery_pred.hpp,
 // the predicate acc_map_reduce_full_ranges evaluates) and compacts the survivors in place in the participant's span;
 // rd_build_txns as it is builds the result.
+// acc_rcmd_redundant_before (InMemoryCommandStore.markShardDurable, impl/InMemoryCommandStore.java:346-370, once per
+// distinct bound of the input): the input validated and max-merged into the store's RedundantBefore map (the
+// acc_maxconflicts form and the two steps of cfkredundant.hpp), then the prune, count -> scan -> emit:
+//   1. k_rp_lim, a thread per input range: lim[j] = #stored TxnIds < bound[j] (the table is in compareTo order, so
+//      "C below bound j" is row < lim[j]); max lim beside it;
+//   2. k_rp_rowner, a thread per row: the owner row of every stored range;
+//   3. k_rp_cut<false>, a thread per stored range: the first input range that ends above its start by binary search, then
+//      the walk over the intersecting input ranges, those with row >= lim[j] skipped: its surviving pieces counted;
+//   4. one scan of the piece counts; k_rp_rows, a thread per row: its new range count, keep = erased || row >= max lim ||
+//      count > 0; one scan (four arrays) of keep, the kept rows' range counts and dep counts, and the cut flags;
+//   5. one read-back: the three new sizes and the rows cut. Nothing cut or dropped: nothing is rewritten;
+//   6. k_rp_write, a thread per row (every row column, the new offsets, the deps' segments); k_rp_cut<true>, the walk of
+//      3. again, writing the pieces with their owner, entry flag and the OR masks; the deps by the segmented copy of
+//      cfkredundant.hip; then the index and the adoption as an update ends (finish_table).
+// Under a non-empty map the updates' ranges are trimmed first (trim_delta): k_rt_owner, k_rt_trim<false>, a scan,
+// k_rt_off, one read-back and, if any range changed, k_rt_trim<true>; the fold then runs on the trimmed columns.
 // Integer work only: HBM/latency bound, no MFMA.
 
+#include "cfkredundant.hpp"
 #include "rangedeps.hpp"
 #include "ranges_with.hpp"
 #include "recovery_pred.hpp"
@@ -79,6 +96,9 @@ struct acc_rcmd {
     uint32_t *cls = nullptr;
     // byte sizes of the arrays above in declaration order (adopted from the context: they differ from the counts)
     size_t bytes[26] = {};
+    // acc_rcmd_redundant_before: the store's RedundantBefore map (key code -> shardAppliedOrInvalidatedBefore), created
+    // by the first accepted call
+    acc_maxconflicts *rb = nullptr;
 };
 
 namespace acc {
@@ -416,6 +436,236 @@ __global__ __launch_bounds__(BLOCK) void k_rc_write(uint32_t n2, Delta d, Table 
     }
 }
 
+// ---------------------------------------------------------------- RedundantBefore: the prune
+
+// the input of one acc_rcmd_redundant_before on the device, with lim[j] = #stored TxnIds < bound[j]
+struct Bounds {
+    uint32_t m;
+    const uint64_t *rs, *re;
+    const uint32_t *lim;
+};
+
+// g[0] = max lim
+__global__ __launch_bounds__(BLOCK) void k_rp_lim(uint32_t m, const uint64_t *__restrict__ bm, const uint64_t *__restrict__ bl,
+                                                  const int32_t *__restrict__ bn, Table s, uint32_t *__restrict__ lim,
+                                                  uint64_t *__restrict__ g)
+{
+    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
+    uint32_t lo = 0;
+    if (j < m) {
+        const uint64_t xm = bm[j], xl = bl[j];
+        const int32_t xn = bn[j];
+        uint32_t hi = s.n;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
+        }
+        lim[j] = lo;
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) lo = max(lo, shfl_xor(lo, dd));
+    if (lane_id() == 0 && lo) atomicMax((unsigned long long *)&g[0], (unsigned long long)lo);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_rp_rowner(uint32_t n, const uint32_t *__restrict__ rng_off, uint32_t *__restrict__ rowner)
+{
+    const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
+    if (x >= n) return;
+    for (uint32_t k = rng_off[x]; k < rng_off[x + 1]; ++k) rowner[k] = x;
+}
+
+// the first input range that ends above a (the input is sorted and disjoint: its ends ascend)
+__device__ __forceinline__ uint32_t first_above(const uint64_t *__restrict__ re, uint32_t m, uint64_t a)
+{
+    uint32_t lo = 0, hi = m;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (re[mid] <= a) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// What the prune's second pass writes per kept row and per new range.
+struct Pruned {
+    const uint64_t *poff;    // [R + 1] exclusive scan of the piece counts
+    const uint64_t *kidx;    // [n + 1] exclusive scan of keep: the new row
+    const uint64_t *roff;    // [n + 1] exclusive scan of the kept rows' range counts
+    uint64_t *rs, *re;       // the new table's ranges
+    uint32_t *rowner, *eflag;
+};
+
+// Stored range k = (a, b) of row r minus the input ranges j with r < lim[j] (AbstractRanges.subtract: its maximal pieces
+// outside them, in order, none empty). Rows at or above max lim keep their ranges as they are. WRITE == false: cnt[k] =
+// the pieces, chg[r] = 1 where they are not (a, b) itself. WRITE: the pieces at roff[r] + (poff[k] - poff[first range
+// of r]), with the new row as owner, and the OR of the starts and ends (g[2], g[3]).
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK) void k_rp_cut(uint32_t R, Table s, const uint32_t *__restrict__ rowner, Bounds in,
+                                                  uint64_t *__restrict__ cnt, uint32_t *__restrict__ chg, Pruned o,
+                                                  uint64_t *__restrict__ g)
+{
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    uint64_t ms = 0, me = 0;
+    if (k < R) {
+        const uint32_t r = rowner[k];
+        const uint32_t maxlim = (uint32_t)g[0];
+        const uint64_t a = s.rs[k], b = s.re[k];
+        uint64_t dst = 0;
+        uint32_t x = 0;
+        if constexpr (WRITE) {
+            x = (uint32_t)o.kidx[r];
+            dst = o.roff[r] + (o.poff[k] - o.poff[s.rng_off[r]]);
+        }
+        uint32_t pieces = 0;
+        bool same = true;
+        auto piece = [&](uint64_t ps, uint64_t pe) {
+            if constexpr (WRITE) {
+                o.rs[dst] = ps; o.re[dst] = pe;
+                o.rowner[dst] = x; o.eflag[dst] = 1u;
+                ms |= ps; me |= pe;
+                ++dst;
+            }
+            ++pieces;
+        };
+        if (r >= maxlim) piece(a, b);
+        else {
+            uint64_t cur = a;
+            bool open = true;   // cur < b: something of the range is still uncovered
+            for (uint32_t j = first_above(in.re, in.m, a); j < in.m && in.rs[j] < b; ++j) {
+                if (r >= in.lim[j]) continue;
+                if (cur < in.rs[j]) piece(cur, in.rs[j]);
+                same = false;
+                if (in.re[j] >= b) { open = false; break; }
+                cur = in.re[j];
+            }
+            if (open) piece(cur, b);
+        }
+        if constexpr (!WRITE) {
+            cnt[k] = pieces;
+            if (!same) chg[r] = 1u;
+        }
+    }
+    if constexpr (WRITE) {
+#pragma unroll
+        for (int dd = 32; dd >= 1; dd >>= 1) { ms |= shfl_xor(ms, dd); me |= shfl_xor(me, dd); }
+        // the masks only gain bits: a wave whose bits are all in already (nearly every wave after the first few) adds
+        // nothing, and thousands of read-modify-writes of one word would serialise
+        if (lane_id() == 0) {
+            if (ms & ~__hip_atomic_load(&g[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicOr((unsigned long long *)&g[2], (unsigned long long)ms);
+            if (me & ~__hip_atomic_load(&g[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                atomicOr((unsigned long long *)&g[3], (unsigned long long)me);
+        }
+    }
+}
+
+// row r: keep = erased || r >= max lim || it has ranges left; the counts of the kept rows; cutf = kept with changed ranges
+__global__ __launch_bounds__(BLOCK) void k_rp_rows(Table s, const uint64_t *__restrict__ poff, const uint32_t *__restrict__ chg,
+                                                   uint64_t *__restrict__ keep, uint64_t *__restrict__ kcnt,
+                                                   uint64_t *__restrict__ kdep, uint64_t *__restrict__ cutf,
+                                                   const uint64_t *__restrict__ g)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= s.n) return;
+    const uint32_t maxlim = (uint32_t)g[0];
+    const uint64_t c = poff[s.rng_off[r + 1]] - poff[s.rng_off[r]];
+    const bool k = (s.flags[r] & ACC_RCMD_ERASED) || r >= maxlim || c > 0;
+    keep[r] = k ? 1u : 0u;
+    kcnt[r] = k ? c : 0u;
+    kdep[r] = k ? s.dep.off[r + 1] - s.dep.off[r] : 0u;
+    cutf[r] = k && chg[r] ? 1u : 0u;
+}
+
+// every row column of the kept rows at their new row, the new offsets (their ends by the thread of the last old row: the
+// new table may be empty), the index's per-row input, and each kept row's deps as a segment of the segmented copy
+__global__ __launch_bounds__(BLOCK) void k_rp_write(Table s, const uint64_t *__restrict__ keep, const uint64_t *__restrict__ kidx,
+                                                    const uint64_t *__restrict__ roff, const uint64_t *__restrict__ doff,
+                                                    TableOut o, uint4 *__restrict__ tinfo, uint32_t *__restrict__ dsrc)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= s.n) return;
+    if (r == s.n - 1) {
+        const uint64_t n2 = kidx[s.n];
+        o.rng_off[n2] = (uint32_t)roff[s.n];
+        o.dep_off[n2] = (uint32_t)doff[s.n];
+    }
+    if (!keep[r]) return;
+    const uint64_t x = kidx[r];
+    o.tm[x] = s.tm[r]; o.tl[x] = s.tl[r]; o.tn[x] = s.tn[r];
+    o.flags[x] = s.flags[r];
+    o.em[x] = s.em[r]; o.el[x] = s.el[r]; o.en[x] = s.en[r];
+    o.status[x] = s.status[r];
+    o.rng_off[x] = (uint32_t)roff[r];
+    o.dep_off[x] = (uint32_t)doff[r];
+    dsrc[x] = s.dep.off[r];
+    tinfo[x] = make_uint4(0u, (uint32_t)x, 0u, 1u);
+}
+
+// ---------------------------------------------------------------- RedundantBefore: registration under the map
+
+// the owner update of every range of the delta (offsets validated)
+__global__ __launch_bounds__(BLOCK) void k_rt_owner(uint32_t D, const uint32_t *__restrict__ rng_off, uint32_t *__restrict__ uown)
+{
+    const uint32_t u = blockIdx.x * BLOCK + threadIdx.x;
+    if (u >= D) return;
+    for (uint32_t k = rng_off[u]; k < rng_off[u + 1]; ++k) uown[k] = u;
+}
+
+// Range k = (a, b) of non-erasing update u of a range-domain TxnId t minus the map's intervals whose bound is above t
+// (RedundantBefore.removeShardRedundant); the ranges of erasing updates and of key-domain TxnIds, which nothing reads,
+// stay. A closed interval [st, en] of key codes is (st - 1, en] (EndInclusive) or [st, en + 1) in the store's bound
+// type. WRITE == false: cnt[k] = the pieces, *ntrim counts the ranges that do not stay as they are.
+template <bool WRITE>
+__global__ __launch_bounds__(BLOCK) void k_rt_trim(Delta d, const uint32_t *__restrict__ uown, mc::Map mp, uint64_t *__restrict__ cnt,
+                                                   const uint64_t *__restrict__ toff, uint64_t *__restrict__ ors,
+                                                   uint64_t *__restrict__ ore, uint64_t *__restrict__ ntrim)
+{
+    const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
+    bool changed = false;
+    if (k < d.NR) {
+        const uint32_t u = uown[k];
+        const uint64_t a = d.rs[k], b = d.re[k];
+        const uint64_t tm = d.tm[u], tl = d.tl[u];
+        const int32_t tn = d.tn[u];
+        uint64_t dst = 0;
+        if constexpr (WRITE) dst = toff[k];
+        uint32_t pieces = 0;
+        auto piece = [&](uint64_t ps, uint64_t pe) {
+            if constexpr (WRITE) { ors[dst] = ps; ore[dst] = pe; ++dst; }
+            ++pieces;
+        };
+        if (!(tl & 1u) || (d.flags[u] & ACC_RCMD_ERASED)) piece(a, b);
+        else {
+            uint64_t cur = a;
+            bool open = true;
+            // the first interval whose end lies above a: en > a (EndInclusive), en + 1 > a
+            uint64_t i = mp.ei ? mc::lower64(mp.en, mp.nv, a + 1) : mc::lower64(mp.en, mp.nv, a);
+            for (; i < mp.nv; ++i) {
+                const uint64_t st = mp.st[i], en = mp.en[i];
+                const uint64_t is = mp.ei ? st - 1 : st;
+                const uint64_t ie = mp.ei ? en : (en == ~0ull ? en : en + 1);
+                if (is >= b) break;
+                if (ts_cmp(mp.vm[i], mp.vl[i], mp.vn[i], tm, tl, tn) <= 0) continue;
+                if (cur < is) piece(cur, is);
+                changed = true;
+                if (ie >= b) { open = false; break; }
+                cur = ie;
+            }
+            if (open) piece(cur, b);
+        }
+        if constexpr (!WRITE) cnt[k] = pieces;
+    }
+    if constexpr (!WRITE) {
+        const unsigned long long bc = __ballot(changed);
+        if (bc && lane_id() == 0) atomicAdd((unsigned long long *)ntrim, (unsigned long long)__popcll(bc));
+    }
+}
+
+// the trimmed delta's rng_off
+__global__ __launch_bounds__(BLOCK) void k_rt_off(uint32_t D, const uint32_t *__restrict__ rng_off, const uint64_t *__restrict__ toff,
+                                                  uint32_t *__restrict__ out)
+{
+    const uint32_t u = blockIdx.x * BLOCK + threadIdx.x;
+    if (u > D) return;
+    out[u] = (uint32_t)toff[rng_off[u]];
+}
+
 // ---------------------------------------------------------------- query
 
 struct Queries {
@@ -616,6 +866,7 @@ void rcmd_free(acc_rcmd *s)
                      (void *)s->cs_kind, (void *)s->cls, (void *)s->em, (void *)s->el, (void *)s->en, (void *)s->status,
                      (void *)s->dep_off, (void *)s->dm, (void *)s->dl, (void *)s->dn, (void *)s->ds, (void *)s->de, (void *)s->dk })
         (void)hipFree(p);
+    mc_free(s->rb);
     delete s;
 }
 
@@ -652,6 +903,131 @@ void rcmd_state(acc_ctx *ctx, acc_rcmd *s, acc_rcmd_state *out)
                            acc_ts_cols{ s->dm, s->dl, s->dn }, s->ds, s->de, s->dk };
 }
 
+// The end of every call that rewrites the table (an update, a prune). o: the new table, n2 rows, R2 ranges, ND2 deps, in
+// the context's rc_t_* buffers; b: the index's inputs over it (tinfo, rowner, eflag, eidx allocated); g[2], g[3]: the OR
+// masks of the range starts and ends, g[4], g[5]: two words of the caller's, read back with them (w). The index is
+// rebuilt from the new table by rd_range_dict as acc_rangedeps_batch runs it, and its arrays and the table move into
+// the store with acc_ctx::swap_buf (the context keeps the store's previous arrays for its next results).
+struct Finished {
+    uint64_t w[2];
+    uint32_t NE, n_dict;
+};
+static Finished finish_table(acc_ctx *ctx, acc_rcmd *store, const TableOut &o, RdBuild &b, uint32_t n2, uint64_t R2, uint64_t ND2,
+                             const uint64_t *g)
+{
+    Finished fin{};
+    b.tl = o.tl;
+    b.rs = o.rs;
+    b.re = o.re;
+    scan<uint32_t, OpAdd<uint32_t>>(ctx, b.eflag, b.eidx, (size_t)R2, true, b.eidx + R2);
+    {
+        ReadBack rb(ctx);
+        const auto hm = rb.words((const uint64_t *)(g + 2), 4);   // start mask, end mask, the caller's two words
+        ReadBack::Word<uint32_t> ne;
+        if (R2) ne = rb.u32(b.eidx + R2);
+        rb.wait();
+        b.mask_s = hm[0]; b.mask_e = hm[1];
+        fin.w[0] = hm[2]; fin.w[1] = hm[3];
+        b.NE = ne;
+    }
+    rd_range_dict(ctx, b);
+    uint32_t n_dict = 0;
+    {
+        ReadBack rb(ctx);
+        ReadBack::Word<uint32_t> nd;
+        if (b.NE) nd = rb.u32(b.dincl + b.NE);
+        rb.wait();   // everything of this call is complete: the store may take the arrays
+        n_dict = nd;
+    }
+
+    // ---- the store adopts the table and the index; the context keeps its previous arrays for the next results
+    int bi = 0;
+    auto adopt = [&](const char *name, auto *&p) {
+        void *v = p;
+        ctx->swap_buf(name, v, store->bytes[bi++]);
+        p = static_cast<std::remove_reference_t<decltype(p)>>(v);
+    };
+    adopt("rc_t_tm", store->tm); adopt("rc_t_tl", store->tl); adopt("rc_t_tn", store->tn); adopt("rc_t_flags", store->flags);
+    adopt("rc_t_rng_off", store->rng_off); adopt("rc_t_rs", store->rs); adopt("rc_t_re", store->re);
+    adopt("rd_dict_s", store->dict_s); adopt("rd_dict_e", store->dict_e); adopt("rd_dincl", store->dincl);
+    adopt("rd_cs_s", store->cs_s); adopt("rd_cs_e", store->cs_e); adopt("rd_cs_info", store->cs_info);
+    adopt("rd_cs_kind", store->cs_kind); adopt("rd_cls", store->cls);
+    adopt("rc_t_em", store->em); adopt("rc_t_el", store->el); adopt("rc_t_en", store->en); adopt("rc_t_status", store->status);
+    adopt("rc_t_doff", store->dep_off); adopt("rc_t_dm", store->dm); adopt("rc_t_dl", store->dl); adopt("rc_t_dn", store->dn);
+    adopt("rc_t_ds", store->ds); adopt("rc_t_de", store->de); adopt("rc_t_dk", store->dk);
+    store->ND = ND2;
+    store->n = n2;
+    store->R = (uint32_t)R2;
+    store->NE = b.NE;
+    store->n_dict = n_dict;
+    ctx->rd_valid = false;   // an earlier result may name arrays the store or the next call now owns
+    fin.NE = b.NE;
+    fin.n_dict = n_dict;
+    return fin;
+}
+
+// the new table's arrays (the context's rc_t_* buffers) and the index's inputs over it
+static TableOut table_out(acc_ctx *ctx, uint32_t n2, uint64_t R2, uint64_t ND2)
+{
+    return TableOut{ ctx->get<uint64_t>("rc_t_tm", n2), ctx->get<uint64_t>("rc_t_tl", n2), ctx->get<int32_t>("rc_t_tn", n2),
+                     ctx->get<uint8_t>("rc_t_flags", n2), ctx->get<uint32_t>("rc_t_rng_off", (size_t)n2 + 1),
+                     ctx->get<uint64_t>("rc_t_rs", R2), ctx->get<uint64_t>("rc_t_re", R2),
+                     ctx->get<uint64_t>("rc_t_em", n2), ctx->get<uint64_t>("rc_t_el", n2), ctx->get<int32_t>("rc_t_en", n2),
+                     ctx->get<uint8_t>("rc_t_status", n2), ctx->get<uint32_t>("rc_t_doff", (size_t)n2 + 1),
+                     ctx->get<uint64_t>("rc_t_dm", ND2), ctx->get<uint64_t>("rc_t_dl", ND2), ctx->get<int32_t>("rc_t_dn", ND2),
+                     ctx->get<uint64_t>("rc_t_ds", ND2), ctx->get<uint64_t>("rc_t_de", ND2), ctx->get<uint8_t>("rc_t_dk", ND2) };
+}
+static RdBuild index_inputs(acc_ctx *ctx, const acc_rcmd *store, uint32_t n2, uint64_t R2)
+{
+    RdBuild b;
+    b.n = n2;
+    b.R = (size_t)R2;
+    b.end_inclusive = (int)store->end_inclusive;
+    b.tinfo = ctx->get<uint4>("rd_tinfo", n2);
+    b.rowner = ctx->get<uint32_t>("rd_rowner", R2);
+    b.eflag = ctx->get<uint32_t>("rd_eflag", R2);
+    b.eidx = ctx->get<uint32_t>("rd_eidx", R2 + 1);
+    return b;
+}
+
+// Registration under a non-empty map (InMemorySafeStore.update :757-760): the ranges of every non-erasing update of a
+// range-domain TxnId t lose what the map's intervals with a bound above t cover. d's range columns are replaced by the
+// trimmed ones (a range may split: NR may grow); returns the ranges changed or removed. The offsets have passed
+// validation.
+static uint64_t trim_delta(acc_ctx *ctx, const acc_maxconflicts *rbm, Delta &d)
+{
+    if (d.NR == 0) return 0;
+    const mc::Map mp = mc_map(rbm);
+    uint32_t *uown = ctx->get<uint32_t>("rt_uown", d.NR);
+    uint64_t *cnt = ctx->get<uint64_t>("rt_cnt", d.NR), *toff = ctx->get<uint64_t>("rt_toff", (size_t)d.NR + 1);
+    uint64_t *ntrim = ctx->get<uint64_t>("rt_ntrim", 1);
+    ACC_HIP(hipMemsetAsync(ntrim, 0, 8, ctx->stream));
+    launch(ctx, "rt_owner", k_rt_owner, dim3(grid_for(d.D, BLOCK)), dim3(BLOCK), 0, d.D, d.rng_off, uown);
+    launch(ctx, "rt_count", k_rt_trim<false>, dim3(grid_for(d.NR, BLOCK)), dim3(BLOCK), 0, d, (const uint32_t *)uown, mp, cnt,
+           (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr, ntrim);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, cnt, toff, d.NR, true, toff + d.NR);
+    uint64_t nt, NR2;
+    {
+        ReadBack rb(ctx);
+        const auto a = rb.u64(ntrim);
+        const auto b = rb.u64(toff + d.NR);
+        rb.wait();
+        nt = a; NR2 = b;
+    }
+    if (nt == 0) return 0;   // nothing under any bound above its TxnId: the delta as it is
+    if (NR2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "trimmed updates too large (ranges >= 2^32 - 1)");
+    uint32_t *noff = ctx->get<uint32_t>("rt_roff", (size_t)d.D + 1);
+    uint64_t *ors = ctx->get<uint64_t>("rt_rs", NR2), *ore = ctx->get<uint64_t>("rt_re", NR2);
+    launch(ctx, "rt_off", k_rt_off, dim3(grid_for((size_t)d.D + 1, BLOCK)), dim3(BLOCK), 0, d.D, d.rng_off, (const uint64_t *)toff, noff);
+    launch(ctx, "rt_write", k_rt_trim<true>, dim3(grid_for(d.NR, BLOCK)), dim3(BLOCK), 0, d, (const uint32_t *)uown, mp,
+           (uint64_t *)nullptr, (const uint64_t *)toff, ors, ore, (uint64_t *)nullptr);
+    d.rng_off = noff;
+    d.rs = ors;
+    d.re = ore;
+    d.NR = (uint32_t)NR2;
+    return nt;
+}
+
 // acc_rcmd_update (state == false: in's state columns are not read) and acc_rcmd_update_cmds
 static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *in, bool state)
 {
@@ -667,6 +1043,7 @@ static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_u
     ctx->stat("rcmd.erased_ignored", 0);
     ctx->stat("rcmd.entries", store->NE);
     ctx->stat("rcmd.stored_ranges", store->n_dict);
+    ctx->stat("rcmd.update_ranges_trimmed", 0);
     if (D == 0) {
         if (NR) fail(ACC_E_ARG, "rng_off must start at 0, be non-decreasing and end at n_ranges");
         if (NDin) fail(ACC_E_ARG, "dep_off must start at 0, be non-decreasing and end at n_deps");
@@ -726,6 +1103,9 @@ static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_u
         nkey = (uint32_t)hg[1];
     }
 
+    // under a non-empty RedundantBefore map the fold sees the trimmed ranges (a store never marked launches nothing here)
+    const uint64_t ntrim = store->rb && store->rb->nv ? trim_delta(ctx, store->rb, d) : 0;
+
     // ---- 3. groups against the stored TxnIds
     const Table s = table_of(store);
     const uint32_t n = store->n;
@@ -751,6 +1131,7 @@ static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_u
     const uint32_t n2 = n + nnew;
     if (n2 == 0) {   // an empty store and key-domain TxnIds only
         ctx->stat("rcmd.skipped_key_domain", nkey);
+        ctx->stat("rcmd.update_ranges_trimmed", ntrim);
         return;
     }
 
@@ -790,78 +1171,22 @@ static void rcmd_update_impl(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_u
     }
     if (R2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (ranges >= 2^32 - 1)");
     if (ND2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (deps >= 2^32 - 1)");
-    TableOut o{ ctx->get<uint64_t>("rc_t_tm", n2), ctx->get<uint64_t>("rc_t_tl", n2), ctx->get<int32_t>("rc_t_tn", n2),
-                ctx->get<uint8_t>("rc_t_flags", n2), ctx->get<uint32_t>("rc_t_rng_off", (size_t)n2 + 1),
-                ctx->get<uint64_t>("rc_t_rs", R2), ctx->get<uint64_t>("rc_t_re", R2),
-                ctx->get<uint64_t>("rc_t_em", n2), ctx->get<uint64_t>("rc_t_el", n2), ctx->get<int32_t>("rc_t_en", n2),
-                ctx->get<uint8_t>("rc_t_status", n2), ctx->get<uint32_t>("rc_t_doff", (size_t)n2 + 1),
-                ctx->get<uint64_t>("rc_t_dm", ND2), ctx->get<uint64_t>("rc_t_dl", ND2), ctx->get<int32_t>("rc_t_dn", ND2),
-                ctx->get<uint64_t>("rc_t_ds", ND2), ctx->get<uint64_t>("rc_t_de", ND2), ctx->get<uint8_t>("rc_t_dk", ND2) };
-    RdBuild b;
-    b.n = n2;
-    b.R = (size_t)R2;
-    b.end_inclusive = (int)store->end_inclusive;
-    b.tinfo = ctx->get<uint4>("rd_tinfo", n2);
-    b.rowner = ctx->get<uint32_t>("rd_rowner", R2);
-    b.eflag = ctx->get<uint32_t>("rd_eflag", R2);
-    b.eidx = ctx->get<uint32_t>("rd_eidx", R2 + 1);
+    const TableOut o = table_out(ctx, n2, R2, ND2);
+    RdBuild b = index_inputs(ctx, store, n2, R2);
     launch(ctx, "rc_write", k_rc_write, dim3(grid_for(n2, BLOCK)), dim3(BLOCK), 0, n2, d, s, (const uint32_t *)dr.first,
            (const uint32_t *)grow, (const uint32_t *)insx, (const uint32_t *)isnew, f, (const uint64_t *)off, (const uint64_t *)doff, o, b.tinfo, b.rowner,
            b.eflag, g);
 
-    // ---- 6. the index from the new table (rd_range_dict as acc_rangedeps_batch runs it)
-    b.tl = o.tl;
-    b.rs = o.rs;
-    b.re = o.re;
-    scan<uint32_t, OpAdd<uint32_t>>(ctx, b.eflag, b.eidx, (size_t)R2, true, b.eidx + R2);
-    uint64_t n_ign, n_upd;
-    {
-        ReadBack rb(ctx);
-        const auto hm = rb.words((const uint64_t *)(g + 2), 4);   // start mask, end mask, ignored updates, updated commands
-        ReadBack::Word<uint32_t> ne;
-        if (R2) ne = rb.u32(b.eidx + R2);
-        rb.wait();
-        b.mask_s = hm[0]; b.mask_e = hm[1];
-        n_ign = hm[2]; n_upd = hm[3];
-        b.NE = ne;
-    }
-    rd_range_dict(ctx, b);
-    uint32_t n_dict = 0;
-    {
-        ReadBack rb(ctx);
-        ReadBack::Word<uint32_t> nd;
-        if (b.NE) nd = rb.u32(b.dincl + b.NE);
-        rb.wait();   // everything of this update is complete: the store may take the arrays
-        n_dict = nd;
-    }
-
-    // ---- the store adopts the table and the index; the context keeps its previous arrays for the next results
-    int bi = 0;
-    auto adopt = [&](const char *name, auto *&p) {
-        void *v = p;
-        ctx->swap_buf(name, v, store->bytes[bi++]);
-        p = static_cast<std::remove_reference_t<decltype(p)>>(v);
-    };
-    adopt("rc_t_tm", store->tm); adopt("rc_t_tl", store->tl); adopt("rc_t_tn", store->tn); adopt("rc_t_flags", store->flags);
-    adopt("rc_t_rng_off", store->rng_off); adopt("rc_t_rs", store->rs); adopt("rc_t_re", store->re);
-    adopt("rd_dict_s", store->dict_s); adopt("rd_dict_e", store->dict_e); adopt("rd_dincl", store->dincl);
-    adopt("rd_cs_s", store->cs_s); adopt("rd_cs_e", store->cs_e); adopt("rd_cs_info", store->cs_info);
-    adopt("rd_cs_kind", store->cs_kind); adopt("rd_cls", store->cls);
-    adopt("rc_t_em", store->em); adopt("rc_t_el", store->el); adopt("rc_t_en", store->en); adopt("rc_t_status", store->status);
-    adopt("rc_t_doff", store->dep_off); adopt("rc_t_dm", store->dm); adopt("rc_t_dl", store->dl); adopt("rc_t_dn", store->dn);
-    adopt("rc_t_ds", store->ds); adopt("rc_t_de", store->de); adopt("rc_t_dk", store->dk);
-    store->ND = ND2;
-    store->n = n2;
-    store->R = (uint32_t)R2;
-    store->NE = b.NE;
-    store->n_dict = n_dict;
-    ctx->rd_valid = false;   // an earlier result may name arrays the store or the next call now owns
+    // ---- 6. the index from the new table; the store adopts both
+    const Finished fin = finish_table(ctx, store, o, b, n2, R2, ND2, g);
+    const uint64_t n_ign = fin.w[0], n_upd = fin.w[1];
     ctx->stat("rcmd.inserted", nnew);
     ctx->stat("rcmd.updated", n_upd);
     ctx->stat("rcmd.skipped_key_domain", nkey);
     ctx->stat("rcmd.erased_ignored", n_ign);
-    ctx->stat("rcmd.entries", b.NE);
-    ctx->stat("rcmd.stored_ranges", n_dict);
+    ctx->stat("rcmd.entries", fin.NE);
+    ctx->stat("rcmd.stored_ranges", fin.n_dict);
+    ctx->stat("rcmd.update_ranges_trimmed", ntrim);
 }
 
 void rcmd_update(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_updates *in)
@@ -877,6 +1202,118 @@ void rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates 
 {
     if (!store || !in) fail(ACC_E_ARG, "null argument");
     rcmd_update_impl(ctx, store, in, true);
+}
+
+// InMemoryCommandStore.markShardDurable (:346-370) for the resident table, once per distinct bound of the input: the
+// map merged first (RedundantBefore.merge), then every non-erased command below a bound loses the input ranges that
+// hold a bound above it, and leaves when none of its ranges is left.
+void rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in)
+{
+    if (!store || !in) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->end_inclusive > 1) fail(ACC_E_ARG, "end_inclusive must be 0 (StartInclusive) or 1 (EndInclusive)");
+    if (in->end_inclusive != store->end_inclusive) fail(ACC_E_ARG, "end_inclusive differs from the store's Range bound type");
+    for (const char *z : { "rcmd.redundant_cmds_cut", "rcmd.redundant_cmds_dropped", "rcmd.redundant_prune_us", "rcmd.redundant_index_us" })
+        ctx->stat(z, 0);
+    ctx->stat("rcmd.redundant_ranges_before", store->R);
+    ctx->stat("rcmd.redundant_ranges_after", store->R);
+    if (in->n_ranges == 0) return;
+    hipStream_t st = ctx->stream;
+    const RbInput ri = rb_stage_ranges(ctx, in);
+    if (!store->rb) store->rb = mc_new(store->device, store->end_inclusive);   // (the ranges have passed)
+    rb_merge_staged(ctx, store->rb, ri);
+    const uint32_t n = store->n, R = store->R, m = ri.n;
+    if (n == 0) { ctx->sync(); return; }   // an empty store records the map
+    hipEvent_t ev[3] = { ctx->take_event(), ctx->take_event(), ctx->take_event() };
+    struct Give {
+        acc_ctx *c; hipEvent_t *e;
+        ~Give() { for (int i = 0; i < 3; ++i) c->event_pool.push_back(e[i]); }
+    } give{ ctx, ev };
+    ACC_HIP(hipEventRecord(ev[0], st));
+
+    // ---- count: lim per input range, the pieces of every stored range, keep and the counts of every row
+    const Table s = table_of(store);
+    uint64_t *g = ctx->get<uint64_t>("rc_g", 8);
+    ACC_HIP(hipMemsetAsync(g, 0, 8 * sizeof(uint64_t), st));
+    uint32_t *lim = ctx->get<uint32_t>("rp_lim", m);
+    launch(ctx, "rp_lim", k_rp_lim, dim3(grid_for(m, BLOCK)), dim3(BLOCK), 0, m, ri.bm, ri.bl, ri.bn, s, lim, g);
+    uint32_t *rown = ctx->get<uint32_t>("rp_rowner", R), *chg = ctx->get<uint32_t>("rp_chg", n);
+    ACC_HIP(hipMemsetAsync(chg, 0, (size_t)n * sizeof(uint32_t), st));
+    launch(ctx, "rp_rowner", k_rp_rowner, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, n, s.rng_off, rown);
+    const Bounds bnd{ m, ri.rs, ri.re, lim };
+    uint64_t *cnt = ctx->get<uint64_t>("rp_cnt", R), *poff = ctx->get<uint64_t>("rp_poff", (size_t)R + 1);
+    launch(ctx, "rp_count", k_rp_cut<false>, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, R, s, (const uint32_t *)rown, bnd, cnt, chg,
+           Pruned{}, g);
+    scan<uint64_t, OpAdd<uint64_t>>(ctx, cnt, poff, R, true, poff + R);
+    uint64_t *keep = ctx->get<uint64_t>("rp_keep", n), *kcnt = ctx->get<uint64_t>("rp_kcnt", n), *kdep = ctx->get<uint64_t>("rp_kdep", n);
+    uint64_t *cutf = ctx->get<uint64_t>("rp_cutf", n);
+    uint64_t *kidx = ctx->get<uint64_t>("rp_kidx", (size_t)n + 1), *roff = ctx->get<uint64_t>("rp_roff", (size_t)n + 1);
+    uint64_t *doff = ctx->get<uint64_t>("rp_doff", (size_t)n + 1), *cidx = ctx->get<uint64_t>("rp_cidx", (size_t)n + 1);
+    launch(ctx, "rp_rows", k_rp_rows, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, (const uint64_t *)poff, (const uint32_t *)chg, keep,
+           kcnt, kdep, cutf, (const uint64_t *)g);
+    {
+        const uint64_t *in4[4] = { keep, kcnt, kdep, cutf };
+        uint64_t *out4[4] = { kidx, roff, doff, cidx }, *tot4[4] = { kidx + n, roff + n, doff + n, cidx + n };
+        const size_t n4[4] = { n, n, n, n };
+        scan_multi<uint64_t, OpAdd<uint64_t>>(ctx, 4, in4, out4, n4, true, tot4);
+    }
+    // ---- the one read-back: the new sizes and the rows cut (rows dropped = n - n2)
+    uint64_t ncut, ndrop, n2, R2, ND2;
+    {
+        ReadBack rb(ctx);
+        const auto a = rb.u64(kidx + n);
+        const auto b = rb.u64(roff + n);
+        const auto c = rb.u64(doff + n);
+        const auto d = rb.u64(cidx + n);
+        rb.wait();
+        n2 = a; R2 = b; ND2 = c; ncut = d;
+    }
+    if (n2 > n || ND2 > store->ND) fail(ACC_E_STATE, "internal: a prune grew the range-command table");
+    ndrop = n - n2;
+    ctx->stat("rcmd.redundant_cmds_cut", ncut);
+    ctx->stat("rcmd.redundant_cmds_dropped", ndrop);
+    if (ncut == 0 && ndrop == 0) return;   // no array is rewritten, every view stays valid
+    if (R2 >= 0xFFFFFFFFull) fail(ACC_E_CAP, "range-command store too large (ranges >= 2^32 - 1)");
+
+    // ---- emit: every column once, the index's inputs with them
+    const TableOut o = table_out(ctx, (uint32_t)n2, R2, ND2);
+    RdBuild b = index_inputs(ctx, store, (uint32_t)n2, R2);
+    uint32_t *dsrc = ctx->get<uint32_t>("rp_dsrc", n2);
+    launch(ctx, "rp_write", k_rp_write, dim3(grid_for(n, BLOCK)), dim3(BLOCK), 0, s, (const uint64_t *)keep, (const uint64_t *)kidx,
+           (const uint64_t *)roff, (const uint64_t *)doff, o, b.tinfo, dsrc);
+    launch(ctx, "rp_cut", k_rp_cut<true>, dim3(grid_for(R, BLOCK)), dim3(BLOCK), 0, R, s, (const uint32_t *)rown, bnd, (uint64_t *)nullptr,
+           (uint32_t *)nullptr, Pruned{ poff, kidx, roff, o.rs, o.re, b.rowner, b.eflag }, g);
+    rb::Cols dc{};
+    dc.s64[0] = s.dep.m; dc.s64[1] = s.dep.l; dc.s64[2] = s.dep.s; dc.s64[3] = s.dep.e;
+    dc.d64[0] = o.dm; dc.d64[1] = o.dl; dc.d64[2] = o.ds; dc.d64[3] = o.de;
+    dc.s32[0] = s.dep.n; dc.d32[0] = o.dn;
+    dc.s8 = s.dep.k; dc.d8 = o.dk;
+    dc.n64 = 4; dc.n32 = 1;
+    rb_segcopy(ctx, "rp_copy_deps", dc, ND2, o.dep_off + n2, (uint32_t)n2, o.dep_off, dsrc);
+    ACC_HIP(hipEventRecord(ev[1], st));
+    const uint32_t R0 = R;
+    finish_table(ctx, store, o, b, (uint32_t)n2, R2, ND2, g);
+    ACC_HIP(hipEventRecord(ev[2], st));
+    ctx->sync();
+    float ms_p = 0, ms_i = 0;
+    ACC_HIP(hipEventElapsedTime(&ms_p, ev[0], ev[1]));
+    ACC_HIP(hipEventElapsedTime(&ms_i, ev[1], ev[2]));
+    ctx->stat("rcmd.redundant_prune_us", (uint64_t)(ms_p * 1000.0f));
+    ctx->stat("rcmd.redundant_index_us", (uint64_t)(ms_i * 1000.0f));
+    ctx->stat("rcmd.redundant_ranges_before", R0);
+    ctx->stat("rcmd.redundant_ranges_after", R2);
+}
+
+void rcmd_redundant_view(acc_rcmd *store, acc_cfk_redundant_map *out)
+{
+    if (!store || !out) fail(ACC_E_ARG, "null argument");
+    *out = acc_cfk_redundant_map{};
+    out->end_inclusive = store->end_inclusive;
+    if (const acc_maxconflicts *m = store->rb) {
+        out->n = m->nv;
+        out->st = m->st; out->en = m->en;
+        out->bound = acc_ts_cols{ m->vm, m->vl, m->vn };
+    }
 }
 
 static void rcmd_check_query_errors(uint64_t e)

@@ -50,6 +50,8 @@
  *   acc_rcmd_map_reduce_full  the range-command half of the recovery scans (mapReduceRangesInternal :883-960 with every
  *                          TestStartedAt / TestDep / TestStatus) read from the same store and the state its updates
  *                          carry (acc_rcmd_update_cmds).
+ *   acc_rcmd_redundant_before  CommandStore.markShardDurable (local/CommandStore.java:520-528 ->
+ *                          impl/InMemoryCommandStore.java:346-370) on the same store: the prune of its range half.
  *   acc_levelise           execution-order restatement of Commands.updateWaitingOn local/Commands.java:776-830
  *                          (deterministic wavefront schedule).
  *
@@ -938,8 +940,8 @@ int  acc_cfk_missing(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_batch_view *out);
  * (set by acc_cfk_apply_deps); cfk.redundant_prune_us / cfk.redundant_view_us (stream time of the prune passes and of
  * the view rebuild).
  * Out of scope: RedundantBefore.collectDeps (:418-421: the (range, bound) range deps added to PreAccept results), the
- * locally-redundant, bootstrap and stale fields of an Entry, registerHistorical, and pruning of the range-command store
- * (its commands leave through ACC_RCMD_ERASED).
+ * locally-redundant, bootstrap and stale fields of an Entry, and registerHistorical. (The range-command store is
+ * pruned by its own call, acc_rcmd_redundant_before below.)
  * acc_cfk_redundant_view describes the map: closed intervals over the key codes, ascending and disjoint (adjacent
  * intervals with equal bounds are one), with the bound of each. */
 typedef struct acc_cfk_redundant_in {
@@ -1219,6 +1221,59 @@ typedef struct acc_rcmd_state {
 int  acc_rcmd_update_cmds(acc_ctx *ctx, acc_rcmd *store, const acc_rcmd_cmd_updates *updates);
 int  acc_rcmd_state_view(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out);
 int  acc_rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *out_view);
+
+/* RedundantBefore on the resident range-command store: the prune that keeps the range half a steady-state store, as
+ * acc_cfk_redundant_before keeps the key half. CommandStore.markShardDurable (local/CommandStore.java:520-528) merges a
+ * sync point into RedundantBefore; InMemoryCommandStore.markShardDurable (impl/InMemoryCommandStore.java:346-370) then
+ * cuts `ranges` out of every range command below syncId and removes those left empty; from then on
+ * InMemorySafeStore.update (:757-760) registers only what RedundantBefore.removeShardRedundant
+ * (local/RedundantBefore.java:214-223, 431-435) leaves of a range command's ranges.
+ * Input and map structs are acc_cfk_redundant_before's. in->end_inclusive must equal the store's; range j is (s, e] or
+ * [s, e) by that bound type and holds bound[j], the shardAppliedOrInvalidatedBefore TxnId. Bounds are per range so one
+ * call can carry several sync points: one call is the reference's markShardDurable calls, one per distinct bound, in
+ * any order (AbstractRanges.subtract cuts each range of the left side into its maximal pieces outside the right side
+ * and never merges across them, so subtracting disjoint ranges one after the other, in any order, is subtracting their
+ * union). In call order:
+ *   1. validation; ACC_E_ARG, store and map unchanged: mem not host / device, end_inclusive > 1 or not the store's,
+ *      ranges unsorted, overlapping (rng_end[j-1] > rng_start[j]) or with start >= end, null arguments. n_ranges == 0
+ *      is a no-op.
+ *   2. the store's map RB, key code -> TxnId (all TxnId.NONE at first), becomes the pointwise Timestamp.compareTo
+ *      maximum of RB and the input (RedundantBefore.merge: a lower bound is absorbed, never an error). An empty store
+ *      records the map.
+ *   3. the prune, defined by the call's input (as in the reference), not by the merged map: for every non-erased
+ *      command C, J(C) = { j : C.txnId < bound[j] } strictly by compareTo (a TxnId that compares equal to a bound
+ *      stays; identity bits outside compareTo do not matter); C.ranges = C.ranges.subtract(the ranges of J(C)): each
+ *      stored range cut into its maximal pieces outside them, in order, none empty, nothing merged. A non-erased
+ *      command with non-empty J(C) whose ranges are now empty leaves the table, one that already held no ranges
+ *      included (removeIf tests every command below syncId). Rows above a dropped row shift down with their raw TxnId
+ *      bits, status, executeAt, HAS_DEPS and deps spans unchanged (a range command's own deps are not trimmed here).
+ *      Erased rows are not touched: they hold no ranges and stay as the tombstones that make later updates of that
+ *      TxnId no-ops.
+ *   4. if any row was cut or dropped the index is rebuilt from the new table exactly as an update rebuilds it, the new
+ *      arrays are adopted, and earlier views of the store (acc_rcmd_view, acc_rcmd_state_view, results) are invalid.
+ *      If nothing was cut or dropped no array is rewritten and every view stays valid.
+ * Registration under a non-empty map (acc_rcmd_update, acc_rcmd_update_cmds; only once some bound is above NONE): per
+ * non-erasing update of a range-domain TxnId t, the ranges that enter the Ranges.with fold are
+ * add.subtract(the map's intervals whose bound > t). Validation runs on the caller's ranges, before trimming. A command
+ * whose every update trims to nothing is still inserted, with no ranges (computeIfAbsent runs regardless), and stays
+ * until a later prune whose bound is above it. Erasing updates, key-domain TxnIds and the state columns behave as
+ * without a map. The store's owned ranges (ranges().allBetween) stay unmodelled: the store takes what it is given.
+ * The queries (acc_rcmd_rangedeps, acc_rcmd_map_reduce_full) do not consult the map: they read the pruned state, as
+ * mapReduceRangesInternal does.
+ * acc_rcmd_redundant_view describes the map as acc_cfk_redundant_view does (closed intervals over the key codes,
+ * ascending and disjoint, adjacent equal bounds merged; DEVICE pointers valid until the next
+ * acc_rcmd_redundant_before on the store); n == 0 on a store that was never marked.
+ * Stats: rcmd.redundant_cmds_cut (commands whose ranges changed but that stayed), rcmd.redundant_cmds_dropped,
+ * rcmd.redundant_ranges_before / rcmd.redundant_ranges_after (table ranges), rcmd.update_ranges_trimmed (input ranges
+ * the registration pre-pass changed or removed; set by the update calls), rcmd.redundant_prune_us /
+ * rcmd.redundant_index_us (stream time of the prune passes and of the index rebuild).
+ * Out of scope: RedundantBefore.collectDeps, the (range, bound) deps PreAccept adds to its result
+ * (RedundantBefore.java:181-190, 418-421); an Entry's locally-redundant, bootstrap and stale fields;
+ * historicalRangeCommands and maxRedundant (InMemoryCommandStore.java:350-354, 366); removing the tombstones of erased
+ * commands; the state of a dropped command: it is gone, a later acc_rcmd_update_cmds of that TxnId carries its own
+ * state and a plain acc_rcmd_update re-inserts it NotDefined, as for any absent TxnId. */
+int  acc_rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in);
+int  acc_rcmd_redundant_view(acc_ctx *ctx, acc_rcmd *store, acc_cfk_redundant_map *out);
 
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
