@@ -56,7 +56,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
            "acc_rcmd_update_cmds", "acc_rcmd_state_view", "acc_rcmd_map_reduce_full", "acc_rcmd_redundant_before",
-           "acc_rcmd_redundant_view",
+           "acc_rcmd_redundant_view", "acc_rcmd_partial_rangedeps",
            "acc_ranges_of", "acc_ranges_with", "acc_ranges_subtract", "acc_ranges_merge_touching", "acc_ranges_select",
            "acc_ranges_index_of", "acc_ranges_contains_all_keys", "acc_ranges_contains_all", "acc_rangedeps_is_covered_by",
            "acc_partial_deps_covering", "acc_rmm_without", "acc_recovery_deps_reduce"]
@@ -108,6 +108,10 @@ class RangedepsView(C.Structure):
                 ("rng_start", C.c_void_p), ("rng_end", C.c_void_p),
                 ("arena_off", C.c_void_p), ("arena", C.c_void_p), ("rd_off", C.c_void_p),
                 ("range_id", C.c_void_p), ("u_off", C.c_void_p), ("dep_txn", C.c_void_p)]
+
+
+class RcmdPartialView(C.Structure):
+    _fields_ = [("rd", RangedepsView), ("n_ids", C.c_uint32), ("n_cmd", C.c_uint32), ("ids", TsCols), ("id_row", C.c_void_p)]
 
 
 class RangedepsOut(C.Structure):
@@ -599,6 +603,8 @@ def load():
         L.acc_rcmd_redundant_before.restype = C.c_int
         L.acc_rcmd_redundant_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantMap)]
         L.acc_rcmd_redundant_view.restype = C.c_int
+        L.acc_rcmd_partial_rangedeps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkMixedQueries), C.POINTER(RcmdPartialView)]
+        L.acc_rcmd_partial_rangedeps.restype = C.c_int
     except AttributeError:
         if not os.environ.get("ACC_LIB_PATH"):   # an older tuning build (A/B runs) may lack them; the product may not
             raise

@@ -1378,6 +1378,25 @@ class RangeCmdStore:
         self.ctx.check(self.ctx._lib.acc_rcmd_rangedeps(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
         return self.ctx.copy_out_range(view)
 
+    def partial_rangedeps(self, queries: dict) -> "BatchRangeDeps":
+        """rangedeps(queries) with RedundantBefore.collectDeps' range deps (acc_rcmd_partial_rangedeps; PreAccept's
+        builder.build().with(redundant), messages/PreAccept.java:245-265): per query one (Range(m), bound[m]) dep for
+        every interval m of the store's RedundantBefore map with a bound above TxnId.NONE that a participant touches,
+        united with the stab result. The BatchRangeDeps is over two union tables: rng_start / rng_end = the store's
+        dictionary merged with those interval ranges; dep_txn index ids. Two more attributes, host arrays: ids =
+        dict(msb, lsb, node), the table's TxnIds merged with the distinct bounds in compareTo order; id_row[i] = the
+        table() row of id i, or 0xFFFFFFFF for a bound no row equals. The store is not modified."""
+        keep = []
+        qi = _mixed_queries_in(queries, self.end_inclusive, 0, keep)
+        view = L.RcmdPartialView()
+        self.ctx.check(self.ctx._lib.acc_rcmd_partial_rangedeps(self.ctx.handle, self._h, C.byref(qi), C.byref(view)))
+        r = self.ctx.copy_out_range(view.rd)
+        n = int(view.n_ids)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, n, dt) if n else np.zeros(0, dt)  # noqa: E731
+        r.ids = dict(msb=g(view.ids.msb, np.uint64), lsb=g(view.ids.lsb, np.uint64), node=g(view.ids.node, np.int32))
+        r.id_row = g(view.id_row, np.uint32)
+        return r
+
 
 def mixed_queries_from_preaccept(q: dict) -> dict:
     """The acc_preaccept_in-layout queries (msb, lsb, node, is_range, part_off, part_start, part_end; optional xmsb,
@@ -1430,7 +1449,7 @@ class ReplicaStore:
         self.rcmd = RangeCmdStore(ctx, end_inclusive)
 
     def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True,
-                        range_part: dict | None = None) -> dict:
+                        range_part: dict | None = None, redundant_deps: bool = False) -> dict:
         """part: the batch's updates (cfk_update_stream layout); queries: its PreAccept queries (default: one per
         command first seen in part). Returns dict(propose = MaxConflicts.get + fast path per query, keydeps = the
         KeyDeps of every txn of the store after the batch, when scan). scan="new": instead keydeps_new = the KeyDeps of
@@ -1441,7 +1460,11 @@ class ReplicaStore:
         range_part: the batch's range-command updates (RangeCmdStore.update layout plus optional xmsb, xlsb, xnode: their
         executeAts, default the TxnIds), applied to the range-command store and merged into MaxConflicts with their
         ranges. With scan="new" the result also holds rangedeps_new = the RangeDeps of the same queries from the
-        range-command store after the update (acc_rcmd_rangedeps): with keydeps_new, both halves of PartialDeps."""
+        range-command store after the update (acc_rcmd_rangedeps): with keydeps_new, both halves of PartialDeps.
+        redundant_deps (with scan="new"): instead of rangedeps_new the result holds partial_rangedeps_new =
+        RangeCmdStore.partial_rangedeps of the same queries, the range half with the (range, bound) deps
+        RedundantBefore.collectDeps adds for what mark_shard_durable pruned: with keydeps_new the whole PartialDeps of
+        PreAccept.calculatePartialDeps."""
         from . import workload as W
         q = W.preaccept_queries(part) if queries is None else queries
         out = dict(propose=self.mc.get(q))
@@ -1477,7 +1500,10 @@ class ReplicaStore:
             if not mixed:
                 nq = dict(nq, rng_off=np.zeros(len(q["msb"]) + 1, np.uint32), rng_start=np.zeros(0, np.uint64),
                           rng_end=np.zeros(0, np.uint64))
-            out["rangedeps_new"] = self.rcmd.rangedeps(nq)
+            if redundant_deps:
+                out["partial_rangedeps_new"] = self.rcmd.partial_rangedeps(nq)
+            else:
+                out["rangedeps_new"] = self.rcmd.rangedeps(nq)
         elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
         return out

@@ -54,6 +54,7 @@ void rcmd_state(acc_ctx *ctx, acc_rcmd *store, acc_rcmd_state *out);
 void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_in *q, acc_rangedeps_view *view);
 void rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in);
 void rcmd_redundant_view(acc_rcmd *store, acc_cfk_redundant_map *out);
+void rcmd_partial_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rcmd_partial_view *out);
 }  // namespace acc
 
 namespace {
@@ -437,6 +438,15 @@ int acc_rcmd_redundant_view(acc_ctx *ctx, acc_rcmd *store, acc_cfk_redundant_map
 {
     if (!ctx) return ACC_E_ARG;
     return acc_guard(ctx, [&] { acc::rcmd_redundant_view(store, out); });
+}
+
+int acc_rcmd_partial_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rcmd_partial_view *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::rcmd_partial_rangedeps(ctx, store, q, out);
+    });
 }
 
 int acc_keydeps_copy_out(acc_ctx *ctx, acc_keydeps_out *out)

@@ -55,51 +55,16 @@
 //      cfkredundant.hip; then the index and the adoption as an update ends (finish_table).
 // Under a non-empty map the updates' ranges are trimmed first (trim_delta): k_rt_owner, k_rt_trim<false>, a scan,
 // k_rt_off, one read-back and, if any range changed, k_rt_trim<true>; the fold then runs on the trimmed columns.
+// acc_rcmd_partial_rangedeps (the stab result with RedundantBefore.collectDeps' deps) is rcmd_partial.hip: it runs
+// acc_rcmd_rangedeps' front end and tail through the rcmd_* functions of rcmd_partial.hpp, and every call here that
+// rewrites the table or merges into the map clears the flag of the union index it caches in the store.
 // Integer work only: HBM/latency bound, no MFMA.
 
-#include "cfkredundant.hpp"
-#include "rangedeps.hpp"
+#include "rcmd_partial.hpp"
 #include "ranges_with.hpp"
 #include "recovery_pred.hpp"
 
 #include <type_traits>
-
-struct acc_rcmd {
-    int device = 0;
-    uint32_t end_inclusive = 0;
-    uint32_t n = 0;        // commands (table rows)
-    uint32_t R = 0;        // ranges of the table
-    uint32_t NE = 0;       // index entries = ranges of the non-erased commands
-    uint32_t n_dict = 0;   // distinct stored ranges
-    // the table
-    uint64_t *tm = nullptr, *tl = nullptr;
-    int32_t *tn = nullptr;
-    uint8_t *flags = nullptr;
-    uint32_t *rng_off = nullptr;
-    uint64_t *rs = nullptr, *re = nullptr;
-    // the state of each command (flags holds HAS_DEPS beside ERASED) and its deps, dep_off[n] = ND
-    uint64_t ND = 0;
-    uint64_t *em = nullptr, *el = nullptr;
-    int32_t *en = nullptr;
-    uint8_t *status = nullptr;
-    uint32_t *dep_off = nullptr;
-    uint64_t *dm = nullptr, *dl = nullptr;
-    int32_t *dn = nullptr;
-    uint64_t *ds = nullptr, *de = nullptr;
-    uint8_t *dk = nullptr;
-    // the index (rd_range_dict's arrays; class_off lies NCLS + 1 words into cls)
-    uint64_t *dict_s = nullptr, *dict_e = nullptr;
-    uint32_t *dincl = nullptr;
-    uint64_t *cs_s = nullptr, *cs_e = nullptr;
-    uint2 *cs_info = nullptr;
-    uint8_t *cs_kind = nullptr;
-    uint32_t *cls = nullptr;
-    // byte sizes of the arrays above in declaration order (adopted from the context: they differ from the counts)
-    size_t bytes[26] = {};
-    // acc_rcmd_redundant_before: the store's RedundantBefore map (key code -> shardAppliedOrInvalidatedBefore), created
-    // by the first accepted call
-    acc_maxconflicts *rb = nullptr;
-};
 
 namespace acc {
 
@@ -668,14 +633,6 @@ __global__ __launch_bounds__(BLOCK) void k_rt_off(uint32_t D, const uint32_t *__
 
 // ---------------------------------------------------------------- query
 
-struct Queries {
-    uint32_t nq, P, R;
-    const uint64_t *tm, *tl, *xm, *xl;
-    const int32_t *tn, *xn;
-    const uint32_t *key_off, *rng_off;
-    const uint64_t *key, *rs, *re;
-};
-
 // Per query: the checks of acc_cfk_keydeps_mixed (Kind.ofOrdinal, Kind.witnesses(), both offset arrays, the domain of
 // its participants, Keys sorted unique, Ranges sorted and deoverlapped with start < end); then, inside offsets that
 // passed, its row {lim, tpos, witnesses, domain}: lim = stored TxnIds below S = executeAt (STARTED_BEFORE, :901-902),
@@ -867,6 +824,7 @@ void rcmd_free(acc_rcmd *s)
                      (void *)s->dep_off, (void *)s->dm, (void *)s->dl, (void *)s->dn, (void *)s->ds, (void *)s->de, (void *)s->dk })
         (void)hipFree(p);
     mc_free(s->rb);
+    rcmd_union_free(s);
     delete s;
 }
 
@@ -961,6 +919,7 @@ static Finished finish_table(acc_ctx *ctx, acc_rcmd *store, const TableOut &o, R
     store->NE = b.NE;
     store->n_dict = n_dict;
     ctx->rd_valid = false;   // an earlier result may name arrays the store or the next call now owns
+    store->u.valid = false;  // acc_rcmd_partial_rangedeps rebuilds its union index from the new table
     fin.NE = b.NE;
     fin.n_dict = n_dict;
     return fin;
@@ -1222,6 +1181,7 @@ void rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundan
     const RbInput ri = rb_stage_ranges(ctx, in);
     if (!store->rb) store->rb = mc_new(store->device, store->end_inclusive);   // (the ranges have passed)
     rb_merge_staged(ctx, store->rb, ri);
+    store->u.valid = false;   // the map may have changed: the partial call's union index names its intervals
     const uint32_t n = store->n, R = store->R, m = ri.n;
     if (n == 0) { ctx->sync(); return; }   // an empty store records the map
     hipEvent_t ev[3] = { ctx->take_event(), ctx->take_event(), ctx->take_event() };
@@ -1441,47 +1401,66 @@ static void publish_view(acc_ctx *ctx, const RdBuild &b, acc_rangedeps_view *vie
     ctx->rd_valid = true;
 }
 
-void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *in, acc_rangedeps_view *view)
+RdBuild rcmd_begin_rangedeps(acc_ctx *ctx, const acc_rcmd *store, const acc_cfk_mixed_queries *in)
 {
-    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
     if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
     check_query_bounds(store, in->end_inclusive, in->n_pairs, in->n_ranges);
-    const uint32_t nq = in->n_query;
-    RdBuild b = begin_query(ctx, store, nq, in->n_pairs, in->n_ranges);
-    auto empty = [&] {
-        publish_empty(ctx, store, b, view);
-        ctx->stat("rangedeps.entries", store->NE);
-        ctx->stat("rangedeps.stored_ranges", store->n_dict);
-        ctx->stat("rangedeps.queries", b.Q);
-        ctx->stat("rangedeps.raw_entries", 0);
-        ctx->sync();
-    };
-    if (nq == 0) return empty();
+    return begin_query(ctx, store, in->n_query, in->n_pairs, in->n_ranges);
+}
 
-    // ---- stage and validate; the per-query rows
-    uint32_t *owner = nullptr;
+Queries rcmd_prep_rangedeps(acc_ctx *ctx, const acc_rcmd *store, const acc_cfk_mixed_queries *in, RdBuild &b, uint32_t *&owner)
+{
     uint64_t *g = nullptr;
     const Queries Q = stage_queries(ctx, b, in, in->txn_id, &in->execute_at, owner, g);
-    launch(ctx, "rc_qprep", k_rc_qprep<false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), 0, 0u, b.tinfo, owner,
+    launch(ctx, "rc_qprep", k_rc_qprep<false>, dim3(grid_for(b.n, BLOCK)), dim3(BLOCK), 0, Q, table_of(store), 0, 0u, b.tinfo, owner,
            b.rowner, g);
     rcmd_check_query_errors(read_prep(ctx, g, b));
-    if (store->NE == 0) return empty();   // nothing to stab: no commands, or none with ranges that is not erased
+    return Q;
+}
 
-    // ---- the reused stages over the store's index
+void rcmd_bind_store_index(RdBuild &b, const acc_rcmd *store, const Queries &Q, const uint32_t *owner)
+{
     bind_store_index(b, store, Q, owner);
-    rd_stab_queries(ctx, b);
-    rd_build_txns(ctx, b);
+}
 
-    ctx->stat("rangedeps.entries", b.NE);
-    ctx->stat("rangedeps.stored_ranges", b.n_dict);
+void rcmd_rangedeps_stats(acc_ctx *ctx, const acc_rcmd *store, const RdBuild &b, bool stabbed)
+{
+    ctx->stat("rangedeps.entries", store->NE);
+    ctx->stat("rangedeps.stored_ranges", store->n_dict);
     ctx->stat("rangedeps.queries", b.Q);
-    ctx->stat("rangedeps.raw_entries", b.E);
+    ctx->stat("rangedeps.raw_entries", stabbed ? b.E : 0);
+    if (!stabbed) return;
     ctx->stat("rangedeps.stab_passes", b.stab_passes);
     ctx->stat("rangedeps.s16_txns", b.tier_txns[1]);
     ctx->stat("rangedeps.s32_txns", b.tier_txns[11]);
     ctx->stat("rangedeps.s64_txns", b.tier_txns[2]);
     ctx->stat("rangedeps.block_txns", b.block_txns);
     ctx->stat("rangedeps.global_txns", b.tier_txns[10]);
+}
+
+void rcmd_publish_view(acc_ctx *ctx, const RdBuild &b, acc_rangedeps_view *view) { publish_view(ctx, b, view); }
+
+void rcmd_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *in, acc_rangedeps_view *view)
+{
+    if (!store || !in || !view) fail(ACC_E_ARG, "null argument");
+    RdBuild b = rcmd_begin_rangedeps(ctx, store, in);
+    auto empty = [&] {
+        publish_empty(ctx, store, b, view);
+        rcmd_rangedeps_stats(ctx, store, b, false);
+        ctx->sync();
+    };
+    if (in->n_query == 0) return empty();
+
+    // ---- stage and validate; the per-query rows
+    uint32_t *owner = nullptr;
+    const Queries Q = rcmd_prep_rangedeps(ctx, store, in, b, owner);
+    if (store->NE == 0) return empty();   // nothing to stab: no commands, or none with ranges that is not erased
+
+    // ---- the reused stages over the store's index
+    bind_store_index(b, store, Q, owner);
+    rd_stab_queries(ctx, b);
+    rd_build_txns(ctx, b);
+    rcmd_rangedeps_stats(ctx, store, b, true);
     ctx->sync();
     publish_view(ctx, b, view);
 }

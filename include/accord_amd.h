@@ -939,7 +939,8 @@ int  acc_cfk_missing(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_batch_view *out);
  * Stats: cfk.redundant_keys_advanced, cfk.redundant_entries_dropped, cfk.redundant_missing_dropped; cfk.deps_trimmed
  * (set by acc_cfk_apply_deps); cfk.redundant_prune_us / cfk.redundant_view_us (stream time of the prune passes and of
  * the view rebuild).
- * Out of scope: RedundantBefore.collectDeps (:418-421: the (range, bound) range deps added to PreAccept results), the
+ * RedundantBefore.collectDeps (:418-421: the (range, bound) range deps added to PreAccept results) is
+ * acc_rcmd_partial_rangedeps, read from the range-command store's copy of the map. Out of scope: the
  * locally-redundant, bootstrap and stale fields of an Entry, and registerHistorical. (The range-command store is
  * pruned by its own call, acc_rcmd_redundant_before below.)
  * acc_cfk_redundant_view describes the map: closed intervals over the key codes, ascending and disjoint (adjacent
@@ -1267,13 +1268,67 @@ int  acc_rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recov
  * rcmd.redundant_ranges_before / rcmd.redundant_ranges_after (table ranges), rcmd.update_ranges_trimmed (input ranges
  * the registration pre-pass changed or removed; set by the update calls), rcmd.redundant_prune_us /
  * rcmd.redundant_index_us (stream time of the prune passes and of the index rebuild).
- * Out of scope: RedundantBefore.collectDeps, the (range, bound) deps PreAccept adds to its result
- * (RedundantBefore.java:181-190, 418-421); an Entry's locally-redundant, bootstrap and stale fields;
+ * RedundantBefore.collectDeps, the (range, bound) deps PreAccept adds to its result (RedundantBefore.java:181-190,
+ * 418-421), is acc_rcmd_partial_rangedeps below.
+ * Out of scope: an Entry's locally-redundant, bootstrap and stale fields;
  * historicalRangeCommands and maxRedundant (InMemoryCommandStore.java:350-354, 366); removing the tombstones of erased
  * commands; the state of a dropped command: it is gone, a later acc_rcmd_update_cmds of that TxnId carries its own
  * state and a plain acc_rcmd_update re-inserts it NotDefined, as for any absent TxnId. */
 int  acc_rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in);
 int  acc_rcmd_redundant_view(acc_ctx *ctx, acc_rcmd *store, acc_cfk_redundant_map *out);
+
+/* PreAccept's RangeDeps from the pruned store: the stab result with RedundantBefore.collectDeps' range deps.
+ * PreAccept.calculatePartialDeps (messages/PreAccept.java:245-265) returns builder.build().with(redundant), where
+ * redundant = RedundantBefore.collectDeps (local/RedundantBefore.java:181-190, 418-421) holds one (entry.range,
+ * shardAppliedOrInvalidatedBefore) range dep for every RedundantBefore entry a participant of the txn touches
+ * (ReducingRangeMap.foldl, utils/ReducingRangeMap.java:120-196): the dep on the sync point stands for every dep the
+ * prune removed. acc_rcmd_partial_rangedeps is acc_rcmd_rangedeps with that second side, so that with
+ * acc_cfk_keydeps(_mixed) it is the whole PartialDeps of calculatePartialDeps from resident state (collectDeps adds no
+ * key dep).
+ * The map is the store's own (acc_rcmd_redundant_view): an Entry is modelled by its shardAppliedOrInvalidatedBefore
+ * alone, and since Builder.tryMergeEqual and slice (RedundantBefore.java:470-496) keep entry.range equal to the map
+ * segment and merge touching entries that are otherwise equal, a maximal interval m = [st, en] of the view is exactly
+ * one entry.range: Range(m) = (st - 1, en] on an EndInclusive store, [st, en + 1) otherwise. Epoch bounds are
+ * unmodelled (outOfBounds is never true).
+ * Per query q, I(q) = the intervals m with bound[m] > TxnId.NONE that a participant of q touches: a key k when
+ * st <= k <= en, a range when it intersects Range(m) as a set of keys (touching ends do not intersect); each interval
+ * once per query. Nothing else filters: no STARTED_BEFORE test against executeAt (the reference carries a TODO there,
+ * PreAccept.java:261), no witnesses() test, no exclusion of the query's own TxnId, and whatever the domain of the bound
+ * TxnId the pair is a range dep (Deps.AbstractBuilder.add routes by the range's domain, primitives/Deps.java:56-71).
+ * The result of q is Stab(q).with(Redundant(q)) (RangeDeps.with, primitives/RangeDeps.java:567-581, a linearUnion):
+ * Stab(q) what acc_rcmd_rangedeps returns, Redundant(q) the RangeDeps of {(Range(m), bound[m]) : m in I(q)}; ranges by
+ * Range::compare, TxnIds by compareTo, each range's list the union of both sides, a (range, TxnId) pair of both sides
+ * (the sync point stored as a range command whose range equals the interval) once.
+ * rd is the context's last RangeDeps result in the acc_rcmd_rangedeps layout over two union tables: its dictionary
+ * (rd.rng_start / rng_end) is the store's dictionary merged with Range(m) of every interval with bound > NONE, equal
+ * ranges once; dep_txn index ids, the table's TxnIds (erased rows included) merged with the distinct bounds > NONE,
+ * Timestamp.equals ids once; id_row[i] is the acc_rcmd_view row of id i or 0xFFFFFFFF for a bound no row equals. Raw
+ * bits of an id: the stored row's where a row equals it (linearUnion keeps the left instance, the builder's), else the
+ * bound's as acc_rcmd_redundant_view reports them for the lowest interval holding it. (In a query whose stab result
+ * lacks that command the reference would carry the bound's own instance; the two differ only in bits outside
+ * Timestamp.equals, and that per-query difference is not modelled.)
+ * acc_rangedeps_copy_out copies rd, dictionary included; ids and id_row are read with acc_copy_out. Everything is valid
+ * until the next RangeDeps compute call on the context or the next update or prune of the store. The store is not
+ * modified. Validation, errors and the rangedeps.* stats are acc_rcmd_rangedeps's, by the same code in the same order.
+ * With no bound above NONE (a store never marked, or only NONE bounds) the call is acc_rcmd_rangedeps: a store never
+ * marked launches its kernels and no others, rd is bit-identical, ids are the table's columns and id_row[i] = i. (A map
+ * of NONE bounds only is found to be one by the index build of the first call after it changed.) An empty store with a
+ * non-empty map still returns the redundant deps.
+ * The union tables, the per-interval ids and the stabbing index's (range id, TxnId position) column renamed into them
+ * are cached in the store: built by the first call after an acc_rcmd_update*, or an acc_rcmd_redundant_before with
+ * ranges, and reused until the next one (updates and prunes themselves do no work for it).
+ * Stats: rcmd.partial_intervals (the sum of |I(q)|), rcmd.partial_pairs_shared (pairs of both sides),
+ * rcmd.union_builds (index builds over the store's life), rcmd.union_ids, rcmd.union_ranges.
+ * Out of scope: PartialDeps.covering; a variant reading the CommandsForKey store's map (ReplicaStore keeps the two
+ * maps equal). */
+typedef struct acc_rcmd_partial_view {
+    acc_rangedeps_view rd;   /* n_txn = n_query; rd.rng_start / rng_end [rd.n_ranges]: the union dictionary; range_id
+                                index it, dep_txn index ids, arena holds positions in the query's own dep_txn list */
+    uint32_t    n_ids, n_cmd;
+    acc_ts_cols ids;         /* [n_ids] DEVICE */
+    const uint32_t *id_row;  /* [n_ids] DEVICE */
+} acc_rcmd_partial_view;
+int  acc_rcmd_partial_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rcmd_partial_view *out);
 
 /* ---- MaxConflicts and the PreAccept executeAt proposal (local/MaxConflicts.java:31-96,
  * local/CommandStore.java:280-290 updateMaxConflicts, :320-345 preaccept) ----
