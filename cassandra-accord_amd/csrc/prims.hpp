@@ -839,17 +839,48 @@ static inline OsWords os_words(acc_ctx *ctx, const char *tag, size_t words)
     return OsWords{ b[s.par], b[s.par ^ 1], (uint32_t)s.dirty[s.par ^ 1], &s, words };
 }
 
+// The three-launch sort: per pass a tile histogram, a column scan per digit and a stable scatter, with no look-back
+// between tiles and so no bound on n or on the passes. radix_sort reaches it only where the one-sweep sort's 30-bit
+// status counts do not hold the size, n >= 2^30 - 1 (bits <= 64 keeps passes <= OS_MAXP): the largest sorts of a
+// store, which no test can afford. The test shim (prims_test.hip) calls it directly at small n. k / v are the
+// "<tag>_k?" / "<tag>_v?" buffers of n elements; n > 0 and passes > 0 (radix_sort returns before for either).
+static inline Sorted radix_sort_3launch(acc_ctx *ctx, const char *tag, const uint64_t *keys, const uint32_t *vals, size_t n,
+                                        int passes, uint64_t *const k[2], uint32_t *const v[2])
+{
+    char nh[40], th[48], ts[48];
+    snprintf(th, sizeof th, "%s.hist", tag);
+    snprintf(ts, sizeof ts, "%s.scatter", tag);
+    snprintf(nh, sizeof nh, "%s_hist", tag);
+    const uint32_t ntiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
+    uint32_t *hist = ctx->get<uint32_t>(nh, (size_t)256 * ntiles);
+    char nt[48];
+    snprintf(nt, sizeof nt, "%s_dtot", tag);
+    uint32_t *dtot = ctx->get<uint32_t>(nt, 256);
+    const uint64_t *kin = keys;
+    const uint32_t *vin = vals;
+    int cur = 0;
+    for (int p = 0; p < passes; ++p) {
+        int shift = 8 * p;
+        launch(ctx, th, k_rs_hist, dim3(ntiles), dim3(BLOCK), 0, kin, n, shift, hist, ntiles);
+        launch(ctx, "rs_colscan", k_rs_colscan, dim3(256), dim3(BLOCK), 0, hist, ntiles, dtot);
+        launch(ctx, ts, k_rs_scatter, dim3(ntiles), dim3(BLOCK), 0, kin, vin, k[cur], v[cur], n, shift,
+               (const uint32_t *)hist, (const uint32_t *)dtot, ntiles, (p == 0 && !vals) ? 1 : 0);
+        kin = k[cur];
+        vin = v[cur];
+        cur ^= 1;
+    }
+    return { (uint64_t *)kin, (uint32_t *)vin };
+}
+
 // Stable sort of n (key, value) pairs by the low `bits` bits of key (higher bits must be zero).
 // vals == nullptr sorts with values = index. Results live in context buffers "<tag>_k?/_v?" and stay
 // valid until the next sort with the same tag.
 static inline Sorted radix_sort(acc_ctx *ctx, const char *tag, const uint64_t *keys, const uint32_t *vals, size_t n, int bits)
 {
-    char nk0[40], nk1[40], nv0[40], nv1[40], nh[40], th[48], ts[48];
-    snprintf(th, sizeof th, "%s.hist", tag);
+    char nk0[40], nk1[40], nv0[40], nv1[40], th[48], ts[48];
     snprintf(ts, sizeof ts, "%s.scatter", tag);
     snprintf(nk0, sizeof nk0, "%s_k0", tag); snprintf(nk1, sizeof nk1, "%s_k1", tag);
     snprintf(nv0, sizeof nv0, "%s_v0", tag); snprintf(nv1, sizeof nv1, "%s_v1", tag);
-    snprintf(nh, sizeof nh, "%s_hist", tag);
     uint64_t *k[2] = { ctx->get<uint64_t>(nk0, n), ctx->get<uint64_t>(nk1, n) };
     uint32_t *v[2] = { ctx->get<uint32_t>(nv0, n), ctx->get<uint32_t>(nv1, n) };
     int passes = (bits + 7) / 8;
@@ -888,25 +919,7 @@ static inline Sorted radix_sort(acc_ctx *ctx, const char *tag, const uint64_t *k
         }
         return { (uint64_t *)kin, (uint32_t *)vin };
     }
-    const uint32_t ntiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE);
-    uint32_t *hist = ctx->get<uint32_t>(nh, (size_t)256 * ntiles);
-    char nt[48];
-    snprintf(nt, sizeof nt, "%s_dtot", tag);
-    uint32_t *dtot = ctx->get<uint32_t>(nt, 256);
-    const uint64_t *kin = keys;
-    const uint32_t *vin = vals;
-    int cur = 0;
-    for (int p = 0; p < passes; ++p) {
-        int shift = 8 * p;
-        launch(ctx, th, k_rs_hist, dim3(ntiles), dim3(BLOCK), 0, kin, n, shift, hist, ntiles);
-        launch(ctx, "rs_colscan", k_rs_colscan, dim3(256), dim3(BLOCK), 0, hist, ntiles, dtot);
-        launch(ctx, ts, k_rs_scatter, dim3(ntiles), dim3(BLOCK), 0, kin, vin, k[cur], v[cur], n, shift,
-               (const uint32_t *)hist, (const uint32_t *)dtot, ntiles, (p == 0 && !vals) ? 1 : 0);
-        kin = k[cur];
-        vin = v[cur];
-        cur ^= 1;
-    }
-    return { (uint64_t *)kin, (uint32_t *)vin };
+    return radix_sort_3launch(ctx, tag, keys, vals, n, passes, k, v);
 }
 
 // Stable sort of n u64 keys by bits [lo, lo + bits) (bits above must be zero; bits below ride along, e.g. an index packed
