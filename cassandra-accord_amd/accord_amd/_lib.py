@@ -51,7 +51,7 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_deps_from_json", "acc_deps_to_json",
            "acc_cfk_create", "acc_cfk_destroy", "acc_cfk_update", "acc_cfk_view", "acc_cfk_apply", "acc_cfk_snap_to_batch",
            "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed",
-           "acc_cfk_map_reduce_full", "acc_cfk_redundant_before", "acc_cfk_redundant_view", "acc_max_conflicts",
+           "acc_cfk_map_reduce_full", "acc_cfk_notify", "acc_cfk_redundant_before", "acc_cfk_redundant_view", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
@@ -331,6 +331,21 @@ class CfkRedundantMap(C.Structure):
                 ("bound", TsCols)]
 
 
+class CfkNotifyIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_keys", C.c_uint32), ("key_code", C.c_void_p), ("tier", C.c_uint32)]
+
+
+class CfkNotifyView(C.Structure):
+    _fields_ = [("n_keys", C.c_uint32), ("n_txn", C.c_uint32), ("n_events", C.c_uint64),
+                ("min_uncommitted", C.c_void_p), ("next", C.c_void_p), ("next_write", C.c_void_p), ("ev_off", C.c_void_p),
+                ("ev_entry", C.c_void_p), ("ev_txn", C.c_void_p), ("ev_pos", C.c_void_p), ("ev_kind", C.c_void_p),
+                ("rel_keys", C.c_void_p)]
+
+
+ACC_NOTIFY_WAITING_TO_EXECUTE, ACC_NOTIFY_RELEASE = 0, 1
+ACC_NOTIFY_NONE = 0xFFFFFFFF
+ACC_NOTIFY_TIER_LANE, ACC_NOTIFY_TIER_WAVE, ACC_NOTIFY_TIER_SORT = 1, 2, 3
+
 ACC_RCMD_ERASED = 1
 
 
@@ -569,6 +584,8 @@ def load():
         L.acc_cfk_keydeps_mixed.restype = C.c_int
         L.acc_cfk_map_reduce_full.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRecoveryIn), C.POINTER(KeydepsView)]
         L.acc_cfk_map_reduce_full.restype = C.c_int
+        L.acc_cfk_notify.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkNotifyIn), C.POINTER(CfkNotifyView)]
+        L.acc_cfk_notify.restype = C.c_int
         L.acc_cfk_redundant_before.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantIn)]
         L.acc_cfk_redundant_before.restype = C.c_int
         L.acc_cfk_redundant_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantMap)]

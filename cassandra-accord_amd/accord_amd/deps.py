@@ -1021,6 +1021,9 @@ class MaxConflictsMap:
 
 # ---------------------------------------------------------------- device-resident CommandsForKey store
 
+_EMPTY_KEY = np.zeros(1, np.uint64)   # a non-NULL key_code for an empty list of asked keys
+
+
 class CfkStore:
     """A CommandsForKey store kept in HBM and updated by batches of commands (acc_cfk_*): CommandsForKey.update for
     every key of every command (local/CommandsForKey.java:652-706)."""
@@ -1162,6 +1165,35 @@ class CfkStore:
         view = L.KeydepsView()
         self.ctx.check(self.ctx._lib.acc_cfk_map_reduce_full(self.ctx.handle, self._h, C.byref(ri), C.byref(view)))
         return self.ctx.copy_out(view, None)
+
+    def notify(self, keys=None, tier: int = 0) -> dict:
+        """CommandsForKey.notify's releases for the asked keys (acc_cfk_notify; local/CommandsForKey.java:1501-1635 over
+        the derived fields of :422-470): keys = sorted unique key codes, None for every key of the store. Host arrays
+        out: key (the asked codes; state()'s keys for None); min_uncommitted, next, next_write [n_keys]: entry indices
+        into state()'s entry columns, L.ACC_NOTIFY_NONE for null; ev_off [n_keys + 1]; per event, in TxnId order within
+        its key, ev_entry (state() entry), ev_txn (index into view() order), ev_kind (L.ACC_NOTIFY_WAITING_TO_EXECUTE for
+        a COMMITTED entry, L.ACC_NOTIFY_RELEASE for a STABLE entry that no longer waits on the key), ev_pos (the
+        entry's index in committed[]); rel_keys [view txns]: the asked keys that release each txn. tier forces one
+        ranking tier (L.ACC_NOTIFY_TIER_*); results do not depend on it. The store is not modified."""
+        kc = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+        ni = L.CfkNotifyIn(L.ACC_MEM_HOST, 0 if kc is None else len(kc),
+                           None if kc is None else (kc.ctypes.data if len(kc) else _EMPTY_KEY.ctypes.data), int(tier))
+        v = L.CfkNotifyView()
+        self.ctx.check(self.ctx._lib.acc_cfk_notify(self.ctx.handle, self._h, C.byref(ni), C.byref(v)))
+        nk, ne, nt = int(v.n_keys), int(v.n_events), int(v.n_txn)
+        g = lambda ptr, cnt, dt: device_array(self.ctx, ptr, cnt, dt) if cnt else np.zeros(0, dt)  # noqa: E731
+        out = dict(min_uncommitted=g(v.min_uncommitted, nk, np.uint32), next=g(v.next, nk, np.uint32),
+                   next_write=g(v.next_write, nk, np.uint32), ev_off=g(v.ev_off, nk + 1, np.uint64),
+                   ev_entry=g(v.ev_entry, ne, np.uint32), ev_txn=g(v.ev_txn, ne, np.uint32), ev_pos=g(v.ev_pos, ne, np.uint32),
+                   ev_kind=g(v.ev_kind, ne, np.uint8), rel_keys=g(v.rel_keys, nt, np.uint32))
+        if kc is None and nk == 0:
+            kc = np.zeros(0, np.uint64)
+        if kc is None:
+            s = L.CfkSnap()
+            self.ctx.check(self.ctx._lib.acc_cfk_state(self.ctx.handle, self._h, C.byref(s)))
+            kc = g(s.key, nk, np.uint64)
+        out["key"] = kc
+        return out
 
     def redundant_before(self, ranges: dict, end_inclusive: int = 1):
         """Advance the store's RedundantBefore (acc_cfk_redundant_before; CommandsForKey.withRedundantBefore,
@@ -1449,7 +1481,7 @@ class ReplicaStore:
         self.rcmd = RangeCmdStore(ctx, end_inclusive)
 
     def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True,
-                        range_part: dict | None = None, redundant_deps: bool = False) -> dict:
+                        range_part: dict | None = None, redundant_deps: bool = False, notify: bool = False) -> dict:
         """part: the batch's updates (cfk_update_stream layout); queries: its PreAccept queries (default: one per
         command first seen in part). Returns dict(propose = MaxConflicts.get + fast path per query, keydeps = the
         KeyDeps of every txn of the store after the batch, when scan). scan="new": instead keydeps_new = the KeyDeps of
@@ -1464,7 +1496,10 @@ class ReplicaStore:
         redundant_deps (with scan="new"): instead of rangedeps_new the result holds partial_rangedeps_new =
         RangeCmdStore.partial_rangedeps of the same queries, the range half with the (range, bound) deps
         RedundantBefore.collectDeps adds for what mark_shard_durable pruned: with keydeps_new the whole PartialDeps of
-        PreAccept.calculatePartialDeps."""
+        PreAccept.calculatePartialDeps.
+        notify: the result also holds notify = CfkStore.notify over the keys part's updates touched, read from the
+        store after the batch: the Stable commands that lost their wait on one of those keys (step 3 of execution
+        ordering, CommandsForKey.notify)."""
         from . import workload as W
         q = W.preaccept_queries(part) if queries is None else queries
         out = dict(propose=self.mc.get(q))
@@ -1506,7 +1541,13 @@ class ReplicaStore:
                 out["rangedeps_new"] = self.rcmd.rangedeps(nq)
         elif scan:
             out["keydeps"] = self.cfk.calculate_partial_deps()
+        if notify:
+            out["notify"] = self.cfk.notify(np.unique(np.asarray(part["key"], dtype=np.uint64)))
         return out
+
+    def notify(self, keys=None) -> dict:
+        """CfkStore.notify on this store's CommandsForKey: the execution releases of the asked keys (None: every key)."""
+        return self.cfk.notify(keys)
 
     _RECOVERY_NAMES = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
                            stable_started_before_with="stableStartedBeforeAndWitnessed",

@@ -43,6 +43,7 @@ void cfk_free(acc_cfk *cfk);
 void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keydeps_view *view);
 void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *view);
 void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *view);
+void cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out);
 acc_cfk *cfk_new(int device);
 acc_rcmd *rcmd_new(int device, uint32_t end_inclusive);
 void rcmd_free(acc_rcmd *store);
@@ -314,6 +315,15 @@ int acc_cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_redundant_before(ctx, cfk, in);
+    });
+}
+
+int acc_cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_notify(ctx, cfk, in, out);
     });
 }
 

@@ -1073,6 +1073,64 @@ typedef struct acc_cfk_recovery_in {
 } acc_cfk_recovery_in;
 int  acc_cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *out_view);
 
+/* ---- Execution releases from the resident CommandsForKey store ----
+ * acc_cfk_notify reads the key-major state (acc_cfk_state: status, executeAt, missing[] of every TxnInfo) and answers,
+ * for every asked key, what CommandsForKey.notify (local/CommandsForKey.java:1501-1635, behind notifyAndUpdatePending,
+ * :1163-1215) tells Commands.removeWaitingOnKeyAndMaybeExecute (local/Commands.java:859-876): the derived fields of the
+ * CommandsForKey constructor (:422-470) and the events of the full-range scan notify(AnyGloballyVisible, 0,
+ * committed.length). APPLIED and INVALID_OR_TRUNCATED entries pass the scan's counters (:1524-1526), so a scan from index
+ * 0 equals a scan from `next`; every window notifyAndUpdatePending asks for starts at next.executeAt or Timestamp.NONE,
+ * so each reference call's events are a prefix, in committed[] order, of the events given here (ev_pos cuts it); `kinds`
+ * filters only the COMMITTED branch. The store is not modified.
+ * Per key, over its entries in TxnId order (Timestamp.compareTo throughout): an entry is uncommitted below COMMITTED
+ * (ordinals 0..3), committed-class when COMMITTED, STABLE or APPLIED; INVALID_OR_TRUNCATED is neither.
+ *   min_uncommitted  the first uncommitted entry;
+ *   next             the COMMITTED or STABLE entry with the least executeAt, ties to the lower TxnId (strict >, :442-445);
+ *   next_write       the same among Writes; each of the two is null when min_uncommitted < its executeAt (:451-458);
+ *   committed[]      the committed-class entries sorted by executeAt, ties in TxnId order (a stable sort).
+ * For a STABLE entry T of kind k with executeAt X: c[W], c[R], c[S] count the COMMITTED and STABLE entries before T in
+ * committed[] by class (Write; Read; SyncPoint or ExclusiveSyncPoint), u[.] the uncommitted entries with TxnId < X by
+ * the same classes (TRANSITIVELY_KNOWN and HISTORICAL ones by their kind: the closed form of the uncommittedIndex
+ * backfill, :1540-1570). expect = (c+u)[W] for a Read, plus (c+u)[R] for a Write, plus (c+u)[S] for a sync point.
+ * missingCount = |missing(T)|, less the ids below min_uncommitted when both exist (:1596-1603). T is released iff
+ * expect == missingCount: an ACC_NOTIFY_RELEASE event. Every COMMITTED entry gives an ACC_NOTIFY_WAITING_TO_EXECUTE
+ * event (the progress-log call, :1528-1537); a STABLE entry that is held gives none.
+ * Input: key_code sorted unique (NULL: every key of the store, n_keys ignored); a key without a CFK gives an empty row.
+ * Output (DEVICE pointers, valid until the context's next compute call): per row min_uncommitted / next / next_write as
+ * entry indices into the acc_cfk_state entry columns (ACC_NOTIFY_NONE: null) and ev_off; per event, in TxnId order
+ * within the row, ev_entry (acc_cfk_state entry), ev_txn (index into the acc_cfk_view txn order, the dep_txn convention
+ * of acc_cfk_keydeps), ev_kind and ev_pos (the entry's index in committed[], applied entries included); per view txn
+ * rel_keys = the number of asked keys that release it, to compare with its set WaitingOn key bits.
+ * tier: the bumped (executeAt != TxnId) committed-class entries of a key are ranked by a lane, a wave or the store-wide
+ * sort by their number; a non-zero tier forces one (where the key fits it, else the sort). Results do not depend on it.
+ * Errors: mem, an unknown tier, unsorted or duplicate keys: ACC_E_ARG; a LocalOnly or EphemeralRead entry in an asked
+ * key (the reference's illegalState), a non-empty status-only store (acc_cfk_update): ACC_E_STATE. An empty store and
+ * n_keys == 0 give empty results; a failed call leaves the context usable. Stats: cfk.notify_keys, cfk.notify_candidates
+ * (COMMITTED or STABLE entries of the asked keys), cfk.notify_releases, cfk.notify_sorted, cfk.notify_us.
+ * Out of scope: Unmanaged pending records (notifyUnmanaged, registerUnmanaged); the progress-log side of
+ * notifyWaitingOnCommit (min_uncommitted is given for the caller to do it); the range-command half of WaitingOn. */
+#define ACC_NOTIFY_WAITING_TO_EXECUTE 0
+#define ACC_NOTIFY_RELEASE            1
+#define ACC_NOTIFY_NONE               0xFFFFFFFFu
+#define ACC_NOTIFY_TIER_LANE          1
+#define ACC_NOTIFY_TIER_WAVE          2
+#define ACC_NOTIFY_TIER_SORT          3
+typedef struct acc_cfk_notify_in {
+    uint32_t mem, n_keys;
+    const uint64_t *key_code;   /* sorted unique; NULL: every key of the store */
+    uint32_t tier;              /* 0: library default; other values force one kernel tier (tests) */
+} acc_cfk_notify_in;
+typedef struct acc_cfk_notify_view {
+    uint32_t n_keys, n_txn;
+    uint64_t n_events;
+    const uint32_t *min_uncommitted, *next, *next_write;   /* [n_keys] */
+    const uint64_t *ev_off;                                /* [n_keys + 1] */
+    const uint32_t *ev_entry, *ev_txn, *ev_pos;            /* [n_events] */
+    const uint8_t  *ev_kind;                               /* [n_events] */
+    const uint32_t *rel_keys;                              /* [n_txn] */
+} acc_cfk_notify_view;
+int  acc_cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out);
+
 /* ---- A device-resident range-command store and the RangeDeps of new txns ----
  * The other half of PreAccept.calculatePartialDeps beside acc_cfk_keydeps_mixed: the deps on the store's range commands
  * (InMemorySafeStore.mapReduceActive -> mapReduceRangesInternal, impl/InMemoryCommandStore.java:863-870, 883-960). The
