@@ -51,7 +51,8 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_deps_from_json", "acc_deps_to_json",
            "acc_cfk_create", "acc_cfk_destroy", "acc_cfk_update", "acc_cfk_view", "acc_cfk_apply", "acc_cfk_snap_to_batch",
            "acc_cfk_apply_deps", "acc_cfk_state", "acc_cfk_missing", "acc_cfk_keydeps", "acc_cfk_keydeps_mixed",
-           "acc_cfk_map_reduce_full", "acc_cfk_notify", "acc_cfk_redundant_before", "acc_cfk_redundant_view", "acc_max_conflicts",
+           "acc_cfk_map_reduce_full", "acc_cfk_notify", "acc_cfk_register_unmanaged", "acc_cfk_notify_unmanaged",
+           "acc_cfk_unmanaged_view", "acc_cfk_redundant_before", "acc_cfk_redundant_view", "acc_max_conflicts",
            "acc_maxconflicts_create", "acc_maxconflicts_destroy", "acc_maxconflicts_update", "acc_maxconflicts_get",
            "acc_maxconflicts_size",
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
@@ -346,6 +347,36 @@ ACC_NOTIFY_WAITING_TO_EXECUTE, ACC_NOTIFY_RELEASE = 0, 1
 ACC_NOTIFY_NONE = 0xFFFFFFFF
 ACC_NOTIFY_TIER_LANE, ACC_NOTIFY_TIER_WAVE, ACC_NOTIFY_TIER_SORT = 1, 2, 3
 
+
+class CfkUnmanagedIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_waiters", C.c_uint32), ("n_pairs", C.c_uint64), ("n_deps", C.c_uint64),
+                ("txn_id", TsCols), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
+                ("dep_off", C.c_void_p), ("deps", TsCols), ("tier", C.c_uint32)]
+
+
+class CfkUnmanagedOut(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("n_inserted", C.c_uint64), ("outcome", C.c_void_p), ("until", TsCols)]
+
+
+class CfkUnmanagedTable(C.Structure):
+    _fields_ = [("n_rec", C.c_uint32), ("n_deps", C.c_uint64), ("key", C.c_void_p), ("pending", C.c_void_p),
+                ("until", TsCols), ("txn_id", TsCols), ("execute_at", TsCols), ("dep_off", C.c_void_p), ("deps", TsCols)]
+
+
+class CfkUnmanagedNotifyIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_keys", C.c_uint32), ("key_code", C.c_void_p)]
+
+
+class CfkUnmanagedEvents(C.Structure):
+    _fields_ = [("n_events", C.c_uint32), ("n_rec", C.c_uint32), ("ev_kind", C.c_void_p), ("ev_flags", C.c_void_p),
+                ("ev_key", C.c_void_p), ("ev_txn", TsCols), ("ev_until", TsCols)]
+
+
+ACC_UNM_COMMIT, ACC_UNM_APPLY = 0, 1
+ACC_UNM_READY, ACC_UNM_PENDING_COMMIT, ACC_UNM_PENDING_APPLY = 0, 1, 2
+ACC_UNM_TIER_LANE, ACC_UNM_TIER_WAVE = 1, 2
+ACC_UNM_EV_TO_APPLY, ACC_UNM_EV_RELEASE = 0, 1
+
 ACC_RCMD_ERASED = 1
 
 
@@ -586,6 +617,13 @@ def load():
         L.acc_cfk_map_reduce_full.restype = C.c_int
         L.acc_cfk_notify.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkNotifyIn), C.POINTER(CfkNotifyView)]
         L.acc_cfk_notify.restype = C.c_int
+        L.acc_cfk_register_unmanaged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkUnmanagedIn), C.POINTER(CfkUnmanagedOut)]
+        L.acc_cfk_register_unmanaged.restype = C.c_int
+        L.acc_cfk_notify_unmanaged.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkUnmanagedNotifyIn),
+                                               C.POINTER(CfkUnmanagedEvents)]
+        L.acc_cfk_notify_unmanaged.restype = C.c_int
+        L.acc_cfk_unmanaged_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkUnmanagedTable)]
+        L.acc_cfk_unmanaged_view.restype = C.c_int
         L.acc_cfk_redundant_before.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantIn)]
         L.acc_cfk_redundant_before.restype = C.c_int
         L.acc_cfk_redundant_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkRedundantMap)]

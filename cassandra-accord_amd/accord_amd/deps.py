@@ -1195,6 +1195,65 @@ class CfkStore:
         out["key"] = kc
         return out
 
+    def register_unmanaged(self, waiters: dict, tier: int = 0) -> dict:
+        """CommandsForKey.registerUnmanaged for every (waiter, key) pair (acc_cfk_register_unmanaged;
+        local/CommandsForKey.java:1406-1498): waiters = the apply_deps update layout without status / flags (msb, lsb,
+        node: the waiters' TxnIds, range-domain or EphemeralRead / LocalOnly; xmsb, xlsb, xnode: their executeAts;
+        key_off, key: the keys each waits on, sorted unique; dep_off, dmsb, dlsb, dnode: each pair's deps, sorted
+        unique). Host arrays out, per pair: outcome (L.ACC_UNM_READY / _PENDING_COMMIT / _PENDING_APPLY) and
+        until_msb / until_lsb / until_node (waiting_until, zeros for READY); n_inserted = the TRANSITIVELY_KNOWN entries
+        the call added to state(). Not-ready pairs become records of unmanaged(). tier forces one evaluation tier
+        (L.ACC_UNM_TIER_*); results do not depend on it."""
+        a = {k: np.ascontiguousarray(np.asarray(waiters[k], dt)) for k, dt in (
+            ("msb", np.uint64), ("lsb", np.uint64), ("node", np.int32), ("xmsb", np.uint64), ("xlsb", np.uint64),
+            ("xnode", np.int32), ("key_off", np.uint32), ("key", np.uint64), ("dep_off", np.uint32), ("dmsb", np.uint64),
+            ("dlsb", np.uint64), ("dnode", np.int32))}
+        p = lambda k: a[k].ctypes.data  # noqa: E731
+        ui = L.CfkUnmanagedIn(L.ACC_MEM_HOST, len(a["msb"]), len(a["key"]), len(a["dmsb"]), L.TsCols(p("msb"), p("lsb"), p("node")),
+                              L.TsCols(p("xmsb"), p("xlsb"), p("xnode")), p("key_off"), p("key"), p("dep_off"),
+                              L.TsCols(p("dmsb"), p("dlsb"), p("dnode")), int(tier))
+        o = L.CfkUnmanagedOut()
+        self.ctx.check(self.ctx._lib.acc_cfk_register_unmanaged(self.ctx.handle, self._h, C.byref(ui), C.byref(o)))
+        n = int(o.n_pairs)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, n, dt) if n else np.zeros(0, dt)  # noqa: E731
+        return dict(outcome=g(o.outcome, np.uint8), until_msb=g(o.until.msb, np.uint64), until_lsb=g(o.until.lsb, np.uint64),
+                    until_node=g(o.until.node, np.int32), n_inserted=int(o.n_inserted))
+
+    def notify_unmanaged(self, keys=None) -> dict:
+        """notifyUnmanaged over the pending records of the asked keys (acc_cfk_notify_unmanaged;
+        local/CommandsForKey.java:1206-1212, 1270-1316, 1333-1388): keys = sorted unique key codes, None for every key
+        that has a record. Host arrays out, one event per affected record in table order: ev_kind
+        (L.ACC_UNM_EV_TO_APPLY: a COMMIT record became an APPLY record; L.ACC_UNM_EV_RELEASE: removeWaitingOn), ev_flags
+        (bit 0: re-evaluated from COMMIT in this call), ev_key, ev_txn_msb / _lsb / _node (the waiter), ev_until_msb /
+        _lsb / _node (the record's APPLY waiting_until, zeros if it never had one); n_rec = the records left."""
+        kc = None if keys is None else np.ascontiguousarray(keys, dtype=np.uint64)
+        ni = L.CfkUnmanagedNotifyIn(L.ACC_MEM_HOST, 0 if kc is None else len(kc),
+                                    None if kc is None else (kc.ctypes.data if len(kc) else _EMPTY_KEY.ctypes.data))
+        v = L.CfkUnmanagedEvents()
+        self.ctx.check(self.ctx._lib.acc_cfk_notify_unmanaged(self.ctx.handle, self._h, C.byref(ni), C.byref(v)))
+        n = int(v.n_events)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, n, dt) if n else np.zeros(0, dt)  # noqa: E731
+        return dict(ev_kind=g(v.ev_kind, np.uint8), ev_flags=g(v.ev_flags, np.uint8), ev_key=g(v.ev_key, np.uint64),
+                    ev_txn_msb=g(v.ev_txn.msb, np.uint64), ev_txn_lsb=g(v.ev_txn.lsb, np.uint64),
+                    ev_txn_node=g(v.ev_txn.node, np.int32), ev_until_msb=g(v.ev_until.msb, np.uint64),
+                    ev_until_lsb=g(v.ev_until.lsb, np.uint64), ev_until_node=g(v.ev_until.node, np.int32), n_rec=int(v.n_rec))
+
+    def unmanaged(self) -> dict:
+        """Host copy of the pending table (acc_cfk_unmanaged_view), records in registration order: key, pending
+        (L.ACC_UNM_COMMIT / L.ACC_UNM_APPLY), until_msb / _lsb / _node, msb / lsb / node (the waiter's TxnId), xmsb /
+        xlsb / xnode (its executeAt), dep_off, dmsb / dlsb / dnode (the deps a COMMIT record keeps)."""
+        t = L.CfkUnmanagedTable()
+        self.ctx.check(self.ctx._lib.acc_cfk_unmanaged_view(self.ctx.handle, self._h, C.byref(t)))
+        n, nd = int(t.n_rec), int(t.n_deps)
+        g = lambda ptr, cnt, dt: device_array(self.ctx, ptr, cnt, dt) if cnt else np.zeros(0, dt)  # noqa: E731
+        return dict(key=g(t.key, n, np.uint64), pending=g(t.pending, n, np.uint8), until_msb=g(t.until.msb, n, np.uint64),
+                    until_lsb=g(t.until.lsb, n, np.uint64), until_node=g(t.until.node, n, np.int32),
+                    msb=g(t.txn_id.msb, n, np.uint64), lsb=g(t.txn_id.lsb, n, np.uint64), node=g(t.txn_id.node, n, np.int32),
+                    xmsb=g(t.execute_at.msb, n, np.uint64), xlsb=g(t.execute_at.lsb, n, np.uint64),
+                    xnode=g(t.execute_at.node, n, np.int32),
+                    dep_off=g(t.dep_off, n + 1, np.uint32) if n else np.zeros(1, np.uint32),
+                    dmsb=g(t.deps.msb, nd, np.uint64), dlsb=g(t.deps.lsb, nd, np.uint64), dnode=g(t.deps.node, nd, np.int32))
+
     def redundant_before(self, ranges: dict, end_inclusive: int = 1):
         """Advance the store's RedundantBefore (acc_cfk_redundant_before; CommandsForKey.withRedundantBefore,
         local/CommandsForKey.java:1654-1684): ranges = dict(rng_start, rng_end: sorted, non-overlapping, start < end;
@@ -1548,6 +1607,16 @@ class ReplicaStore:
     def notify(self, keys=None) -> dict:
         """CfkStore.notify on this store's CommandsForKey: the execution releases of the asked keys (None: every key)."""
         return self.cfk.notify(keys)
+
+    def register_unmanaged(self, waiters: dict) -> dict:
+        """CfkStore.register_unmanaged on this store's CommandsForKey: a Stable command CommandsForKey does not manage (a
+        sync point, a range read, an EphemeralRead) registers on every key it waits on."""
+        return self.cfk.register_unmanaged(waiters)
+
+    def notify_unmanaged(self, keys=None) -> dict:
+        """CfkStore.notify_unmanaged on this store's CommandsForKey, after a batch: the pending records of the asked
+        keys (None: every key that has one) that move to APPLY or are released."""
+        return self.cfk.notify_unmanaged(keys)
 
     _RECOVERY_NAMES = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
                            stable_started_before_with="stableStartedBeforeAndWitnessed",

@@ -44,6 +44,9 @@ void cfk_keydeps(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_queries *q, acc_keyde
 void cfk_keydeps_mixed(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_mixed_queries *q, acc_keydeps_view *view);
 void cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_in *q, acc_keydeps_view *view);
 void cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out);
+void cfk_register_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_in *in, acc_cfk_unmanaged_out *out);
+void cfk_notify_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_notify_in *in, acc_cfk_unmanaged_events *out);
+void cfk_unmanaged_view(acc_cfk *cfk, acc_cfk_unmanaged_table *out);
 acc_cfk *cfk_new(int device);
 acc_rcmd *rcmd_new(int device, uint32_t end_inclusive);
 void rcmd_free(acc_rcmd *store);
@@ -325,6 +328,30 @@ int acc_cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_
         ACC_HIP(hipSetDevice(ctx->device));
         acc::cfk_notify(ctx, cfk, in, out);
     });
+}
+
+int acc_cfk_register_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_in *in, acc_cfk_unmanaged_out *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_register_unmanaged(ctx, cfk, in, out);
+    });
+}
+
+int acc_cfk_notify_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_notify_in *in, acc_cfk_unmanaged_events *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::cfk_notify_unmanaged(ctx, cfk, in, out);
+    });
+}
+
+int acc_cfk_unmanaged_view(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_unmanaged_table *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] { acc::cfk_unmanaged_view(cfk, out); });
 }
 
 int acc_cfk_redundant_view(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_redundant_map *out)

@@ -16,6 +16,9 @@
 #include "dict.hpp"
 #include "cfkquery.hpp"
 #include "cfkredundant.hpp"
+#include "cfkunmanaged.hpp"
+
+#include <chrono>
 
 struct acc_cfk {
     int device = 0;
@@ -53,6 +56,8 @@ struct acc_cfk {
     // acc_cfk_redundant_before: the store's RedundantBefore map (key code -> shardRedundantBefore), created by the first
     // call, which also fixes its Range bound type
     acc_maxconflicts *rb = nullptr;
+    // acc_cfk_register_unmanaged / acc_cfk_notify_unmanaged: the Unmanaged pending records (cfkunmanaged.hip)
+    acc::um::Table unm;
 };
 
 namespace acc {
@@ -386,6 +391,7 @@ void cfk_free(acc_cfk *cfk)
                      (void *)cfk->bmiss_off, (void *)cfk->bmiss_txn })
         (void)hipFree(p);
     mc_free(cfk->rb);
+    um::table_free(cfk->unm);
     delete cfk;
 }
 
@@ -555,6 +561,89 @@ void cfk_redundant_before(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_redundant_in
     ctx->stat("cfk.redundant_view_us", (uint64_t)(ms_v * 1000.0f));
     ctx->stat("cfk.redundant_entries_dropped", ne0 - r.ne);
     ctx->stat("cfk.redundant_missing_dropped", nm0 - r.nm);
+}
+
+void cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out);
+
+namespace {
+uint64_t us_since(std::chrono::steady_clock::time_point t0)
+{
+    return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+// CommandsForKey.registerUnmanaged (local/CommandsForKey.java:1406-1498) for every (waiter, key) pair, as
+// SafeCommandStore.updateCommandsForKey calls it for a command CommandsForKey does not manage
+// (local/SafeCommandStore.java:246-268): the pairs evaluated against the state as it stands (cfkunmanaged.hip), the
+// missing deps merged in as TRANSITIVELY_KNOWN entries and adopted as acc_cfk_apply_deps adopts its result, then the
+// not-ready pairs appended to the pending table. A failure before the adoption leaves the store and the table as they were.
+void cfk_register_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_in *in, acc_cfk_unmanaged_out *out)
+{
+    if (!cfk || !in || !out) fail(ACC_E_ARG, "null argument");
+    if (in->mem != ACC_MEM_HOST && in->mem != ACC_MEM_DEVICE) fail(ACC_E_ARG, "mem must be ACC_MEM_HOST or ACC_MEM_DEVICE");
+    if (in->tier > ACC_UNM_TIER_WAVE) fail(ACC_E_ARG, "tier must be 0 (default) or ACC_UNM_TIER_LANE / _WAVE");
+    if (!cfk->deps && cfk->n)
+        fail(ACC_E_STATE, "the store holds status-only state (acc_cfk_update): it has no key-major CommandsForKey to register on");
+    const auto t0 = std::chrono::steady_clock::now();
+    *out = acc_cfk_unmanaged_out{};
+    for (const char *z : { "cfk.unmanaged_pairs", "cfk.unmanaged_ready", "cfk.unmanaged_pending_commit", "cfk.unmanaged_pending_apply",
+                           "cfk.unmanaged_tk_inserted" })
+        ctx->stat(z, 0);
+    ctx->stat("cfk.unmanaged_records", cfk->unm.n_rec);
+    if (in->n_waiters == 0) return;
+    acc_cfk::KeyMajor &k = cfk->km;
+    if (!k.ent_off) {   // empty state: offsets [0]
+        realloc_dev(k.ent_off, 1);
+        realloc_dev(k.miss_off, 1);
+        k.bytes[1] = k.bytes[9] = 4;
+        ACC_HIP(hipMemsetAsync(k.ent_off, 0, 4, ctx->stream));
+        ACC_HIP(hipMemsetAsync(k.miss_off, 0, 4, ctx->stream));
+    }
+    const CfkResident s = cfk_resident(cfk);
+    const um::Registered r = um::register_eval(ctx, cfk->rb, s, k.ne, k.nm, cfk->unm, in, out);
+    if (r.n_inserted) {
+        const acc_cfk_snap_view &v = r.view;
+        const acc_cfk_snap next{ ACC_MEM_DEVICE, v.n_keys, v.n_entries, v.n_missing, v.key, v.ent_off, v.txn_id, v.execute_at,
+                                 v.status, v.miss_off, v.missing };
+        acc_cfk_batch_view bv{};
+        cfk_snap_to_batch(ctx, &next, &bv, true);
+        adopt_result(ctx, cfk, v, bv);
+        cfk->deps = true;
+    }
+    um::register_append(ctx, cfk->unm, r);
+    ctx->sync();
+    ctx->stat("cfk.unmanaged_pairs", r.n_pairs);
+    ctx->stat("cfk.unmanaged_ready", r.ready);
+    ctx->stat("cfk.unmanaged_pending_commit", r.pending_commit);
+    ctx->stat("cfk.unmanaged_pending_apply", r.pending_apply);
+    ctx->stat("cfk.unmanaged_tk_inserted", r.n_inserted);
+    ctx->stat("cfk.unmanaged_records", cfk->unm.n_rec);
+    ctx->stat("cfk.unmanaged_register_us", us_since(t0));
+}
+
+// The tail of notifyAndUpdatePending (local/CommandsForKey.java:1206-1212) for the records of the asked keys:
+// acc_cfk_notify for minUncommitted / next, then the COMMIT and APPLY steps of notifyUnmanaged (cfkunmanaged.hip).
+void cfk_notify_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_notify_in *in, acc_cfk_unmanaged_events *out)
+{
+    if (!cfk || !in || !out) fail(ACC_E_ARG, "null argument");
+    const auto t0 = std::chrono::steady_clock::now();
+    acc_cfk_notify_in ni{};
+    ni.mem = in->mem; ni.n_keys = in->n_keys; ni.key_code = in->key_code; ni.tier = 0;
+    acc_cfk_notify_view nv{};
+    cfk_notify(ctx, cfk, &ni, &nv);
+    const CfkResident s = cfk_resident(cfk);
+    const uint64_t *akey = in->key_code ? stage_in(ctx, "um_in_akey", in->key_code, in->n_keys, in->mem) : nullptr;
+    um::notify(ctx, cfk->rb, s, cfk->unm, akey, in->key_code ? in->n_keys : 0, nv.min_uncommitted, nv.next, out);
+    ctx->stat("cfk.unmanaged_records", cfk->unm.n_rec);
+    ctx->stat("cfk.unmanaged_notify_us", us_since(t0));
+}
+
+void cfk_unmanaged_view(acc_cfk *cfk, acc_cfk_unmanaged_table *out)
+{
+    if (!cfk || !out) fail(ACC_E_ARG, "null argument");
+    const um::Table &t = cfk->unm;
+    *out = acc_cfk_unmanaged_table{ t.n_rec, t.n_dep, t.key, t.pending, acc_ts_cols{ t.um, t.ul, t.un }, acc_ts_cols{ t.tm, t.tl, t.tn },
+                                    acc_ts_cols{ t.xm, t.xl, t.xn }, t.dep_off, acc_ts_cols{ t.dm, t.dl, t.dn } };
 }
 
 void cfk_redundant_view(acc_cfk *cfk, acc_cfk_redundant_map *out)

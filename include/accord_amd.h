@@ -1107,8 +1107,9 @@ int  acc_cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_
  * key (the reference's illegalState), a non-empty status-only store (acc_cfk_update): ACC_E_STATE. An empty store and
  * n_keys == 0 give empty results; a failed call leaves the context usable. Stats: cfk.notify_keys, cfk.notify_candidates
  * (COMMITTED or STABLE entries of the asked keys), cfk.notify_releases, cfk.notify_sorted, cfk.notify_us.
- * Out of scope: Unmanaged pending records (notifyUnmanaged, registerUnmanaged); the progress-log side of
- * notifyWaitingOnCommit (min_uncommitted is given for the caller to do it); the range-command half of WaitingOn. */
+ * Out of scope: the progress-log side of notifyWaitingOnCommit (min_uncommitted is given for the caller to do it); the
+ * range-command half of WaitingOn. (Unmanaged pending records: acc_cfk_register_unmanaged / acc_cfk_notify_unmanaged
+ * below.) */
 #define ACC_NOTIFY_WAITING_TO_EXECUTE 0
 #define ACC_NOTIFY_RELEASE            1
 #define ACC_NOTIFY_NONE               0xFFFFFFFFu
@@ -1130,6 +1131,117 @@ typedef struct acc_cfk_notify_view {
     const uint32_t *rel_keys;                              /* [n_txn] */
 } acc_cfk_notify_view;
 int  acc_cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc_cfk_notify_view *out);
+
+/* ---- Unmanaged pending records of the resident CommandsForKey store ----
+ * Commands that wait on keys without being CommandsForKey members: range-domain txns (range reads, every sync point) and
+ * key-domain EphemeralRead / LocalOnly. When one becomes Stable, SafeCommandStore.updateCommandsForKey
+ * (local/SafeCommandStore.java:246-268) calls CommandsForKey.registerUnmanaged (local/CommandsForKey.java:1406-1498) on
+ * every key it waits on, and from then on notifyAndUpdatePending (:1206-1214) runs notifyUnmanaged (:1270-1316) after
+ * each update. The store keeps the records (Unmanaged, :140-184) in a pending table in DEVICE memory, freed by
+ * acc_cfk_destroy: per record the key code (records name their key by code and survive the key leaving the state),
+ * pending (ACC_UNM_COMMIT / ACC_UNM_APPLY), waiting_until, the waiter's TxnId and executeAt (raw bits) and, for a COMMIT
+ * record, the waiter's dep list for that key (an APPLY record is never re-evaluated and keeps none). Records stay in
+ * registration order (call order, then pair order); compaction is stable and a record that moves from COMMIT to APPLY
+ * keeps its slot: every threshold test is a per-record predicate, so nothing needs the Unmanaged.compareTo order.
+ * acc_cfk_unmanaged_view describes the table (DEVICE pointers, valid until the store's next acc_cfk_register_unmanaged
+ * or acc_cfk_notify_unmanaged). acc_cfk_redundant_before carries the table unchanged (the reference's "TODO filter
+ * pending unmanageds", :1682).
+ *
+ * acc_cfk_register_unmanaged: `in` is acc_cfk_updates without status / flags: per waiter TxnId, executeAt and keys
+ * (sorted unique), per (waiter, key) pair partialDeps().keyDeps.txnIds(key) (sorted unique). Every pair is evaluated
+ * against the store as it stands before the call (:1415-1498; outcomes do not depend on pair order: a dep another pair
+ * inserts as TRANSITIVELY_KNOWN counts as uncommitted absent or present). Deps below RB(key), the store's
+ * RedundantBefore map, are skipped (a dep equal to the bound stays); none left: ACC_UNM_READY. For each remaining dep:
+ * absent from the key's entries: not ready, not waitingToApply, and the dep is missing; present below COMMITTED: not
+ * ready, not waitingToApply; otherwise (INVALID_OR_TRUNCATED included), if the waiter's kind awaitsOnlyDeps
+ * (ExclusiveSyncPoint, EphemeralRead; primitives/Txn.java:211-214) or the entry's executeAt is below the waiter's:
+ * ready &= status >= APPLIED, executesAt = max(executesAt, entry.executeAt). Outcome: ready: ACC_UNM_READY (the shim's
+ * removeWaitingOn; no record, nothing inserted); else waitingToApply: ACC_UNM_PENDING_APPLY with waiting_until =
+ * executesAt; else ACC_UNM_PENDING_COMMIT with waiting_until = the pair's last dep. The distinct missing (key, TxnId) of
+ * all not-ready pairs are merged into the key-major state as TxnInfo.create(id, TRANSITIVELY_KNOWN) (executeAt = TxnId,
+ * empty missing[]; other entries' missing[] untouched, :1454-1471; a key without a CFK is created) and the txn-major
+ * view is rebuilt as acc_cfk_apply_deps rebuilds it; with nothing missing no store array is rewritten and every view
+ * stays valid. The view holds one status per TxnId: a missing dep that the store holds on another key with a status
+ * other than TRANSITIVELY_KNOWN fails the call with ACC_E_STATE. Then the new records are appended.
+ * `out` (DEVICE pointers, valid until the context's next compute call): per pair outcome and until (zeros for READY),
+ * and n_inserted. For an awaitsOnlyDeps waiter the caller raises WaitingOn.executeAtLeast to `until` of each
+ * PENDING_APPLY pair (:1476-1484).
+ * tier: pairs with at most UM_LANE_MAX (16) deps at or above the bound are evaluated by one lane, longer ones by one
+ * wave; a non-zero tier forces one for every pair. Results do not depend on it.
+ * Errors leave the store and the table unchanged. ACC_E_ARG: mem; offsets not starting at 0, decreasing, or not ending
+ * at the counts; keys of a waiter not sorted unique; deps of a pair not sorted unique; a kind ordinal above 5; a managed
+ * waiter (key domain and a globally visible kind); the same waiter TxnId twice in one call; an unknown tier.
+ * ACC_E_STATE: a non-empty status-only store (acc_cfk_update). ACC_E_CAP: the table's records or deps would reach
+ * 2^32 - 1. n_waiters == 0 is a no-op. Registering a (waiter, key) at most once across calls is the caller's contract,
+ * as in the reference.
+ *
+ * acc_cfk_notify_unmanaged: key_code sorted unique (NULL: every key that has a record). It first runs acc_cfk_notify on
+ * those keys for min_uncommitted and next (and inherits its errors), then per record of an asked key applies :1206-1212
+ * and :1270-1316 in closed form. COMMIT step: Tc = minUncommitted's TxnId (Timestamp.MAX when null); a COMMIT record with
+ * waiting_until < Tc is re-evaluated by updatePending (:1333-1388): deps below the current RB(key) are skipped, the walk
+ * stops at the key's last entry (deps beyond it are ignored), the test is awaitsOnlyDeps || executeAt <
+ * waiterExecuteAt with no COMMITTED check; a dep that is absent while a later entry exists is the reference's
+ * illegalState: ACC_E_STATE, table unchanged. The record is either released or becomes an APPLY record in its slot with
+ * waiting_until = executesAt, its deps dropped. The step runs unconditionally (when nothing newly committed no record
+ * qualifies: a COMMIT record's last dep is at or above an uncommitted entry). APPLY step, on the table after the COMMIT
+ * step, only if minUncommitted == null || next != null: Ta = next's executeAt (MAX when next is null); APPLY records
+ * with waiting_until < Ta are released. Both thresholds are exclusive.
+ * Output (DEVICE pointers, valid until the context's next compute call): one event per affected record in table order:
+ * ev_kind (ACC_UNM_EV_TO_APPLY / ACC_UNM_EV_RELEASE), ev_flags (bit 0: re-evaluated from COMMIT in this call), ev_key,
+ * ev_txn, ev_until (the record's APPLY waiting_until, zeros if it never had one); n_events, and n_rec after the stable
+ * compaction. RELEASE is removeWaitingOn(txnId, key); with bit 0 set, an awaitsOnlyDeps waiter and a non-zero ev_until
+ * the caller also calls updateExecuteAtLeast(ev_until) (:1372-1381). A call that moves nothing leaves the table and
+ * its view as they are.
+ * Stats: cfk.unmanaged_pairs, _ready, _pending_commit, _pending_apply, _tk_inserted, _records, _register_us
+ * (register); cfk.unmanaged_reevaluated, _released, _records, _notify_us (notify).
+ * Out of scope: the progress-log side of notifyWaitingOnCommit; updatePendingAsync's load scheduling (the device always
+ * has the command's deps in the record); registerHistorical; the range-command half of WaitingOn. */
+#define ACC_UNM_COMMIT          0
+#define ACC_UNM_APPLY           1
+#define ACC_UNM_READY           0
+#define ACC_UNM_PENDING_COMMIT  1
+#define ACC_UNM_PENDING_APPLY   2
+#define ACC_UNM_TIER_LANE       1
+#define ACC_UNM_TIER_WAVE       2
+#define ACC_UNM_EV_TO_APPLY     0
+#define ACC_UNM_EV_RELEASE      1
+typedef struct acc_cfk_unmanaged_in {
+    uint32_t mem, n_waiters;     /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t n_pairs, n_deps;
+    acc_ts_cols txn_id, execute_at;   /* [n_waiters] */
+    const uint32_t *key_off;     /* [n_waiters+1] */
+    const uint64_t *key;         /* [n_pairs] sorted unique per waiter */
+    const uint32_t *dep_off;     /* [n_pairs+1] */
+    acc_ts_cols deps;            /* [n_deps] sorted unique per pair */
+    uint32_t tier;               /* 0: library default; ACC_UNM_TIER_LANE / _WAVE force one kernel tier (tests) */
+} acc_cfk_unmanaged_in;
+typedef struct acc_cfk_unmanaged_out {
+    uint64_t n_pairs, n_inserted;
+    const uint8_t *outcome;      /* [n_pairs] ACC_UNM_READY / _PENDING_COMMIT / _PENDING_APPLY */
+    acc_ts_cols until;           /* [n_pairs] waiting_until; zeros for READY */
+} acc_cfk_unmanaged_out;
+typedef struct acc_cfk_unmanaged_table {   /* DEVICE pointers */
+    uint32_t n_rec;
+    uint64_t n_deps;
+    const uint64_t *key;         /* [n_rec] */
+    const uint8_t  *pending;     /* [n_rec] ACC_UNM_COMMIT / ACC_UNM_APPLY */
+    acc_ts_cols until, txn_id, execute_at;
+    const uint32_t *dep_off;     /* [n_rec+1] */
+    acc_ts_cols deps;            /* [n_deps] */
+} acc_cfk_unmanaged_table;
+typedef struct acc_cfk_unmanaged_notify_in {
+    uint32_t mem, n_keys;
+    const uint64_t *key_code;    /* sorted unique; NULL: every key that has a record */
+} acc_cfk_unmanaged_notify_in;
+typedef struct acc_cfk_unmanaged_events {
+    uint32_t n_events, n_rec;
+    const uint8_t *ev_kind, *ev_flags;   /* [n_events] */
+    const uint64_t *ev_key;
+    acc_ts_cols ev_txn, ev_until;
+} acc_cfk_unmanaged_events;
+int  acc_cfk_register_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_in *in, acc_cfk_unmanaged_out *out);
+int  acc_cfk_notify_unmanaged(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_unmanaged_notify_in *in, acc_cfk_unmanaged_events *out);
+int  acc_cfk_unmanaged_view(acc_ctx *ctx, acc_cfk *cfk, acc_cfk_unmanaged_table *out);
 
 /* ---- A device-resident range-command store and the RangeDeps of new txns ----
  * The other half of PreAccept.calculatePartialDeps beside acc_cfk_keydeps_mixed: the deps on the store's range commands
