@@ -58,6 +58,8 @@ EXPORTS = ["acc_create", "acc_destroy", "acc_last_error", "acc_sync", "acc_strea
            "acc_rcmd_create", "acc_rcmd_destroy", "acc_rcmd_update", "acc_rcmd_view", "acc_rcmd_rangedeps",
            "acc_rcmd_update_cmds", "acc_rcmd_state_view", "acc_rcmd_map_reduce_full", "acc_rcmd_redundant_before",
            "acc_rcmd_redundant_view", "acc_rcmd_partial_rangedeps",
+           "acc_waiting_create", "acc_waiting_destroy", "acc_waiting_register", "acc_waiting_notify", "acc_waiting_erase",
+           "acc_waiting_view",
            "acc_ranges_of", "acc_ranges_with", "acc_ranges_subtract", "acc_ranges_merge_touching", "acc_ranges_select",
            "acc_ranges_index_of", "acc_ranges_contains_all_keys", "acc_ranges_contains_all", "acc_rangedeps_is_covered_by",
            "acc_partial_deps_covering", "acc_rmm_without", "acc_recovery_deps_reduce"]
@@ -407,6 +409,47 @@ class RcmdState(C.Structure):
                 ("dep_start", C.c_void_p), ("dep_end", C.c_void_p), ("dep_is_key", C.c_void_p)]
 
 
+class WaitingRegisterIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_waiters", C.c_uint32), ("n_keys", C.c_uint64), ("n_deps", C.c_uint64),
+                ("txn_id", TsCols), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
+                ("key_wait", C.c_void_p), ("dep_off", C.c_void_p), ("dep", TsCols), ("dep_wait", C.c_void_p),
+                ("tier", C.c_uint32)]
+
+
+class WaitingRegisterOut(C.Structure):
+    _fields_ = [("n_waiters", C.c_uint32), ("reserved", C.c_uint32), ("waiting", C.c_void_p), ("execute_at_least", TsCols)]
+
+
+class WaitingNotifyIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_changed", C.c_uint32), ("changed", TsCols), ("n_rel", C.c_uint32),
+                ("tier", C.c_uint32), ("rel_txn", TsCols), ("rel_key", C.c_void_p), ("rel_flags", C.c_void_p),
+                ("rel_until", TsCols)]
+
+
+class WaitingNotifyOut(C.Structure):
+    _fields_ = [("n_ready", C.c_uint32), ("reserved", C.c_uint32), ("n_changed", C.c_uint64), ("ready_rec", C.c_void_p),
+                ("ready_txn", TsCols), ("ready_execute_at_least", TsCols)]
+
+
+class WaitingEraseIn(C.Structure):
+    _fields_ = [("mem", C.c_uint32), ("n_ids", C.c_uint32), ("txn_id", TsCols)]
+
+
+class WaitingTable(C.Structure):
+    _fields_ = [("n_rec", C.c_uint32), ("reserved", C.c_uint32), ("n_keys", C.c_uint64), ("n_deps", C.c_uint64),
+                ("txn_id", TsCols), ("execute_at", TsCols), ("execute_at_least", TsCols), ("flags", C.c_void_p),
+                ("key_off", C.c_void_p), ("key", C.c_void_p), ("key_wait", C.c_void_p), ("dep_off", C.c_void_p),
+                ("dep", TsCols), ("dep_state", C.c_void_p), ("n_wait_dep", C.c_void_p), ("n_wait_key", C.c_void_p),
+                ("next_waiting_on", C.c_void_p)]
+
+
+ACC_WT_NOT_WAITING, ACC_WT_WAITING, ACC_WT_APPLIED_OR_INVALIDATED = 0, 1, 2
+ACC_WT_AWAITS_ONLY_DEPS, ACC_WT_RANGE_DOMAIN = 1, 2
+ACC_WT_REL_KEY = 1
+ACC_WT_NONE = 0xFFFFFFFF
+ACC_WT_TIER_LANE, ACC_WT_TIER_WAVE = 1, 2
+
+
 class ConflictsIn(C.Structure):
     _fields_ = [("mem", C.c_uint32), ("n_upd", C.c_uint32), ("end_inclusive", C.c_uint32), ("n_keys", C.c_uint64),
                 ("n_ranges", C.c_uint64), ("execute_at", TsCols), ("key_off", C.c_void_p), ("key", C.c_void_p),
@@ -660,6 +703,20 @@ def load():
         L.acc_rcmd_redundant_view.restype = C.c_int
         L.acc_rcmd_partial_rangedeps.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(CfkMixedQueries), C.POINTER(RcmdPartialView)]
         L.acc_rcmd_partial_rangedeps.restype = C.c_int
+        L.acc_waiting_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.acc_waiting_create.restype = C.c_int
+        L.acc_waiting_destroy.argtypes = [C.c_void_p]
+        L.acc_waiting_destroy.restype = None
+        L.acc_waiting_register.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(WaitingRegisterIn),
+                                           C.POINTER(WaitingRegisterOut)]
+        L.acc_waiting_register.restype = C.c_int
+        L.acc_waiting_notify.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(WaitingNotifyIn),
+                                         C.POINTER(WaitingNotifyOut)]
+        L.acc_waiting_notify.restype = C.c_int
+        L.acc_waiting_erase.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(WaitingEraseIn)]
+        L.acc_waiting_erase.restype = C.c_int
+        L.acc_waiting_view.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(WaitingTable)]
+        L.acc_waiting_view.restype = C.c_int
     except AttributeError:
         if not os.environ.get("ACC_LIB_PATH"):   # an older tuning build (A/B runs) may lack them; the product may not
             raise

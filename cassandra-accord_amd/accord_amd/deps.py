@@ -1489,6 +1489,158 @@ class RangeCmdStore:
         return r
 
 
+_WT_REG_COLS = (("msb", np.uint64), ("lsb", np.uint64), ("node", np.int32), ("xmsb", np.uint64), ("xlsb", np.uint64),
+                ("xnode", np.int32), ("key_off", np.uint32), ("key", np.uint64), ("dep_off", np.uint32), ("dmsb", np.uint64),
+                ("dlsb", np.uint64), ("dnode", np.int32))
+_WT_REL_COLS = (("msb", np.uint64), ("lsb", np.uint64), ("node", np.int32), ("key", np.uint64), ("flags", np.uint8),
+                ("until_msb", np.uint64), ("until_lsb", np.uint64), ("until_node", np.int32))
+_WT_ONE = np.zeros(2, np.uint64)   # a non-NULL pointer for an empty column
+
+
+class WaitingStore:
+    """Command.WaitingOn of every registered Stable command, kept in HBM (acc_waiting_*; local/Command.java:1294-1610,
+    advanced as local/Commands.java:735-876 advances it) and read against the per-command state of a RangeCmdStore: which
+    commands can run now. include/accord_amd.h states evaluate(W, i)."""
+
+    def __init__(self, ctx: Context, rcmd: "RangeCmdStore"):
+        self.ctx = ctx
+        self.rcmd = rcmd
+        h = C.c_void_p()
+        ctx.check(ctx._lib.acc_waiting_create(ctx.handle, C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.ctx._lib.acc_waiting_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _cols(self, src: dict, cols, device: bool, keep: list):
+        """The named columns as pointers: host arrays, or device tensors (mem = ACC_MEM_DEVICE) when device."""
+        out = {}
+        for k, dt in cols:
+            if src.get(k) is None:
+                out[k] = None
+                continue
+            a = np.ascontiguousarray(np.asarray(src[k], dt))
+            if device:
+                import torch
+                t = torch.from_numpy(a if len(a) else np.zeros(2, dt)).to(torch.device("cuda", self.ctx.device))
+                keep.append(t)
+                out[k] = t.data_ptr()
+            else:
+                keep.append(a)
+                out[k] = a.ctypes.data if len(a) else _WT_ONE.ctypes.data
+        return out
+
+    def register(self, waiters: dict, tier: int = 0, device: bool = False) -> dict:
+        """initialiseWaitingOn for a batch (acc_waiting_register): waiters = dict(msb, lsb, node: the TxnIds; xmsb, xlsb,
+        xnode: their executeAts; key_off, key: keyDeps.keys() of each, sorted unique; dep_off, dmsb, dlsb, dnode:
+        rangeDeps.txnIds() of each, sorted unique; optional key_wait, dep_wait: the initial bits, default all ones).
+        Host arrays out, per waiter: waiting (the slots it still waits on; 0: ready at once) and eal_msb / eal_lsb /
+        eal_node (executeAtLeast, zeros: null). tier forces one kernel tier (L.ACC_WT_TIER_*); device passes the
+        inputs as device arrays. Results depend on neither."""
+        keep = []
+        n = len(waiters["msb"])
+        p = self._cols(waiters, _WT_REG_COLS + (("key_wait", np.uint8), ("dep_wait", np.uint8)), device, keep)
+        ri = L.WaitingRegisterIn(L.ACC_MEM_DEVICE if device else L.ACC_MEM_HOST, n, len(waiters["key"]), len(waiters["dmsb"]),
+                                 L.TsCols(p["msb"], p["lsb"], p["node"]), L.TsCols(p["xmsb"], p["xlsb"], p["xnode"]),
+                                 p["key_off"], p["key"], p["key_wait"], p["dep_off"], L.TsCols(p["dmsb"], p["dlsb"], p["dnode"]),
+                                 p["dep_wait"], int(tier))
+        o = L.WaitingRegisterOut()
+        self.ctx.check(self.ctx._lib.acc_waiting_register(self.ctx.handle, self._h, self.rcmd._h, C.byref(ri), C.byref(o)))
+        m = int(o.n_waiters)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, m, dt) if m else np.zeros(0, dt)  # noqa: E731
+        return dict(waiting=g(o.waiting, np.uint32), eal_msb=g(o.execute_at_least.msb, np.uint64),
+                    eal_lsb=g(o.execute_at_least.lsb, np.uint64), eal_node=g(o.execute_at_least.node, np.int32))
+
+    def notify(self, changed=None, releases=None, tier: int = 0, device: bool = False) -> dict:
+        """updateDependencyAndMaybeExecute for every waiting slot whose dep is in changed = dict(msb, lsb, node), sorted
+        unique (None: every waiting slot), then removeWaitingOnKeyAndMaybeExecute / updateExecuteAtLeast for the release
+        pairs = dict(msb, lsb, node: the waiter; key; flags: bit 0 L.ACC_WT_REL_KEY clears the key's bit; until_msb,
+        until_lsb, until_node: raises executeAtLeast of an awaits-only-deps waiter, zeros: none) (acc_waiting_notify).
+        Host arrays out: ready_rec (record indices into view()), ready_msb / _lsb / _node, ready_eal_msb / _lsb / _node:
+        the records that waited before the call and do not after it, in TxnId order; n_changed = the slots that stopped
+        waiting."""
+        keep = []
+        tsn = (("msb", np.uint64), ("lsb", np.uint64), ("node", np.int32))
+        c = self._cols(changed, tsn, device, keep) if changed is not None else dict(msb=None, lsb=None, node=None)
+        rel = releases if releases is not None else {k: np.zeros(0, dt) for k, dt in _WT_REL_COLS}
+        r = self._cols(rel, _WT_REL_COLS, device, keep)
+        ni = L.WaitingNotifyIn(L.ACC_MEM_DEVICE if device else L.ACC_MEM_HOST, 0 if changed is None else len(changed["msb"]),
+                               L.TsCols(c["msb"], c["lsb"], c["node"]), len(rel["msb"]), int(tier),
+                               L.TsCols(r["msb"], r["lsb"], r["node"]), r["key"], r["flags"],
+                               L.TsCols(r["until_msb"], r["until_lsb"], r["until_node"]))
+        o = L.WaitingNotifyOut()
+        self.ctx.check(self.ctx._lib.acc_waiting_notify(self.ctx.handle, self._h, self.rcmd._h, C.byref(ni), C.byref(o)))
+        m = int(o.n_ready)
+        g = lambda ptr, dt: device_array(self.ctx, ptr, m, dt) if m else np.zeros(0, dt)  # noqa: E731
+        return dict(ready_rec=g(o.ready_rec, np.uint32), ready_msb=g(o.ready_txn.msb, np.uint64),
+                    ready_lsb=g(o.ready_txn.lsb, np.uint64), ready_node=g(o.ready_txn.node, np.int32),
+                    ready_eal_msb=g(o.ready_execute_at_least.msb, np.uint64),
+                    ready_eal_lsb=g(o.ready_execute_at_least.lsb, np.uint64),
+                    ready_eal_node=g(o.ready_execute_at_least.node, np.int32), n_changed=int(o.n_changed))
+
+    def erase(self, ids: dict, device: bool = False):
+        """Drop the records of ids = dict(msb, lsb, node), sorted unique (acc_waiting_erase); absent ids are ignored, a
+        record that still waits may be erased."""
+        keep = []
+        p = self._cols(ids, (("msb", np.uint64), ("lsb", np.uint64), ("node", np.int32)), device, keep)
+        ei = L.WaitingEraseIn(L.ACC_MEM_DEVICE if device else L.ACC_MEM_HOST, len(ids["msb"]), L.TsCols(p["msb"], p["lsb"], p["node"]))
+        self.ctx.check(self.ctx._lib.acc_waiting_erase(self.ctx.handle, self._h, C.byref(ei)))
+
+    def view(self) -> dict:
+        """Host copy of the store (acc_waiting_view), records in TxnId order: msb, lsb, node; xmsb, xlsb, xnode; eal_msb,
+        eal_lsb, eal_node; flags (L.ACC_WT_AWAITS_ONLY_DEPS | L.ACC_WT_RANGE_DOMAIN); key_off, key, key_wait; dep_off,
+        dmsb, dlsb, dnode, dep_state (L.ACC_WT_NOT_WAITING / _WAITING / _APPLIED_OR_INVALIDATED); n_wait_dep, n_wait_key,
+        next_waiting_on (the highest waiting dep slot, L.ACC_WT_NONE: none)."""
+        t = L.WaitingTable()
+        self.ctx.check(self.ctx._lib.acc_waiting_view(self.ctx.handle, self._h, C.byref(t)))
+        n, nk, nd = int(t.n_rec), int(t.n_keys), int(t.n_deps)
+        g = lambda ptr, cnt, dt: device_array(self.ctx, ptr, cnt, dt) if cnt else np.zeros(0, dt)  # noqa: E731
+        return dict(msb=g(t.txn_id.msb, n, np.uint64), lsb=g(t.txn_id.lsb, n, np.uint64), node=g(t.txn_id.node, n, np.int32),
+                    xmsb=g(t.execute_at.msb, n, np.uint64), xlsb=g(t.execute_at.lsb, n, np.uint64),
+                    xnode=g(t.execute_at.node, n, np.int32), eal_msb=g(t.execute_at_least.msb, n, np.uint64),
+                    eal_lsb=g(t.execute_at_least.lsb, n, np.uint64), eal_node=g(t.execute_at_least.node, n, np.int32),
+                    flags=g(t.flags, n, np.uint8), key_off=g(t.key_off, n + 1, np.uint32), key=g(t.key, nk, np.uint64),
+                    key_wait=g(t.key_wait, nk, np.uint8), dep_off=g(t.dep_off, n + 1, np.uint32),
+                    dmsb=g(t.dep.msb, nd, np.uint64), dlsb=g(t.dep.lsb, nd, np.uint64), dnode=g(t.dep.node, nd, np.int32),
+                    dep_state=g(t.dep_state, nd, np.uint8), n_wait_dep=g(t.n_wait_dep, n, np.uint32),
+                    n_wait_key=g(t.n_wait_key, n, np.uint32), next_waiting_on=g(t.next_waiting_on, n, np.uint32))
+
+    def bitsets(self, view: dict | None = None) -> list:
+        """Per record the Java long[] words of (waitingOn, appliedOrInvalidated): txn i is bit i, key k is bit n_dep + k
+        (Command.java:1434-1435); appliedOrInvalidated is None for a key-domain record, else n_dep bits."""
+        return waiting_bitsets(self.view() if view is None else view)
+
+
+def _java_words(bits: np.ndarray) -> list:
+    """A 0/1 array as SimpleBitSet's long[]: (n + 63) / 64 words, bit i of the set in bit i & 63 of word i >> 6."""
+    n = len(bits)
+    out = [0] * ((n + 63) // 64)
+    for i in np.flatnonzero(bits):
+        out[int(i) >> 6] |= 1 << (int(i) & 63)
+    return [w - (1 << 64) if w >> 63 else w for w in out]   # Java longs are signed
+
+
+def waiting_bitsets(v: dict) -> list:
+    """WaitingStore.bitsets over a view() dict (or a model's dict of the same columns)."""
+    out = []
+    for r in range(len(v["msb"])):
+        d0, d1 = int(v["dep_off"][r]), int(v["dep_off"][r + 1])
+        k0, k1 = int(v["key_off"][r]), int(v["key_off"][r + 1])
+        ds = np.asarray(v["dep_state"][d0:d1])
+        waiting = np.concatenate([ds == L.ACC_WT_WAITING, np.asarray(v["key_wait"][k0:k1]) != 0])
+        applied = _java_words(ds == L.ACC_WT_APPLIED_OR_INVALIDATED) if int(v["flags"][r]) & L.ACC_WT_RANGE_DOMAIN else None
+        out.append((_java_words(waiting), applied))
+    return out
+
+
 def mixed_queries_from_preaccept(q: dict) -> dict:
     """The acc_preaccept_in-layout queries (msb, lsb, node, is_range, part_off, part_start, part_end; optional xmsb,
     xlsb, xnode) as the CfkStore.keydeps_mixed dict: the parts of an is_range == 0 query become its keys (part_start),
@@ -1538,6 +1690,7 @@ class ReplicaStore:
         self.cfk = CfkStore(ctx)
         self.mc = MaxConflictsMap(ctx, end_inclusive)
         self.rcmd = RangeCmdStore(ctx, end_inclusive)
+        self.waiting = WaitingStore(ctx, self.rcmd)
 
     def preaccept_batch(self, part: dict, queries: dict | None = None, scan: bool | str = True,
                         range_part: dict | None = None, redundant_deps: bool = False, notify: bool = False) -> dict:
@@ -1618,6 +1771,44 @@ class ReplicaStore:
         keys (None: every key that has one) that move to APPLY or are released."""
         return self.cfk.notify_unmanaged(keys)
 
+    def register_waiting(self, waiters: dict) -> dict:
+        """WaitingStore.register on this store's WaitingOn records, read against its range-command store: a command
+        that became Stable starts waiting on its keys and range deps."""
+        return self.waiting.register(waiters)
+
+    def notify_waiting(self, changed=None, releases=None) -> dict:
+        """WaitingStore.notify on this store's WaitingOn records: the commands that can run now."""
+        return self.waiting.notify(changed, releases)
+
+    def execution_step(self, keys=None, changed=None) -> dict:
+        """One execution round after a batch: CfkStore.notify and CfkStore.notify_unmanaged on keys (None: every key),
+        their releases turned into release pairs (a RELEASE event clears the waiter's bit for the key; an unmanaged event
+        re-evaluated in the call carries its ev_until for executeAtLeast), and WaitingStore.notify with them and the
+        changed range deps (dict(msb, lsb, node), sorted unique; None: every waiting slot is re-evaluated). Returns
+        WaitingStore.notify's dict plus notify, unmanaged (the two event dicts) and releases (the pairs)."""
+        nt = self.cfk.notify(keys)
+        st = self.cfk.state()
+        um = self.cfk.notify_unmanaged(keys)
+        sel = np.flatnonzero(nt["ev_kind"] == L.ACC_NOTIFY_RELEASE)
+        ent = nt["ev_entry"][sel]
+        row = np.searchsorted(nt["ev_off"].astype(np.int64), sel, side="right") - 1
+        rel_u = um["ev_kind"] == L.ACC_UNM_EV_RELEASE
+        re_u = (um["ev_flags"] & 1).astype(bool)
+        pick = rel_u | re_u
+        until = lambda k, dt: np.where(re_u, um[k], 0).astype(dt)[pick]  # noqa: E731
+        z = lambda dt: np.zeros(len(sel), dt)  # noqa: E731
+        releases = dict(msb=np.concatenate([st["emsb"][ent], um["ev_txn_msb"][pick]]),
+                        lsb=np.concatenate([st["elsb"][ent], um["ev_txn_lsb"][pick]]),
+                        node=np.concatenate([st["enode"][ent], um["ev_txn_node"][pick]]),
+                        key=np.concatenate([nt["key"][row], um["ev_key"][pick]]),
+                        flags=np.concatenate([np.ones(len(sel), np.uint8), rel_u[pick].astype(np.uint8)]),
+                        until_msb=np.concatenate([z(np.uint64), until("ev_until_msb", np.uint64)]),
+                        until_lsb=np.concatenate([z(np.uint64), until("ev_until_lsb", np.uint64)]),
+                        until_node=np.concatenate([z(np.int32), until("ev_until_node", np.int32)]))
+        out = self.waiting.notify(changed, releases)
+        out.update(notify=nt, unmanaged=um, releases=releases)
+        return out
+
     _RECOVERY_NAMES = dict(accepted_started_before_without="acceptedOrCommittedStartedBeforeWithoutWitnessing",
                            stable_started_before_with="stableStartedBeforeAndWitnessed",
                            has_accepted_started_after_without="hasAcceptedOrCommittedStartedAfterWithoutWitnessing",
@@ -1663,6 +1854,7 @@ class ReplicaStore:
         self.rcmd.redundant_before(ranges)
 
     def close(self):
+        self.waiting.close()
         self.cfk.close()
         self.mc.close()
         self.rcmd.close()

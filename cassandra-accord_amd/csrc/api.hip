@@ -59,6 +59,12 @@ void rcmd_map_reduce_full(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_recovery_
 void rcmd_redundant_before(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_redundant_in *in);
 void rcmd_redundant_view(acc_rcmd *store, acc_cfk_redundant_map *out);
 void rcmd_partial_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixed_queries *q, acc_rcmd_partial_view *out);
+acc_waiting *waiting_new(int device);
+void waiting_free(acc_waiting *w);
+void waiting_register(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_register_in *in, acc_waiting_register_out *out);
+void waiting_notify(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_notify_in *in, acc_waiting_notify_out *out);
+void waiting_erase(acc_ctx *ctx, acc_waiting *w, const acc_waiting_erase_in *in);
+void waiting_view(acc_ctx *ctx, acc_waiting *w, acc_waiting_table *out);
 }  // namespace acc
 
 namespace {
@@ -483,6 +489,52 @@ int acc_rcmd_partial_rangedeps(acc_ctx *ctx, acc_rcmd *store, const acc_cfk_mixe
     return acc_guard(ctx, [&] {
         ACC_HIP(hipSetDevice(ctx->device));
         acc::rcmd_partial_rangedeps(ctx, store, q, out);
+    });
+}
+
+int acc_waiting_create(acc_ctx *ctx, acc_waiting **out)
+{
+    if (!ctx || !out) return ACC_E_ARG;
+    *out = nullptr;
+    return acc_guard(ctx, [&] { *out = acc::waiting_new(ctx->device); });
+}
+
+void acc_waiting_destroy(acc_waiting *w) { acc::waiting_free(w); }
+
+int acc_waiting_register(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_register_in *in,
+                         acc_waiting_register_out *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::waiting_register(ctx, w, rcmd, in, out);
+    });
+}
+
+int acc_waiting_notify(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_notify_in *in, acc_waiting_notify_out *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::waiting_notify(ctx, w, rcmd, in, out);
+    });
+}
+
+int acc_waiting_erase(acc_ctx *ctx, acc_waiting *w, const acc_waiting_erase_in *in)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::waiting_erase(ctx, w, in);
+    });
+}
+
+int acc_waiting_view(acc_ctx *ctx, acc_waiting *w, acc_waiting_table *out)
+{
+    if (!ctx) return ACC_E_ARG;
+    return acc_guard(ctx, [&] {
+        ACC_HIP(hipSetDevice(ctx->device));
+        acc::waiting_view(ctx, w, out);
     });
 }
 

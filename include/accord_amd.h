@@ -1108,8 +1108,8 @@ int  acc_cfk_map_reduce_full(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_recovery_
  * n_keys == 0 give empty results; a failed call leaves the context usable. Stats: cfk.notify_keys, cfk.notify_candidates
  * (COMMITTED or STABLE entries of the asked keys), cfk.notify_releases, cfk.notify_sorted, cfk.notify_us.
  * Out of scope: the progress-log side of notifyWaitingOnCommit (min_uncommitted is given for the caller to do it); the
- * range-command half of WaitingOn. (Unmanaged pending records: acc_cfk_register_unmanaged / acc_cfk_notify_unmanaged
- * below.) */
+ * range-command half of WaitingOn and the WaitingOn key bits themselves (acc_waiting_* below takes these releases).
+ * (Unmanaged pending records: acc_cfk_register_unmanaged / acc_cfk_notify_unmanaged below.) */
 #define ACC_NOTIFY_WAITING_TO_EXECUTE 0
 #define ACC_NOTIFY_RELEASE            1
 #define ACC_NOTIFY_NONE               0xFFFFFFFFu
@@ -1195,7 +1195,8 @@ int  acc_cfk_notify(acc_ctx *ctx, acc_cfk *cfk, const acc_cfk_notify_in *in, acc
  * Stats: cfk.unmanaged_pairs, _ready, _pending_commit, _pending_apply, _tk_inserted, _records, _register_us
  * (register); cfk.unmanaged_reevaluated, _released, _records, _notify_us (notify).
  * Out of scope: the progress-log side of notifyWaitingOnCommit; updatePendingAsync's load scheduling (the device always
- * has the command's deps in the record); registerHistorical; the range-command half of WaitingOn. */
+ * has the command's deps in the record); registerHistorical; the range-command half of WaitingOn (acc_waiting_* below,
+ * whose release pairs also take the `until` values given here). */
 #define ACC_UNM_COMMIT          0
 #define ACC_UNM_APPLY           1
 #define ACC_UNM_READY           0
@@ -1555,6 +1556,151 @@ int  acc_maxconflicts_update(acc_ctx *ctx, acc_maxconflicts *map, const acc_conf
 int  acc_maxconflicts_get(acc_ctx *ctx, acc_maxconflicts *map, const acc_preaccept_in *queries, acc_preaccept_out *out);
 /* intervals currently held (ReducingRangeMap.size) */
 uint64_t acc_maxconflicts_size(const acc_maxconflicts *map);
+
+/* ---- Execution readiness from a resident WaitingOn store ----
+ * acc_waiting is Command.WaitingOn (local/Command.java:1294-1610) of every registered Stable command, kept in DEVICE
+ * memory and advanced as local/Commands.java advances it: initialiseWaitingOn (:735-753), updateWaitingOn (:755-830),
+ * updateDependencyAndMaybeExecute (:832-857) and removeWaitingOnKeyAndMaybeExecute (:859-876), read against the state
+ * an acc_rcmd store holds per command (acc_rcmd_state: status, executeAt). One call per batch returns the commands
+ * whose maybeExecute (:656-733) would now pass: it takes the rel pairs acc_cfk_notify / acc_cfk_notify_unmanaged report
+ * and the `until` values the unmanaged calls hand the caller for WaitingOn.executeAtLeast.
+ *
+ * The store: one record per registered command W in TxnId order (Timestamp.compareTo): txn_id and execute_at (raw
+ * bits); flags: ACC_WT_AWAITS_ONLY_DEPS when W's kind is ExclusiveSyncPoint or EphemeralRead (primitives/Txn.java:211-214),
+ * ACC_WT_RANGE_DOMAIN when the record has an appliedOrInvalidated set (Command.java:1435); execute_at_least (all-zero:
+ * null); key[] = keyDeps.keys() codes, sorted unique, with key_wait[] (u8, 0 / 1); dep[] = rangeDeps.txnIds(), sorted
+ * unique, with dep_state[] (u8): ACC_WT_NOT_WAITING, ACC_WT_WAITING, or ACC_WT_APPLIED_OR_INVALIDATED (not waiting and
+ * the bit is set in appliedOrInvalidated). The Java pair (waiting, appliedOrInvalidated) never holds (1, 1), so the
+ * three states are exact; in the Java bitsets txn i is bit i and key k is bit n_dep + k. Beside the records the store
+ * keeps an index from a dep TxnId to the slots that hold it (the dep slots in TxnId order), rebuilt whenever the record
+ * table is rebuilt (register, erase): acc_waiting_notify evaluates only the slots of the changed deps. (The state
+ * columns are copied once per notify, so that a failed call changes nothing, and the ready list is one pass over the
+ * records; neither reads a slot's dep.)
+ *
+ * evaluate(W, i) for a slot whose state is WAITING; D = W.dep[i], found in the acc_rcmd table by Timestamp.equals;
+ * status ordinals as in acc_range_cmds_in (NotDefined 0 .. PreCommitted 4 .. Applied 8, Truncated 9, Invalidated 10):
+ *   0. D is absent or its status is below 4: nothing (ifLoadedAndInitialised null or not hasBeen(PreCommitted), :763-765);
+ *   1. known = 4 <= status <= 9 and D.executeAt is not all-zero (the convention for Erased: an erased row whose
+ *      executeAt is unknown carries zeros). If W awaits only deps, known, and D.executeAt > W.txnId:
+ *      execute_at_least = max(D.executeAt, execute_at_least), the new value on a tie (:782-783);
+ *   2. status >= 9: setAppliedOrInvalidated(i): the state becomes 2 for a range-domain W, 0 otherwise
+ *      (Command.java:1552-1566);
+ *   3. else if D.executeAt > W.executeAt and W does not await only deps: removeWaitingOn, the state becomes 0 (:804-810);
+ *   4. else if status == 8: setAppliedAndPropagate (Command.java:1568-1584): slot i is set as in step 2; if D has a
+ *      record R in this store and R is range-domain, every dep E common to R.dep and W.dep with R.dep_state[E] == 2 is
+ *      set in W as in step 2 if it is WAITING there. R is read as it stood when the call began. An Applied D whose
+ *      record still waits (on a key or a dep) is the reference's broken invariant: ACC_E_STATE, nothing changes;
+ *   5. else W keeps waiting.
+ * A record's slots are evaluated in descending slot order and a slot cleared earlier in the walk is not visited
+ * (utils/SimpleBitSet.java:373-387). The order matters: with deps E < D, D Applied, R_D.dep_state[E] == 2 and E executing
+ * after W, the descending walk leaves E at 2 where an ascending one would leave 0.
+ * Deliberate divergence: the reference's ranged reverseForEach(from, to) indexes every word with fromIndex
+ * (SimpleBitSet.java:404-407), so with 64 or more txnIds it re-visits slots 0..63 and never visits the rest. These calls
+ * visit every waiting slot below n_dep once, descending: what the method's single-word path does.
+ *
+ * acc_waiting_register is initialiseWaitingOn for a batch: per waiter TxnId and executeAt, its keys with key_wait and
+ * its deps with dep_wait, the initial bits (NULL: all ones). The caller decides them: rangeDeps.forEach(
+ * executionParticipants) and the keys inside the store's ranges (:746-751) are topology decisions, and
+ * acc_rangedeps_stab answers the first. Each new record runs evaluate over its waiting slots; the new records enter the
+ * table by a stable merge. out, per waiter: waiting = the slots (deps and keys) it still waits on (0: ready at once) and
+ * execute_at_least. ACC_E_ARG, store unchanged: a bad mem; offsets not starting at 0, decreasing or not ending at the
+ * counts; keys or deps not sorted unique; a key-domain dep TxnId; a kind ordinal above 5; a wait byte above 1; the same
+ * waiter twice in one call or a waiter already registered; an unknown tier. ACC_E_STATE: a waiter that rcmd holds at
+ * status >= 8 (so every new record reads finished records only and the batch is order-free); the step-4 invariant.
+ * ACC_E_CAP at 2^32 - 1 records or slots. n_waiters == 0 is a no-op.
+ *
+ * acc_waiting_notify: changed = dep TxnIds, sorted unique (changed.msb == NULL: every waiting slot is re-evaluated);
+ * per record the waiting slots whose dep is in changed run evaluate, descending (updateDependencyAndMaybeExecute for
+ * each). Then the release pairs (rel_txn, rel_key, rel_flags, rel_until), in any order, duplicates allowed: bit 0 of
+ * rel_flags (ACC_WT_REL_KEY) clears the record's key_wait for that key (removeWaitingOnKeyAndMaybeExecute); a pair with
+ * no record, or with bit 0 set and a key not in the record or a bit already clear, is ignored and counted; a non-zero
+ * rel_until on an awaits-only-deps record raises execute_at_least when it is strictly above it (the guarded
+ * updateExecuteAtLeast of local/CommandsForKey.java:1372-1381, 1476-1484; the existing value stays on a tie). out: the records that were
+ * waiting before the call and are not after it, in TxnId order: ready_rec (record index before any erase), ready_txn,
+ * ready_execute_at_least; n_changed = the slots (deps and keys) that stopped waiting. Errors as for register where they
+ * apply (mem, tier, changed not sorted unique, a rel_flags byte above 1: ACC_E_ARG; step 4: ACC_E_STATE); a failed
+ * call leaves the store unchanged.
+ *
+ * acc_waiting_erase: TxnIds sorted unique; their records leave by a stable compaction and the index is rebuilt. Absent
+ * ids are counted and ignored; a record that still waits may be erased (truncation).
+ * acc_waiting_view: the columns above and per record n_wait_dep, n_wait_key and next_waiting_on = the highest WAITING
+ * dep slot or ACC_WT_NONE (WaitingOn.nextWaitingOn, :1359-1363).
+ * Inputs take mem HOST or DEVICE; outputs are DEVICE pointers, valid until the context's next compute call; the view
+ * until the store's next change. Records with at most WT_LANE_MAX (16) dep slots are walked by one lane, longer ones by
+ * one wave; a non-zero tier forces one. Results do not depend on it.
+ * Stats: wt.records, wt.slots (dep and key slots), wt.register_evaluated and wt.notify_slots (the slots that were
+ * WAITING when the call began among those it was asked to evaluate: every slot of a new record; the slots whose dep is
+ * in changed), wt.propagated, wt.ready, wt.key_released, wt.key_ignored, wt.erased, wt.register_us, wt.notify_us,
+ * wt.erase_us.
+ * Out of scope: removeRedundantDependencies / hasLocallyRedundantDependencies (:758-760); isFullyPreBootstrapOrStale;
+ * the TruncatedApply checkState (:793); listeners and the progress log. */
+#define ACC_WT_NOT_WAITING            0
+#define ACC_WT_WAITING                1
+#define ACC_WT_APPLIED_OR_INVALIDATED 2
+#define ACC_WT_AWAITS_ONLY_DEPS       1u
+#define ACC_WT_RANGE_DOMAIN           2u
+#define ACC_WT_REL_KEY                1u
+#define ACC_WT_NONE                   0xFFFFFFFFu
+#define ACC_WT_TIER_LANE              1
+#define ACC_WT_TIER_WAVE              2
+typedef struct acc_waiting acc_waiting;
+typedef struct acc_waiting_register_in {
+    uint32_t mem, n_waiters;     /* ACC_MEM_HOST or ACC_MEM_DEVICE for every pointer */
+    uint64_t n_keys, n_deps;
+    acc_ts_cols txn_id, execute_at;   /* [n_waiters] */
+    const uint32_t *key_off;     /* [n_waiters+1] */
+    const uint64_t *key;         /* [n_keys] sorted unique per waiter */
+    const uint8_t  *key_wait;    /* [n_keys] 0 / 1; NULL: all ones */
+    const uint32_t *dep_off;     /* [n_waiters+1] */
+    acc_ts_cols dep;             /* [n_deps] range-domain TxnIds, sorted unique per waiter */
+    const uint8_t  *dep_wait;    /* [n_deps] 0 / 1; NULL: all ones */
+    uint32_t tier;               /* 0: library default; ACC_WT_TIER_LANE / _WAVE force one kernel tier (tests) */
+} acc_waiting_register_in;
+typedef struct acc_waiting_register_out {
+    uint32_t n_waiters, reserved;
+    const uint32_t *waiting;     /* [n_waiters] slots still waited on; 0: ready */
+    acc_ts_cols execute_at_least;
+} acc_waiting_register_out;
+typedef struct acc_waiting_notify_in {
+    uint32_t mem, n_changed;
+    acc_ts_cols changed;         /* [n_changed] sorted unique; msb == NULL: every waiting slot */
+    uint32_t n_rel, tier;
+    acc_ts_cols rel_txn;         /* [n_rel] */
+    const uint64_t *rel_key;
+    const uint8_t  *rel_flags;   /* bit 0: ACC_WT_REL_KEY */
+    acc_ts_cols rel_until;       /* zeros: none */
+} acc_waiting_notify_in;
+typedef struct acc_waiting_notify_out {
+    uint32_t n_ready, reserved;
+    uint64_t n_changed;
+    const uint32_t *ready_rec;   /* [n_ready] */
+    acc_ts_cols ready_txn, ready_execute_at_least;
+} acc_waiting_notify_out;
+typedef struct acc_waiting_erase_in {
+    uint32_t mem, n_ids;
+    acc_ts_cols txn_id;          /* [n_ids] sorted unique */
+} acc_waiting_erase_in;
+typedef struct acc_waiting_table {   /* DEVICE pointers */
+    uint32_t n_rec, reserved;
+    uint64_t n_keys, n_deps;
+    acc_ts_cols txn_id, execute_at, execute_at_least;   /* [n_rec] */
+    const uint8_t  *flags;       /* [n_rec] ACC_WT_AWAITS_ONLY_DEPS | ACC_WT_RANGE_DOMAIN */
+    const uint32_t *key_off;     /* [n_rec+1] */
+    const uint64_t *key;         /* [n_keys] */
+    const uint8_t  *key_wait;    /* [n_keys] */
+    const uint32_t *dep_off;     /* [n_rec+1] */
+    acc_ts_cols dep;             /* [n_deps] */
+    const uint8_t  *dep_state;   /* [n_deps] ACC_WT_NOT_WAITING / _WAITING / _APPLIED_OR_INVALIDATED */
+    const uint32_t *n_wait_dep, *n_wait_key, *next_waiting_on;   /* [n_rec] */
+} acc_waiting_table;
+int  acc_waiting_create(acc_ctx *ctx, acc_waiting **out);
+void acc_waiting_destroy(acc_waiting *w);
+int  acc_waiting_register(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_register_in *in,
+                          acc_waiting_register_out *out);
+int  acc_waiting_notify(acc_ctx *ctx, acc_waiting *w, acc_rcmd *rcmd, const acc_waiting_notify_in *in,
+                        acc_waiting_notify_out *out);
+int  acc_waiting_erase(acc_ctx *ctx, acc_waiting *w, const acc_waiting_erase_in *in);
+int  acc_waiting_view(acc_ctx *ctx, acc_waiting *w, acc_waiting_table *out);
 
 /* ---- Levelisation of a dependency graph by executeAt ----
  * Graph over n txns: deps of txn t = dep[off[t] .. off[t+1]) (batch indices); exec_rank[t] = order
