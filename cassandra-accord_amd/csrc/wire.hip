@@ -15,8 +15,9 @@
 // ordered by hash, then String.compareTo through its first 16 bytes (ties beyond them are detected and rejected, never
 // mis-ordered). Numbers as Gson reads them (JsonReader.nextLong, else nextDouble): integer literals that fit a long are
 // LONG; other literals go through Double.parseDouble and are LONG when (long) d == d, else DOUBLE -- the decimal ->
-// double conversion is the exactly rounded fast path (<= 19 significant digits, mantissa <= 2^53, |exponent| <= 22
-// (+15)); literals outside it are rejected. DOUBLE egress is Double.toString: the shortest decimal that rounds back to
+// double conversion is exactly rounded (half even) for every literal of up to 19 significant digits: Clinger's fast
+// path where it applies (mantissa <= 2^53, |exponent| <= 22), else a bignum long division (decimal_to_double); literals
+// with more nonzero digits are rejected. DOUBLE egress is Double.toString: the shortest decimal that rounds back to
 // the value, closest on ties (JDK >= 19; JDK-4511638 changed a few outputs of older JDKs), with Java's layout rules.
 #include "dict.hpp"
 
@@ -297,7 +298,7 @@ struct Cur {
             const int64_t v = c2.integer();
             if (!c2.err) { d.kind = K_LONG; d.value = (uint64_t)v; return; }
         }
-        // PEEKED_NUMBER: Double.parseDouble (exactly rounded fast path only), then (long) d == d -> LONG
+        // PEEKED_NUMBER: Double.parseDouble (exactly rounded, <= 19 significant digits), then (long) d == d -> LONG
         while (m && m % 10 == 0) { m /= 10; ++e10; }
         double v;
         if (inexact) { err |= E_UNSUPPORTED; return; }   // > 19 significant digits
@@ -601,7 +602,7 @@ static void check_json(uint64_t e)
 {
     if (e & E_OFF) fail(ACC_E_ARG, "doc_off must start at 0, be non-decreasing and end at the byte count");
     if (e & E_UNSUPPORTED)
-        fail(ACC_E_ARG, "a datum outside the device path: non-ASCII STRING text, or a number needing Double.parseDouble's slow path");
+        fail(ACC_E_ARG, "a datum outside the device path: non-ASCII STRING text, or a number of more than 19 significant digits");
     if (e & E_FIELD) fail(ACC_E_STATE, "Unknown name in Deps JSON (AssertionError, Json.java:392)");
     if (e & E_KIND) fail(ACC_E_ARG, "unknown Datum.Kind name (Kind.valueOf)");
     if (e & E_NULL_TXN) fail(ACC_E_ARG, "null TxnId in a Deps entry");
@@ -740,8 +741,8 @@ struct Sink {
 struct Dict { const uint8_t *kind, *null; const uint64_t *value; uint64_t n; const uint32_t *len; const uint8_t *str; };
 
 // ---- Double.toString (JDK >= 19: the shortest decimal that rounds to the double, the closest one on ties, and when the
-// shortest has one digit the closest of the one- and two-digit ones), exact integer arithmetic (Burger & Dybvig's
-// free-format digit generation over a 1216-bit bignum)
+// shortest has one digit the closest of all one- and two-digit ones), exact integer arithmetic (Burger & Dybvig's
+// free-format digit generation over the 1408-bit Big)
 // digits of v = f * 2^e (f > 0) into dig[], returns their count; *k10 = decimal exponent of the first digit (v = 0.d1d2.. * 10^(k10+1))
 __device__ int shortest_digits(uint64_t f, int e, bool min_e, uint8_t (&dig)[20], int &k10)
 {
@@ -794,30 +795,38 @@ __device__ int shortest_digits(uint64_t f, int e, bool min_e, uint8_t (&dig)[20]
     // a digit 10 (carry) cannot occur: the generation stops inside the rounding interval
     k10 = k - 1;
     if (n == 1) {
-        // the closest two-digit decimal c/10 * 10^k10 in the interval, when closer than the one-digit one
-        Big t10 = r0;   // r0 / s = v / 10^k10 in [1, 10)
-        t10.mul(10);
+        // the closest decimal of one or two digits in the interval, when closer than the generated digit. r0 / s =
+        // v / 10^k10 lies in [1, 10), or below 1 when the digit is a 1 rounded up across the power of ten (9.88E-323
+        // -> "1"): the two-digit decimals then sit one decade lower (9.9E-323), so the scale is 100 instead of 10.
+        const uint32_t sc = r0.cmp(s) < 0 ? 100u : 10u;
+        Big tq = r0;   // tq / s = v / 10^k10 * sc in [10, 100)
+        tq.mul(sc);
         uint32_t c = 0;
-        Big rem = t10;
+        Big rem = tq;
         while (rem.cmp(s) >= 0) { rem.sub(s); ++c; }
         Big r2 = rem;
         r2.mul(2);
         const int cr = r2.cmp(s);
         const bool up = cr > 0 || (cr == 0 && (c & 1));
         if (up) ++c;
-        if (c < 100 && c % 10 != 0) {
-            // distances at the scale of t10: |c s - t10| against |10 d s - t10|, and the interval ends (10 m+ / 10 m-)
+        if (c < 100 && (sc == 100u || c % 10 != 0)) {
+            // distances at the scale of tq: |c s - tq| against |sc d s - tq|, and the interval ends (sc m+ / sc m-)
             Big cs = s, ds = s;
             cs.mul(c);
-            ds.mul(10u * dig[0]);
-            Big dc = cs.cmp(t10) >= 0 ? cs : t10, dd = ds.cmp(t10) >= 0 ? ds : t10;
-            if (cs.cmp(t10) >= 0) dc.sub(t10); else { Big x = t10; x.sub(cs); dc = x; }
-            if (ds.cmp(t10) >= 0) dd.sub(t10); else { Big x = t10; x.sub(ds); dd = x; }
-            Big lim = cs.cmp(t10) >= 0 ? mp0 : mm0;   // at the scale of r0 (x 10 below)
-            lim.mul(10);
+            ds.mul(sc * dig[0]);
+            Big dc = cs.cmp(tq) >= 0 ? cs : tq, dd = ds.cmp(tq) >= 0 ? ds : tq;
+            if (cs.cmp(tq) >= 0) dc.sub(tq); else { Big x = tq; x.sub(cs); dc = x; }
+            if (ds.cmp(tq) >= 0) dd.sub(tq); else { Big x = tq; x.sub(ds); dd = x; }
+            Big lim = cs.cmp(tq) >= 0 ? mp0 : mm0;   // at the scale of r0 (x sc below)
+            lim.mul(sc);
             const int cin = dc.cmp(lim);
             const bool inside = even ? cin <= 0 : cin < 0;
-            if (inside && dc.cmp(dd) < 0) { dig[0] = (uint8_t)(c / 10); dig[1] = (uint8_t)(c % 10); n = 2; }
+            if (inside && dc.cmp(dd) < 0) {
+                dig[0] = (uint8_t)(c / 10);
+                n = 1;
+                if (c % 10) { dig[1] = (uint8_t)(c % 10); n = 2; }
+                if (sc == 100u) --k10;
+            }
         }
     }
     return n;

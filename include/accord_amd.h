@@ -764,7 +764,7 @@ int acc_latest_deps_merge(acc_ctx *ctx, const acc_latest_in *in, acc_latest_view
  * Keys are datums (mael/Datum.java); their codes in `deps` are dense ranks of every datum of the batch in
  * Datum.compareTo order (hash first, COMPARE_BY_HASH), with the dictionary rank -> (Datum.Kind ordinal, null, value,
  * hash). Every Datum.Kind: LONG and DOUBLE as Gson reads a number (nextLong, else nextDouble; the decimal conversion
- * is Double.parseDouble's exactly rounded fast path, other literals give ACC_E_ARG), HASH, and STRING (ASCII text, JSON
+ * is Double.parseDouble, exactly rounded for up to 19 significant digits -- more give ACC_E_ARG), HASH, and STRING (ASCII text, JSON
  * escapes resolved; two different texts with one hash and equal first 16 characters give ACC_E_ARG). DOUBLE egress is
  * Double.toString (shortest round-trip digits, JDK >= 19), STRING egress Gson's HTML-safe escaping.
  * acc_deps_to_json: the inverse for any acc_rmm_view pair of this context whose key codes index such a dictionary

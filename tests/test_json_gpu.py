@@ -90,9 +90,9 @@ def test_json_strings_and_doubles(ctx, p_string, p_double):
 
 def test_json_number_forms(ctx):
     """Numbers as Datum.read takes them (JsonReader.nextLong, else nextDouble): integral literals in any form are LONG
-    ("1.0", "1e2", "-0"), Long overflow goes through the double ("9223372036854775808" -> DOUBLE 9.223372036854776E18,
-    Java's (long) d == d quirk at 2^63 keeps "9.223372036854775807E18" a LONG), others DOUBLE exactly rounded
-    (Double.parseDouble); escaped strings are unescaped."""
+    ("1.0", "1e2", "-0"), Long overflow goes through the double (Java's saturating (long) d == d reads 2^63, as
+    "9223372036854775808" or "9.223372036854775807E18", as LONG Long.MAX_VALUE), others DOUBLE exactly rounded
+    (Double.parseDouble); escaped strings are unescaped. The rule is json_cases.parse_number."""
     from accord_amd.deps import deps_from_json, deps_to_json
     lits = [b"1.0", b"1e2", b"-0", b"-0.0", b"9223372036854775807", b"9223372036854775808", b"9.223372036854775807E18",
             b"0.1", b"1.5", b"-2.5e-3", b"123456789012345678e-20", b"4.9E-324", b"2.2250738585072014E-308",
@@ -104,15 +104,7 @@ def test_json_number_forms(ctx):
         t = x.decode()
         if t.startswith('"'):
             return JC.gson_string(__import__("json").loads(t))
-        if all(c.isdigit() or c == "-" for c in t):
-            v = int(t)
-            if -(1 << 63) <= v < (1 << 63) and t != "-0":
-                return str(v)
-        d = float(t)
-        ll = max(-(1 << 63), min((1 << 63) - 1, int(d))) if abs(d) < float("inf") else 0
-        if float(ll) == d:
-            return str(ll)
-        return JC.java_double_to_string(d)
+        return JC.write_datum(JC.parse_number(t))   # the LONG / DOUBLE rule the number tests share
     for x, o in zip(lits, out):
         assert o == ('{"keyDeps":[[' + java(x) + ',[1,2,"n1"]]],"rangeDeps":[]}').encode(), (x, o)
 
