@@ -14,6 +14,7 @@
 //      + m; key lists merge (a command registers on keys it was not yet on);
 //   4. key offsets by one scan, then every column is written once into the other buffer set, and the sets swap.
 #include "dict.hpp"
+#include "search.hpp"
 #include "cfkquery.hpp"
 #include "cfkredundant.hpp"
 #include "cfkunmanaged.hpp"
@@ -139,11 +140,7 @@ __global__ __launch_bounds__(BLOCK) void k_cf_locate(Delta d, Store s, const uin
         atomicAdd(skipped, 1u);
         return;
     }
-    uint32_t lo = 0, hi = s.n;
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m;
-    }
+    const uint32_t lo = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, Ts{ xm, xl, xn });
     const bool found = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], xm, xl, xn) == 0;
     pos[k] = lo;
     isnew[k] = found ? 0u : 1u;
@@ -180,8 +177,7 @@ __global__ __launch_bounds__(BLOCK) void k_cf_counts(Delta d, Store s, const int
 {
     const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
     if (x < s.n) {
-        uint32_t lo = 0, hi = nnew;   // inserted TxnIds below stored txn x: insert positions <= x
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (newpos[m] <= x) lo = m + 1; else hi = m; }
+        const uint32_t lo = upper_bound(newpos, 0, nnew, x);   // inserted TxnIds below stored txn x: insert positions <= x
         const uint32_t dst = x + lo;
         const uint32_t a0 = s.key_off[x], na = s.key_off[x + 1] - a0;
         const int32_t u = upd_of_old[x];
@@ -207,8 +203,7 @@ __global__ __launch_bounds__(BLOCK) void k_cf_write(Delta d, Store s, const int3
 {
     const uint32_t x = blockIdx.x * BLOCK + threadIdx.x;
     if (x < s.n) {
-        uint32_t lo = 0, hi = nnew;
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (newpos[m] <= x) lo = m + 1; else hi = m; }
+        const uint32_t lo = upper_bound(newpos, 0, nnew, x);
         const uint32_t dst = x + lo;
         const uint32_t a0 = s.key_off[x], na = s.key_off[x + 1] - a0;
         const int32_t u = upd_of_old[x];

@@ -23,6 +23,7 @@
 // Errors: a status going back (IllegalStateException "stale status", ACC_E_STATE), an addition equal to an existing
 // TxnId or depsKnownBefore equal to a TxnId (the reference's checkState, ACC_E_STATE), malformed input (ACC_E_ARG).
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 namespace cd {
@@ -31,12 +32,6 @@ constexpr uint32_t NONE_K = 0xFFFFFFFFu;
 enum : uint32_t { TK = 0, PRE = 2, ACC = 3, COMMITTED = 4, APPLIED = 6, INVALID = 7 };
 enum : uint64_t { E_ARG_STATUS = 1, E_ARG_SORT = 2, E_ARG_OFF = 4, E_STALE = 8, E_STATE = 16, E_CAP = 32, E_MCAP = 64 };
 
-struct Ts {
-    uint64_t m, l;
-    int32_t n;
-};
-
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
 __device__ __forceinline__ uint32_t kind(const Ts &t) { return (uint32_t)(t.l >> 1) & 7u; }
 // owner.kind().witnesses(t.kind()) (ts.hpp)
 __device__ __forceinline__ bool witnesses(const Ts &owner, const Ts &t) { return (acc::witnesses(kind(owner)) >> kind(t)) & 1u; }
@@ -555,11 +550,7 @@ __global__ __launch_bounds__(BLOCK) void k_cd_check(Snap s, Upd u, uint32_t *__r
         if (b < a || b > s.n_ent || (i == 0 && a != 0) || (i + 1 == s.n_keys && b != s.n_ent)) e |= E_ARG_OFF;
     }
     if (i < s.n_ent) {   // a thread per entry (a hot key holds hundreds of thousands); its key by a search of the offsets
-        uint32_t lo = 0, hi = s.n_keys;   // last key whose entries start at or before i
-        while (hi - lo > 1) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (s.ent_off[mid] <= i) lo = mid; else hi = mid;
-        }
+        const uint32_t lo = seg_of(s.ent_off, s.n_keys, i);   // last key whose entries start at or before i
         if (s.st[i] > INVALID) e |= E_ARG_STATUS;
         if (i > s.ent_off[lo] && cmp(Ts{ s.em[i - 1], s.el[i - 1], s.en[i - 1] }, Ts{ s.em[i], s.el[i], s.en[i] }) >= 0) e |= E_ARG_SORT;
         const uint32_t m0 = s.miss_off[i], m1 = s.miss_off[i + 1];
@@ -934,11 +925,7 @@ __global__ __launch_bounds__(BLOCK) void k_cd_out3e(uint32_t ne, uint32_t nko, c
 {
     const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
     if (e >= ne) return;
-    uint32_t lo = 0, hi = nko;   // last kept key whose entries start at or before e
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (o.ent_off[mid] <= e) lo = mid; else hi = mid;
-    }
+    const uint32_t lo = seg_of(o.ent_off, nko, e);   // last kept key whose entries start at or before e
     const uint32_t k = kkey[lo];
     if (hot[k]) return;   // (k_ch_out3)
     Work w;
@@ -1039,12 +1026,7 @@ __global__ __launch_bounds__(BLOCK) void k_ch_items(uint64_t NI, uint32_t nh, co
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= NI) return;
-    uint32_t lo = 0, hi = nh;   // last h with ioff[h] <= i
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ioff[mid] <= i) lo = mid; else hi = mid;
-    }
-    const uint32_t h = lo, r = (uint32_t)(i - ioff[h]), k = hk[h], q0 = kstart[k];
+    const uint32_t h = seg_of(ioff, nh, (uint32_t)i), r = (uint32_t)(i - ioff[h]), k = hk[h], q0 = kstart[k];
     uint64_t m, l;
     int32_t n;
     if (r < nsnap[h]) {
@@ -1326,11 +1308,7 @@ struct NewList {   // per hot key, its uncommitted entries new in this batch
 };
 __device__ __forceinline__ uint32_t ur_lower(const UR *__restrict__ l, uint32_t lo, uint32_t hi, const Ts &t)
 {
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (cmp(Ts{ l[mid].m, l[mid].l, l[mid].n }, t) < 0) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return partition_point(lo, hi, [&](uint32_t i) { return cmp(Ts{ l[i].m, l[i].l, l[i].n }, t) < 0; });
 }
 __device__ __forceinline__ uint32_t ch_missing(uint32_t e, const uint32_t *__restrict__ eg, const HG *__restrict__ G,
                                                const uint32_t *__restrict__ eoff, const UR *__restrict__ ulist,
@@ -1462,11 +1440,7 @@ __global__ __launch_bounds__(BLOCK) void k_ch_miss(uint32_t ne, const uint32_t *
                 const Ts tid{ t.m, t.l, t.n };
                 keep = cmp(tid, x) != 0 && ((w >> kind(tid)) & 1u);
                 if (keep) {   // not among the deps (sorted)
-                    uint32_t lo = d0, hi = d1;
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (cmp(Ts{ u.dm[mid], u.dl[mid], u.dn[mid] }, tid) < 0) lo = mid + 1; else hi = mid;
-                    }
+                    const uint32_t lo = lower_bound_ts(u.dm, u.dl, u.dn, d0, d1, tid);
                     if (lo < d1 && cmp(Ts{ u.dm[lo], u.dl[lo], u.dn[lo] }, tid) == 0) keep = false;
                 }
             }
@@ -1534,12 +1508,7 @@ __global__ __launch_bounds__(BLOCK) void k_ch_out4(uint64_t nm, uint32_t ne, con
 {
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= nm) return;
-    uint32_t lo = 0, hi = ne;   // last e with moff[e] <= q
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (moff[mid] <= q) lo = mid; else hi = mid;
-    }
-    const uint32_t e = lo, h = G[eg[e]].h;
+    const uint32_t e = seg_of(moff, ne, (uint32_t)q), h = G[eg[e]].h;
     const uint32_t pos = o.ent_off[kpos[hk[h]]] + (e - eoff[h]);
     const uint32_t dst = o.miss_off[pos] + (uint32_t)(q - moff[e]);
     o.mm[dst] = mm[q]; o.ml[dst] = ml[q]; o.mn[dst] = mn[q];
@@ -1775,12 +1744,7 @@ __global__ __launch_bounds__(BLOCK) void k_cb_owner(uint64_t NE, uint32_t nk, co
 {
     const uint64_t e = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (e >= NE) return;
-    uint32_t lo = 0, hi = nk;   // first k with ent_off[k + 1] > e
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ent_off[mid + 1] > e) hi = mid; else lo = mid + 1;
-    }
-    owner[e] = lo;
+    owner[e] = partition_point(0u, nk, [&](uint32_t k) { return ent_off[k + 1] <= e; });   // first k with ent_off[k + 1] > e
 }
 // per entry, in entry order (its columns read contiguously): its key code and missing count at its sorted position,
 // and the check that it carries its TxnId's executeAt and InternalStatus (a TxnId twice on one key is already refused

@@ -28,7 +28,7 @@
 // Work per key is O(n log n) in its entries; nothing is candidates x segment length.
 #include "cfkquery.hpp"
 #include "prims.hpp"
-#include "ts.hpp"
+#include "search.hpp"
 
 #include <chrono>
 
@@ -63,18 +63,8 @@ struct Asked {
     const uint32_t *PU, *PUc[3], *PNc[3], *PB;
 };
 
-struct Ts3 { uint64_t m, l; int32_t n; };
-__device__ __forceinline__ Ts3 id_of(const CfkResident &s, uint32_t se) { return Ts3{ s.em[se], s.el[se], s.en[se] }; }
-__device__ __forceinline__ Ts3 x_of(const CfkResident &s, uint32_t se) { return Ts3{ s.xm[se], s.xl[se], s.xn[se] }; }
-__device__ __forceinline__ int cmp(const Ts3 &a, const Ts3 &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
-
-// last index i of off[0, n) with off[i] <= v (the one non-empty segment that holds element v)
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *off, uint32_t n, uint32_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (off[m] <= v) lo = m; else hi = m; }
-    return lo;
-}
+__device__ __forceinline__ Ts id_of(const CfkResident &s, uint32_t se) { return Ts{ s.em[se], s.el[se], s.en[se] }; }
+__device__ __forceinline__ Ts x_of(const CfkResident &s, uint32_t se) { return Ts{ s.xm[se], s.xl[se], s.xn[se] }; }
 
 __global__ __launch_bounds__(BLOCK) void k_nt_keys(uint32_t nk, const uint64_t *__restrict__ key, CfkResident s,
                                                    uint32_t *__restrict__ kidx, uint32_t *__restrict__ cnt, uint64_t *__restrict__ errs)
@@ -85,9 +75,7 @@ __global__ __launch_bounds__(BLOCK) void k_nt_keys(uint32_t nk, const uint64_t *
     if (key) {
         const uint64_t c = key[i];
         if (i > 0 && key[i - 1] >= c) atomicOr((unsigned long long *)errs, (unsigned long long)E_KEYS);
-        uint32_t lo = 0, hi = s.nk;
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < c) lo = m + 1; else hi = m; }
-        k = lo < s.nk && s.key[lo] == c ? lo : NONE;
+        k = find_sorted(s.key, s.nk, c);
     }
     kidx[i] = k;
     cnt[i] = k == NONE ? 0u : s.ent_off[k + 1] - s.ent_off[k];
@@ -237,9 +225,7 @@ __global__ __launch_bounds__(BLOCK) void k_nt_bflags(uint32_t nb, Asked A, CfkRe
 template <class F>
 __device__ __forceinline__ uint32_t first_counted(uint32_t lo, uint32_t hi, F count_through)
 {
-    uint32_t a = lo, b = hi;
-    while (a < b) { const uint32_t m = (a + b) >> 1; if (count_through(m) == 0) a = m + 1; else b = m; }
-    return a;
+    return partition_point(lo, hi, [&](uint32_t m) { return count_through(m) == 0; });
 }
 
 __global__ __launch_bounds__(BLOCK) void k_nt_keymin(Asked A, uint32_t *__restrict__ kmin)
@@ -269,30 +255,25 @@ __global__ __launch_bounds__(BLOCK) void k_nt_eval(Asked A, CfkResident s, Eval 
         uint32_t flag = 0, kind = ACC_NOTIFY_WAITING_TO_EXECUTE, pos = 0;
         if (cand) {
             const uint32_t i = A.akey[a], s0 = A.aoff[i], s1 = A.aoff[i + 1], b0 = A.PB[s0], b1 = A.PB[s1];
-            const Ts3 id = id_of(s, se), x = x_of(s, se);
+            const Ts id = id_of(s, se), x = x_of(s, se);
             const bool bumped = cmp(x, id) != 0;
             uint32_t p, q, lbx;   // its place in the unbumped run, in the sorted bumped run; the lower bound of executeAt
             if (bumped) {
                 q = v.binv[a];
-                uint32_t lo = s0, hi = s1;
-                while (lo < hi) {   // unbumped e (executeAt = TxnId) precedes it: (e, e) < (x, id)
-                    const uint32_t m = (lo + hi) >> 1;
-                    const Ts3 e = id_of(s, A.src[m]);
+                p = partition_point(s0, s1, [&](uint32_t m) {   // unbumped e (executeAt = TxnId) precedes it: (e, e) < (x, id)
+                    const Ts e = id_of(s, A.src[m]);
                     const int c = cmp(e, x);
-                    if (c < 0 || (c == 0 && cmp(e, id) < 0)) lo = m + 1; else hi = m;
-                }
-                p = lo;
+                    return c < 0 || (c == 0 && cmp(e, id) < 0);
+                });
                 lbx = p > s0 && cmp(id_of(s, A.src[p - 1]), x) == 0 ? p - 1 : p;
             } else {
                 p = a;
                 lbx = a;
-                uint32_t lo = b0, hi = b1;
-                while (lo < hi) {   // bumped b precedes it: (b.x, b) < (id, id)
-                    const uint32_t m = (lo + hi) >> 1, b = v.bperm[m];
+                q = partition_point(b0, b1, [&](uint32_t m) {   // bumped b precedes it: (b.x, b) < (id, id)
+                    const uint32_t b = v.bperm[m];
                     const int c = cmp(x_of(s, A.src[b]), id);
-                    if (c < 0 || (c == 0 && b < a)) lo = m + 1; else hi = m;
-                }
-                q = lo;
+                    return c < 0 || (c == 0 && b < a);
+                });
             }
             pos = (A.PU[p] - A.PU[s0]) + (q - b0);
             flag = 1;
@@ -307,13 +288,8 @@ __global__ __launch_bounds__(BLOCK) void k_nt_eval(Asked A, CfkResident s, Eval 
                 uint32_t mc = m1 - m0;
                 const uint32_t km = v.kmin[i];
                 if (mc > 0 && km != NONE) {
-                    const Ts3 mu = id_of(s, A.src[km]);
-                    uint32_t lo = m0, hi = m1;
-                    while (lo < hi) {
-                        const uint32_t m = (lo + hi) >> 1;
-                        if (ts_cmp(s.mm[m], s.ml[m], s.mn[m], mu.m, mu.l, mu.n) < 0) lo = m + 1; else hi = m;
-                    }
-                    mc -= lo - m0;
+                    const Ts mu = id_of(s, A.src[km]);
+                    mc -= lower_bound_ts(s.mm, s.ml, s.mn, m0, m1, mu) - m0;
                 }
                 rel = expect == mc;
                 flag = rel;
@@ -334,13 +310,7 @@ __global__ __launch_bounds__(BLOCK) void k_nt_eval(Asked A, CfkResident s, Eval 
 // entry e as its index in the store's txn-major view (k_cq_emit's lower bound)
 __device__ __forceinline__ uint32_t view_index(const CfkResident &s, uint32_t e)
 {
-    const Ts3 id = id_of(s, e);
-    uint32_t lo = 0, hi = s.n_txn;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], id.m, id.l, id.n) < 0) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n_txn, id_of(s, e));
 }
 
 struct Events { uint32_t *entry, *txn, *pos; uint8_t *kind; uint32_t *rel_keys; };
@@ -386,7 +356,7 @@ __global__ __launch_bounds__(BLOCK) void k_nt_keyout(Asked A, CfkResident s, Eva
     const uint32_t km = v.kmin[i];
     uint32_t nx = least_live(A, s, v, s0, s1, b0, b1, 7u), nw = least_live(A, s, v, s0, s1, b0, b1, 2u);
     if (km != NONE) {   // minUncommitted.compareTo(next.executeAt) < 0 (:451-458)
-        const Ts3 mu = id_of(s, A.src[km]);
+        const Ts mu = id_of(s, A.src[km]);
         if (nx != NONE && cmp(mu, x_of(s, A.src[nx])) < 0) nx = NONE;
         if (nw != NONE && cmp(mu, x_of(s, A.src[nw])) < 0) nw = NONE;
     }

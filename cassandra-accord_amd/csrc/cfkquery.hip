@@ -128,15 +128,6 @@ __device__ __forceinline__ Best wave_best(Best b)
     return b;
 }
 
-// first index in [0, n) with a[idx] > v
-template <class T>
-__device__ __forceinline__ uint32_t upper(const T *a, uint32_t n, T v)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_cq_validate(Queries Q, uint64_t *__restrict__ errs)
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
@@ -159,11 +150,7 @@ __global__ __launch_bounds__(BLOCK) void k_cq_validate(Queries Q, uint64_t *__re
 __device__ __forceinline__ uint32_t prefix_of(const CfkResident &s, uint32_t s0, uint32_t s1, uint64_t Sm, uint64_t Sl, int32_t Sn,
                                               uint32_t &t0)
 {
-    uint32_t x = s0, y = s1;
-    while (x < y) {
-        const uint32_t m = (x + y) >> 1;
-        if (ts_cmp(s.em[m], s.el[m], s.en[m], Sm, Sl, Sn) < 0) x = m + 1; else y = m;
-    }
+    const uint32_t x = lower_bound_ts(s.em, s.el, s.en, s0, s1, Ts{ Sm, Sl, Sn });
     // entries past it have TxnId > S, and executeAt >= TxnId
     t0 = x < s1 && committed(s.st[x]) && ts_cmp(s.xm[x], s.xl[x], s.xn[x], Sm, Sl, Sn) == 0 ? 1u : 0u;
     return x - s0;
@@ -177,12 +164,11 @@ __global__ __launch_bounds__(BLOCK) void k_cq_locate(Queries Q, CfkResident s, u
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= Q.Qp) return;
-    const uint32_t q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
+    const uint32_t q = upper_bound(Q.off, 0, Q.nq + 1, i) - 1;
     uint32_t a = 0, w = 0, t0 = 0;
     const uint64_t k = Q.key[i];
-    uint32_t lo = 0, hi = s.nk;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
-    if (lo < s.nk && s.key[lo] == k) {
+    const uint32_t lo = find_sorted(s.key, s.nk, k);
+    if (lo != NOT_FOUND) {
         a = s.ent_off[lo];
         w = prefix_of(s, a, s.ent_off[lo + 1], Q.xm[q], Q.xl[q], Q.xn[q], t0);
     }
@@ -362,12 +348,7 @@ __device__ __forceinline__ uint32_t view_index(const CfkResident &s, uint32_t e)
 {
     const uint64_t xm = s.em[e], xl = s.el[e];
     const int32_t xn = s.en[e];
-    uint32_t lo = 0, hi = s.n_txn;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
-    }
-    return lo;
+    return lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n_txn, Ts{ xm, xl, xn });
 }
 
 // the count pass's walk, compacting in position order: every emitted entry as its index in the store's txn-major view
@@ -457,9 +438,7 @@ __global__ __launch_bounds__(BLOCK) void k_cq_build_wave(uint64_t first, uint32_
     const uint64_t body = arena_off[q] + (kd_off[q + 1] - kd_off[q]);
     for (uint32_t i = lane; i < H; i += 64) {
         const uint64_t v = hit[h0 + i];
-        uint32_t lo = 0, hi = U;
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (buf[m] < v) lo = m + 1; else hi = m; }
-        arena[body + i] = (int32_t)lo;
+        arena[body + i] = (int32_t)lower_bound(buf, 0, U, v);
         uflag[h0 + i] = i < U ? 1u : 0u;
         uval[h0 + i] = i < U ? (uint32_t)buf[i] : 0u;
     }
@@ -492,8 +471,7 @@ __global__ __launch_bounds__(BLOCK) void k_cq_gbody(uint64_t G, const uint64_t *
     const uint64_t k = gkey[g];
     const uint32_t q = (uint32_t)(k >> tb);
     const uint64_t g0 = goff[q];
-    uint64_t lo = g0, hi = g0 + gcnt[q];
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (sk[m] < k) lo = m + 1; else hi = m; }
+    const uint64_t lo = lower_bound(sk, g0, g0 + gcnt[q], k);
     arena[arena_off[q] + (kd_off[q + 1] - kd_off[q]) + (g - g0)] = (int32_t)(ginc[lo] - ginc[g0]);
 }
 
@@ -553,11 +531,11 @@ __global__ __launch_bounds__(BLOCK) void k_cq_rbounds(Ranges R, CfkResident s, u
     const uint64_t a = R.start[r], b = R.end[r];
     uint32_t lo, hi;
     if (R.end_inclusive) {
-        lo = upper<uint64_t>(s.key, s.nk, a);
-        hi = upper<uint64_t>(s.key, s.nk, b);
+        lo = upper_bound(s.key, 0, s.nk, a);
+        hi = upper_bound(s.key, 0, s.nk, b);
     } else {
-        lo = a ? upper<uint64_t>(s.key, s.nk, a - 1) : 0u;
-        hi = upper<uint64_t>(s.key, s.nk, b - 1);                      // start < end: b >= 1
+        lo = a ? upper_bound(s.key, 0, s.nk, a - 1) : 0u;
+        hi = upper_bound(s.key, 0, s.nk, b - 1);                      // start < end: b >= 1
     }
     rlo[r] = lo;
     rcnt[r] = hi - lo;
@@ -584,21 +562,20 @@ __global__ __launch_bounds__(BLOCK) void k_cq_roff(uint32_t n, const uint64_t *_
 __device__ __forceinline__ uint32_t pair_segment(const Queries &Q, const Ranges &R, const CfkResident &s, uint32_t i, uint32_t &q,
                                                  uint64_t &k, bool &range)
 {
-    q = upper<uint32_t>(Q.off, Q.nq + 1, i) - 1;
+    q = upper_bound(Q.off, 0, Q.nq + 1, i) - 1;
     const uint32_t j = i - Q.off[q];
     uint32_t seg = s.nk;
     range = Q.ql[q] & 1u;
     if (range) {
         const uint32_t r0 = R.rng_off[q], r1 = R.rng_off[q + 1];
         const uint64_t at = R.cum[r0] + j;
-        const uint32_t r = r0 + upper<uint64_t>(R.cum + r0, r1 - r0, at) - 1;     // the last range starting at or below at
+        const uint32_t r = upper_bound(R.cum, r0, r1, at) - 1;     // the last range starting at or below at
         seg = R.lo[r] + (uint32_t)(at - R.cum[r]);
         k = s.key[seg];
     } else {
         k = R.key_code[R.key_off[q] + j];
-        uint32_t lo = 0, hi = s.nk;
-        while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (s.key[m] < k) lo = m + 1; else hi = m; }
-        if (lo < s.nk && s.key[lo] == k) seg = lo;
+        const uint32_t lo = find_sorted(s.key, s.nk, k);
+        if (lo != NOT_FOUND) seg = lo;
     }
     return seg;
 }
@@ -1120,11 +1097,7 @@ __global__ __launch_bounds__(BLOCK) void k_cr_window(Queries Q, Ranges R, CfkRes
         const uint64_t Xm = Q.qm[q], Xl = Q.ql[q];
         const int32_t Xn = Q.qn[q];
         // Arrays.binarySearch(txns, testTxnId): found <=> X is a member; pos = its index or the insert point
-        uint32_t x = s0, y = s1;
-        while (x < y) {
-            const uint32_t m = (x + y) >> 1;
-            if (ts_cmp(s.em[m], s.el[m], s.en[m], Xm, Xl, Xn) < 0) x = m + 1; else y = m;
-        }
+        const uint32_t x = lower_bound_ts(s.em, s.el, s.en, s0, s1, Ts{ Xm, Xl, Xn });
         const bool known = x < s1 && ts_cmp(s.em[x], s.el[x], s.en[x], Xm, Xl, Xn) == 0;
         if (known || p.test_dep != ACC_DEP_WITH) {
             const uint32_t start = p.started_at == ACC_STARTED_AFTER ? x : s0;

@@ -30,7 +30,6 @@ namespace acc {
 namespace rb {
 
 using mc::Map;
-using mc::Ts;
 
 enum : uint64_t { E_RANGE = 1, E_DEPS = 2 };
 
@@ -79,13 +78,9 @@ __global__ __launch_bounds__(BLOCK) void k_rb_key(Map mp, CfkResident s, Keys o,
         const Ts nb = mc::point(mp, s.key[k]), ob{ o.bm[k], o.bl[k], o.bn[k] };
         const uint32_t e0 = s.ent_off[k], e1 = s.ent_off[k + 1];
         uint32_t lo = e0;
-        adv = mc::cmp(nb, ob) > 0;
+        adv = cmp(nb, ob) > 0;
         if (adv) {   // insertPos(0, shardRedundantBefore): the first entry with TxnId >= the bound
-            uint32_t hi = e1;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (ts_cmp(s.em[m], s.el[m], s.en[m], nb.m, nb.l, nb.n) < 0) lo = m + 1; else hi = m;
-            }
+            lo = lower_bound_ts(s.em, s.el, s.en, e0, e1, nb);
         }
         o.cnt[k] = e1 - lo;
         o.flag[k] = e1 != lo;
@@ -95,15 +90,6 @@ __global__ __launch_bounds__(BLOCK) void k_rb_key(Map mp, CfkResident s, Keys o,
     }
     const unsigned long long b = __ballot(adv);
     if (b && lane_id() == 0) atomicAdd(advanced, (unsigned long long)__popcll(b));
-}
-
-// last index i of off[0, n) with off[i] <= v (off non-decreasing from 0; among equal offsets the last: the one segment
-// that holds element v, the empty ones before it share its offset)
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *off, uint32_t n, uint32_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (off[m] <= v) lo = m; else hi = m; }
-    return lo;
 }
 
 // a thread per entry slot of the old state: slot e2 below the new entry count is new entry e2 (its source entry, the
@@ -119,13 +105,7 @@ __global__ __launch_bounds__(BLOCK) void k_rb_entry(uint64_t ne_old, CfkResident
     uint32_t m0 = s.miss_off[e];
     const uint32_t m1 = s.miss_off[e + 1];
     if (k.trim[kk] && m1 > m0) {   // Arrays.binarySearch(missing, bound): the insert point, or the equal id, which stays
-        const uint64_t bm = k.bm[kk], bl = k.bl[kk];
-        const int32_t bn = k.bn[kk];
-        uint32_t hi = m1;
-        while (m0 < hi) {
-            const uint32_t m = (m0 + hi) >> 1;
-            if (ts_cmp(s.mm[m], s.ml[m], s.mn[m], bm, bl, bn) < 0) m0 = m + 1; else hi = m;
-        }
+        m0 = lower_bound_ts(s.mm, s.ml, s.mn, m0, m1, ts_at(k.bm, k.bl, k.bn, kk));
     }
     msrc[e2] = m0;
     mcnt[e2] = m1 - m0;
@@ -267,11 +247,7 @@ __global__ __launch_bounds__(BLOCK) void k_rb_dep_cut(Map mp, uint64_t NP, uint6
         return;
     }
     const Ts rb = mc::point(mp, key[j]);
-    uint32_t hi = b;
-    while (a < hi) {   // deps.find(shardRedundantBefore): the first dep >= the bound
-        const uint32_t m = (a + hi) >> 1;
-        if (ts_cmp(dm[m], dl[m], dn[m], rb.m, rb.l, rb.n) < 0) a = m + 1; else hi = m;
-    }
+    a = lower_bound_ts(dm, dl, dn, a, b, rb);   // deps.find(shardRedundantBefore): the first dep >= the bound
     cut[j] = a;
     cnt[j] = b - a;
 }

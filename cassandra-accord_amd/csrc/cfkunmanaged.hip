@@ -29,7 +29,7 @@
 #include "cfkunmanaged.hpp"
 #include "cfkredundant.hpp"
 #include "prims.hpp"
-#include "ts.hpp"
+#include "search.hpp"
 
 namespace acc {
 namespace um {
@@ -38,7 +38,6 @@ constexpr uint32_t UM_LANE_MAX = 16;   // trimmed deps of a pair the lane tier w
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
 using mc::Map;
-using mc::Ts;
 
 enum : uint64_t { E_OFF = 1, E_KEYS = 2, E_DEPOFF = 4, E_DEPS = 8, E_KIND = 16, E_MANAGED = 32, E_ILLEGAL = 64 };
 enum : uint32_t { T_LANE = ACC_UNM_TIER_LANE, T_WAVE = ACC_UNM_TIER_WAVE };
@@ -59,43 +58,14 @@ __device__ __forceinline__ Ts dep_of(const In &d, uint32_t i) { return Ts{ d.dm[
 __device__ __forceinline__ Ts id_of(const CfkResident &s, uint32_t e) { return Ts{ s.em[e], s.el[e], s.en[e] }; }
 __device__ __forceinline__ Ts x_of(const CfkResident &s, uint32_t e) { return Ts{ s.xm[e], s.xl[e], s.xn[e] }; }
 
-// last index i of off[0, n) with off[i] <= v (the one non-empty segment that holds element v)
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *off, uint32_t n, uint32_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (off[m] <= v) lo = m; else hi = m; }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t lower_key(const uint64_t *a, uint32_t n, uint64_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
-// first entry of [lo, hi) with TxnId >= t
-__device__ __forceinline__ uint32_t lower_entry(const CfkResident &s, uint32_t lo, uint32_t hi, const Ts &t)
-{
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (mc::cmp(id_of(s, m), t) < 0) lo = m + 1; else hi = m; }
-    return lo;
-}
-
-// the same from a lower bound `from` of the answer: doubling steps, then a bisection of the last step
+// first entry of [from, hi) with TxnId >= t, from a lower bound `from` of the answer: doubling steps, then a bisection of
+// the last step
 __device__ __forceinline__ uint32_t gallop_entry(const CfkResident &s, uint32_t from, uint32_t hi, const Ts &t)
 {
-    if (from >= hi || mc::cmp(id_of(s, from), t) >= 0) return from;
+    if (from >= hi || cmp(id_of(s, from), t) >= 0) return from;
     uint32_t lo = from, w = 1;   // entry lo is below t
-    while (lo + w < hi && mc::cmp(id_of(s, lo + w), t) < 0) { lo += w; w <<= 1; }
-    return lower_entry(s, lo + 1, min(lo + w, hi), t);
-}
-
-// first dep of [lo, hi) >= t (txnIds.find(shardRedundantBefore): the index, or the insert point)
-__device__ __forceinline__ uint32_t lower_dep(const uint64_t *dm, const uint64_t *dl, const int32_t *dn, uint32_t lo, uint32_t hi,
-                                              const Ts &t)
-{
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(dm[m], dl[m], dn[m], t.m, t.l, t.n) < 0) lo = m + 1; else hi = m; }
-    return lo;
+    while (lo + w < hi && cmp(id_of(s, lo + w), t) < 0) { lo += w; w <<= 1; }
+    return lower_bound_ts(s.em, s.el, s.en, lo + 1, min(lo + w, hi), t);
 }
 
 // ---------------------------------------------------------------- register: validation
@@ -140,10 +110,9 @@ __global__ __launch_bounds__(BLOCK) void k_um_pairs(In d, Map mp, int has_rb, Cf
         return;
     }
     const uint64_t c = d.key[j];
-    const uint32_t k = lower_key(s.key, s.nk, c);
-    p.kidx[j] = k < s.nk && s.key[k] == c ? k : NONE;
+    p.kidx[j] = find_sorted(s.key, s.nk, c);
     const Ts bound = has_rb ? mc::point(mp, c) : Ts{ 0, 0, 0 };
-    p.cut[j] = lower_dep(d.dm, d.dl, d.dn, a, b, bound);
+    p.cut[j] = lower_bound_ts(d.dm, d.dl, d.dn, a, b, bound);   // txnIds.find(shardRedundantBefore): the index, or the insert point
 }
 
 // deps of a pair sorted unique, checked dep by dep (one sync point's pair may hold a hot key's every entry): a dep that
@@ -154,7 +123,7 @@ __global__ __launch_bounds__(BLOCK) void k_um_deporder(In d, uint64_t *__restric
     const uint64_t i64 = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i64 == 0 || i64 >= d.ND) return;
     const uint32_t i = (uint32_t)i64;
-    if (mc::cmp(dep_of(d, i - 1), dep_of(d, i)) < 0) return;
+    if (cmp(dep_of(d, i - 1), dep_of(d, i)) < 0) return;
     if (d.dep_off[seg_of(d.dep_off, (uint32_t)d.NP, i)] != i) atomicOr((unsigned long long *)errs, (unsigned long long)E_DEPS);
 }
 
@@ -199,7 +168,7 @@ __device__ __forceinline__ bool see(const CfkResident &s, uint32_t e, bool aod, 
     const uint32_t st = s.st[e];
     if (st < ACC_ST_COMMITTED) { ready = wta = false; return false; }
     ex = x_of(s, e);
-    if (!aod && mc::cmp(ex, wx) >= 0) return false;
+    if (!aod && cmp(ex, wx) >= 0) return false;
     ready &= st >= ACC_ST_APPLIED;
     return true;
 }
@@ -220,12 +189,12 @@ __global__ __launch_bounds__(BLOCK) void k_um_eval_lane(In d, CfkResident s, Pai
     Ts x{ 0, 0, 0 };
     if (n) {
         const uint32_t e1 = k == NONE ? 0u : s.ent_off[k + 1];
-        uint32_t e = k == NONE ? 0u : lower_entry(s, s.ent_off[k], e1, dep_of(d, i));
+        uint32_t e = k == NONE ? 0u : lower_bound_ts(s.em, s.el, s.en, s.ent_off[k], e1, dep_of(d, i));
         while (i < b) {
-            const int c = e == e1 ? -1 : mc::cmp(dep_of(d, i), id_of(s, e));
+            const int c = e == e1 ? -1 : cmp(dep_of(d, i), id_of(s, e));
             if (c == 0) {   // Timestamp.nonNullOrMax: of two equal executeAts the earlier stays
                 Ts ex;
-                if (see(s, e, aod, wx, ready, wta, ex) && (!has_x || mc::cmp(x, ex) < 0)) { x = ex; has_x = true; }
+                if (see(s, e, aod, wx, ready, wta, ex) && (!has_x || cmp(x, ex) < 0)) { x = ex; has_x = true; }
                 ++i; ++e;
             }
             else if (c > 0) ++e;
@@ -255,9 +224,9 @@ __global__ __launch_bounds__(BLOCK) void k_um_eval_wave(uint64_t first, In d, Cf
     for (uint32_t i = i0 + lane; i < b; i += 64) {
         const Ts t = dep_of(d, i);
         e = gallop_entry(s, e, e1, t);
-        if (e < e1 && mc::cmp(id_of(s, e), t) == 0) {
+        if (e < e1 && cmp(id_of(s, e), t) == 0) {
             Ts ex;
-            if (see(s, e, aod, wx, ready, wta, ex) && (!has_x || mc::cmp(x, ex) < 0)) { x = ex; xi = i; has_x = true; }
+            if (see(s, e, aod, wx, ready, wta, ex) && (!has_x || cmp(x, ex) < 0)) { x = ex; xi = i; has_x = true; }
         } else {
             ready = wta = false;
             o.dmiss[i] = 1;
@@ -271,7 +240,7 @@ __global__ __launch_bounds__(BLOCK) void k_um_eval_wave(uint64_t first, In d, Cf
         const uint32_t yi = shfl_xor(xi, m);
         const bool yh = shfl_xor((uint32_t)has_x, m) != 0;
         if (yh) {
-            const int c = has_x ? mc::cmp(y, x) : 1;
+            const int c = has_x ? cmp(y, x) : 1;
             if (c > 0 || (c == 0 && yi < xi)) { x = y; xi = yi; has_x = true; }
         }
     }
@@ -314,12 +283,11 @@ __global__ __launch_bounds__(BLOCK) void k_um_heads(uint32_t M, const uint32_t *
     if (r > 0) {
         const uint32_t q0 = perm[r - 1];
         khead = mkey[q0] != c;
-        head = khead || mc::cmp(dep_of(d, msrc[q0]), dep_of(d, msrc[q])) != 0;
+        head = khead || cmp(dep_of(d, msrc[q0]), dep_of(d, msrc[q])) != 0;
     }
     hflag[r] = head;
     if (khead) {
-        const uint32_t k = lower_key(s.key, s.nk, c);
-        khead = !(k < s.nk && s.key[k] == c);
+        khead = find_sorted(s.key, s.nk, c) == NONE;
     }
     kflag[r] = khead;
 }
@@ -359,13 +327,10 @@ struct StateOut {
 // additions with (key, TxnId) < (c, t)
 __device__ __forceinline__ uint32_t adds_below(const Adds &a, const In &d, uint64_t c, const Ts &t)
 {
-    uint32_t lo = 0, hi = a.nu;
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
+    return partition_point(0u, a.nu, [&](uint32_t m) {
         const uint64_t mk = a.ukey[m];
-        if (mk < c || (mk == c && mc::cmp(dep_of(d, a.usrc[m]), t) < 0)) lo = m + 1; else hi = m;
-    }
-    return lo;
+        return mk < c || (mk == c && cmp(dep_of(d, a.usrc[m]), t) < 0);
+    });
 }
 
 // the key list merged: an old key moves up by the new keys below it, a new key by the old keys below it; each key's
@@ -377,15 +342,15 @@ __global__ __launch_bounds__(BLOCK) void k_um_place_keys(CfkResident s, uint32_t
     if (i == 0) o.ent_off[s.nk + a.nkn] = ne + a.nu;
     if (i < s.nk) {
         const uint64_t c = s.key[i];
-        const uint32_t dst = i + lower_key(a.nkey, a.nkn, c);
+        const uint32_t dst = i + lower_bound(a.nkey, 0, a.nkn, c);
         o.key[dst] = c;
-        o.ent_off[dst] = s.ent_off[i] + lower_key(a.ukey, a.nu, c);
+        o.ent_off[dst] = s.ent_off[i] + lower_bound(a.ukey, 0, a.nu, c);
     } else {
         const uint32_t i2 = i - s.nk;
         const uint64_t c = a.nkey[i2];
-        const uint32_t pk = lower_key(s.key, s.nk, c);
+        const uint32_t pk = lower_bound(s.key, 0, s.nk, c);
         o.key[i2 + pk] = c;
-        o.ent_off[i2 + pk] = (s.nk ? s.ent_off[pk] : 0u) + lower_key(a.ukey, a.nu, c);
+        o.ent_off[i2 + pk] = (s.nk ? s.ent_off[pk] : 0u) + lower_bound(a.ukey, 0, a.nu, c);
     }
 }
 
@@ -405,9 +370,9 @@ __global__ __launch_bounds__(BLOCK) void k_um_place_ent(CfkResident s, uint32_t 
         const uint32_t u = i - ne;
         const uint64_t c = a.ukey[u];
         const Ts t = dep_of(d, a.usrc[u]);
-        const uint32_t pk = lower_key(s.key, s.nk, c);
+        const uint32_t pk = lower_bound(s.key, 0, s.nk, c);
         uint32_t below = s.nk ? s.ent_off[pk] : 0u;   // the old entries on lower keys
-        if (pk < s.nk && s.key[pk] == c) below = lower_entry(s, s.ent_off[pk], s.ent_off[pk + 1], t);
+        if (pk < s.nk && s.key[pk] == c) below = lower_bound_ts(s.em, s.el, s.en, s.ent_off[pk], s.ent_off[pk + 1], t);
         const uint32_t dst = u + below;
         o.em[dst] = t.m; o.el[dst] = t.l; o.en[dst] = t.n;
         o.xm[dst] = t.m; o.xl[dst] = t.l; o.xn[dst] = t.n;
@@ -470,12 +435,11 @@ __global__ __launch_bounds__(BLOCK) void k_um_step(uint32_t n_rec, Recs t, const
     const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
     if (r >= n_rec) return;
     const uint64_t c = t.key[r];
-    const uint32_t k0 = lower_key(s.key, s.nk, c);
-    const uint32_t k = k0 < s.nk && s.key[k0] == c ? k0 : NONE;
+    const uint32_t k = find_sorted(s.key, s.nk, c);
     uint32_t row = k;          // akey == null: the rows are the store's keys, a key without a CFK has an empty one
     bool asked = true;
     if (akey) {
-        row = lower_key(akey, n_asked, c);
+        row = lower_bound(akey, 0, n_asked, c);
         asked = row < n_asked && akey[row] == c;
     }
     uint32_t act = 0, fl = 0;
@@ -486,29 +450,29 @@ __global__ __launch_bounds__(BLOCK) void k_um_step(uint32_t n_rec, Recs t, const
         Ts until{ t.um[r], t.ul[r], t.un[r] };
         bool gone = false;
         // COMMIT: findPendingCommit is exclusive (:1277-1279, CEIL), minUncommitted == null -> Timestamp.MAX
-        if (pend == ACC_UNM_COMMIT && (mu == NONE || mc::cmp(until, id_of(s, mu)) < 0)) {
+        if (pend == ACC_UNM_COMMIT && (mu == NONE || cmp(until, id_of(s, mu)) < 0)) {
             fl = 1;
             atomicAdd(o.counts, 1ull);
             // updatePending :1342-1388
             const uint32_t d1 = t.dep_off[r + 1];
             const Ts bound = has_rb ? mc::point(mp, c) : Ts{ 0, 0, 0 };
-            uint32_t i = lower_dep(dm, dl, dn, t.dep_off[r], d1, bound);
+            uint32_t i = lower_bound_ts(dm, dl, dn, t.dep_off[r], d1, bound);
             bool ready = true, has_x = false;
             Ts x{ 0, 0, 0 };
             if (i < d1) {
                 const bool aod = awaits_only_deps(t.tl[r]);
                 const Ts wx{ t.xm[r], t.xl[r], t.xn[r] };
                 const uint32_t e1 = k == NONE ? 0u : s.ent_off[k + 1];
-                uint32_t e = k == NONE ? 0u : lower_entry(s, s.ent_off[k], e1, Ts{ dm[i], dl[i], dn[i] });
+                uint32_t e = k == NONE ? 0u : lower_bound_ts(s.em, s.el, s.en, s.ent_off[k], e1, Ts{ dm[i], dl[i], dn[i] });
                 while (i < d1 && e < e1) {
-                    const int cc = mc::cmp(Ts{ dm[i], dl[i], dn[i] }, id_of(s, e));
+                    const int cc = cmp(Ts{ dm[i], dl[i], dn[i] }, id_of(s, e));
                     if (cc > 0) ++e;
                     else if (cc < 0) { atomicOr((unsigned long long *)errs, (unsigned long long)E_ILLEGAL); break; }
                     else {
                         const Ts ex = x_of(s, e);
-                        if (aod || mc::cmp(ex, wx) < 0) {
+                        if (aod || cmp(ex, wx) < 0) {
                             ready &= s.st[e] >= ACC_ST_APPLIED;
-                            if (!has_x || mc::cmp(x, ex) < 0) x = ex;
+                            if (!has_x || cmp(x, ex) < 0) x = ex;
                             has_x = true;
                         }
                         ++i; ++e;
@@ -519,7 +483,7 @@ __global__ __launch_bounds__(BLOCK) void k_um_step(uint32_t n_rec, Recs t, const
             else { pend = ACC_UNM_APPLY; until = x; v = x; act = 1; }
         } else if (pend == ACC_UNM_APPLY) v = until;
         // APPLY: only if minUncommitted == null || next != null (:1211); next == null -> Timestamp.MAX; exclusive
-        if (!gone && pend == ACC_UNM_APPLY && (mu == NONE || nx != NONE) && (nx == NONE || mc::cmp(until, x_of(s, nx)) < 0))
+        if (!gone && pend == ACC_UNM_APPLY && (mu == NONE || nx != NONE) && (nx == NONE || cmp(until, x_of(s, nx)) < 0))
             gone = true;
         if (gone) { act = 2; atomicAdd(o.counts + 1, 1ull); }
     }

@@ -117,13 +117,6 @@ __global__ __launch_bounds__(BLOCK) void k_mc_owners(Upd u, uint32_t *__restrict
     for (uint32_t j = u.rng_off[i]; j < u.rng_off[i + 1]; ++j) rown[j] = i;
 }
 
-__device__ __forceinline__ uint32_t lower_u64(const uint64_t *a, uint32_t n, uint64_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 // distinct cut points (dense ranks of the sorted cuts) -> slot starts
 __global__ __launch_bounds__(BLOCK) void k_mc_slots(uint64_t nc, const uint64_t *__restrict__ cut, const uint32_t *__restrict__ crank,
                                                     uint64_t *__restrict__ slot)
@@ -143,8 +136,8 @@ __global__ __launch_bounds__(BLOCK) void k_mc_chmax(uint64_t Q, Parts p, const u
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= Q) return;
     const uint64_t a = p.a[q], b = p.b[q];
-    const uint32_t i0 = lower_u64(slot, m, a);
-    const uint32_t i1 = b == MAXC ? m - 1 : lower_u64(slot, m, b + 1) - 1;
+    const uint32_t i0 = lower_bound(slot, 0, m, a);
+    const uint32_t i1 = b == MAXC ? m - 1 : lower_bound(slot, 0, m, b + 1) - 1;
     const unsigned long long v = ((unsigned long long)(vrank[p.val[q]] + 1) << 32) | (0xFFFFFFFFu - p.val[q]);
     uint32_t l = i0 + M, r = i1 + M + 1;   // half-open [l, r) over the leaves
     while (l < r) {
@@ -241,8 +234,8 @@ __global__ __launch_bounds__(BLOCK) void k_mc_query(Qs q, Map mp, uint64_t *__re
         uint64_t a, b;
         if (isr) range_closed(s, t, mp.ei, a, b);
         else a = b = s;
-        const uint64_t i0 = lower64(mp.en, mp.nv, a);
-        const uint64_t i1e = b == MAXC ? mp.nv : lower64(mp.st, mp.nv, b + 1);   // intervals with st <= b: [0, i1e)
+        const uint64_t i0 = lower_bound(mp.en, 0, mp.nv, a);
+        const uint64_t i1e = b == MAXC ? mp.nv : lower_bound(mp.st, 0, mp.nv, b + 1);   // intervals with st <= b: [0, i1e)
         if (i0 >= i1e) continue;
         const uint64_t bl0 = (i0 + MC_BLK - 1) / MC_BLK, bl1 = i1e / MC_BLK;
         if (bl0 < bl1) {

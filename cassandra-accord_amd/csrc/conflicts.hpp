@@ -4,6 +4,7 @@
 #pragma once
 
 #include "dict.hpp"
+#include "search.hpp"
 
 struct acc_maxconflicts {
     int device = 0;
@@ -19,12 +20,6 @@ struct acc_maxconflicts {
 namespace acc {
 namespace mc {
 
-struct Ts {
-    uint64_t m, l;
-    int32_t n;
-};
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
-
 struct Map {
     const uint64_t *st, *en, *vm, *vl, *bm, *bl;
     const int32_t *vn, *bn;
@@ -32,17 +27,10 @@ struct Map {
     int ei;
 };
 
-__device__ __forceinline__ uint64_t lower64(const uint64_t *a, uint64_t n, uint64_t v)   // first index with a[i] >= v
-{
-    uint64_t lo = 0, hi = n;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 // the value at key code k: the one interval with st <= k <= en, or Timestamp.NONE where the map holds nothing
 __device__ __forceinline__ Ts point(const Map &mp, uint64_t k)
 {
-    const uint64_t i = lower64(mp.en, mp.nv, k);
+    const uint64_t i = lower_bound(mp.en, 0, mp.nv, k);
     if (i >= mp.nv || mp.st[i] > k) return Ts{ 0, 0, 0 };
     return Ts{ mp.vm[i], mp.vl[i], mp.vn[i] };
 }

@@ -11,6 +11,7 @@
 // node has few stores, so the distinct store sets are few: their coverings are folded on the host with the restated
 // Ranges.with (ranges.hpp) and each txn carries the index of its set's covering.
 #include "prims.hpp"
+#include "search.hpp"
 #include "ranges.hpp"
 
 #include <map>
@@ -37,9 +38,7 @@ __device__ __forceinline__ bool contains_key(const uint64_t *cs, const uint64_t 
 // (after range j - 1) must intersect range j; an entry starting after the last range fails
 __device__ __forceinline__ bool covered(const uint64_t *cs, const uint64_t *ce, uint64_t lo, uint64_t hi, uint64_t s, uint64_t e)
 {
-    uint64_t a = lo, b = hi;   // j = first covering range with start > s
-    while (a < b) { const uint64_t m = (a + b) >> 1; if (cs[m] <= s) a = m + 1; else b = m; }
-    const uint64_t j = a;
+    const uint64_t j = upper_bound(cs, lo, hi, s);   // first covering range with start > s
     if (j > lo && s < ce[j - 1]) return true;
     if (j == hi) return false;
     return !(cs[j] >= e || ce[j] <= s);   // Range.compareIntersecting == 0

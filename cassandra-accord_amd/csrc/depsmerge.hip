@@ -17,6 +17,7 @@
 //      raw bits then replay the fold exactly (one lane per such group, k_rep_exact) to pick the same instance;
 //   4. output: codes / ranges / raw TxnIds mapped back from the dictionaries.
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -40,17 +41,6 @@ __global__ __launch_bounds__(BLOCK) void k_dm_range_check(size_t n, const uint64
     if (__ballot(bad) && lane_id() == 0) atomicOr((unsigned long long *)err, 1ull);
 }
 
-__device__ __forceinline__ uint64_t ub_u64(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t v)   // first a[i] > v
-{
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
-}
-__device__ __forceinline__ uint64_t lb_u32(const uint32_t *a, uint64_t lo, uint64_t hi, uint32_t v)
-{
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 struct Rep {
     const uint64_t *grp_off, *key_off, *val_off, *k2v_off;   // inputs (device)
     uint64_t R, NV;
@@ -67,8 +57,8 @@ struct Rep {
 };
 
 // reply of value slot i (replies own contiguous slot ranges), group of reply r
-__device__ __forceinline__ uint64_t reply_of(const Rep &p, uint64_t i) { return ub_u64(p.val_off, 0, p.R + 1, i) - 1; }
-__device__ __forceinline__ uint32_t group_of(const Rep &p, uint64_t r) { return (uint32_t)(ub_u64(p.grp_off, 0, (uint64_t)p.ng + 1, r) - 1); }
+__device__ __forceinline__ uint64_t reply_of(const Rep &p, uint64_t i) { return upper_bound(p.val_off, 0, p.R + 1, i) - 1; }
+__device__ __forceinline__ uint32_t group_of(const Rep &p, uint64_t r) { return (uint32_t)(upper_bound(p.grp_off, 0, (uint64_t)p.ng + 1, r) - 1); }
 __device__ __forceinline__ bool reply_empty(const Rep &p, uint64_t r)   // RelationMultiMap.isEmpty (:1012-1015)
 {
     return p.k2v_off[r + 1] - p.k2v_off[r] == p.key_off[r + 1] - p.key_off[r];
@@ -82,7 +72,7 @@ __global__ __launch_bounds__(BLOCK) void k_rep_first(Rep p)
     const uint64_t r = reply_of(p, i);
     if (reply_empty(p, r)) return;
     const uint32_t g = group_of(p, r);
-    const uint64_t pos = lb_u32(p.out_rank, p.out_val_off[g], p.out_val_off[g + 1], p.vrank[i]);
+    const uint64_t pos = lower_bound(p.out_rank, p.out_val_off[g], p.out_val_off[g + 1], p.vrank[i]);
     atomicMin(&p.rep[pos], (uint32_t)i);
 }
 
@@ -93,7 +83,7 @@ __global__ __launch_bounds__(BLOCK) void k_rep_check(Rep p)
     const uint64_t r = reply_of(p, i);
     if (reply_empty(p, r)) return;
     const uint32_t g = group_of(p, r);
-    const uint64_t pos = lb_u32(p.out_rank, p.out_val_off[g], p.out_val_off[g + 1], p.vrank[i]);
+    const uint64_t pos = lower_bound(p.out_rank, p.out_val_off[g], p.out_val_off[g + 1], p.vrank[i]);
     const uint32_t s = p.rep[pos];
     if (s == (uint32_t)i) return;
     if (p.msb[s] != p.msb[i] || p.lsb[s] != p.lsb[i] || p.node[s] != p.node[i]) {

@@ -12,6 +12,7 @@
 // varying bits of every word, sortedness) and the order-rank dictionary of a batch's 2N timestamps, by the sorted-batch
 // shortcut or the general sort (prep_dictionary, redo_general_dictionary, check_errors).
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -259,8 +260,7 @@ __global__ __launch_bounds__(BLOCK) void k_prep_txn(uint32_t n, size_t P, const 
         if (!__syncthreads_or(bad ? 1 : 0) && P) {
             const uint32_t a = (uint32_t)min((size_t)ko[0], P), b = (uint32_t)min((size_t)ko[tcnt], P);
             for (uint32_t j = a + tid; j < b; j += BLOCK) {
-                uint32_t lo = 0, hi = tcnt;   // last txn i with ko[i] <= j (empty txns share their offset with the next)
-                while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (ko[m] <= j) lo = m; else hi = m; }
+                const uint32_t lo = seg_of(ko, tcnt, j);   // last txn i with ko[i] <= j (empty txns share their offset with the next)
                 owner[j] = t0 + lo;
                 const uint64_t kc = key_code[j];
                 km |= kc ^ kref;
@@ -304,15 +304,6 @@ __global__ __launch_bounds__(BLOCK) void k_b_compact(uint32_t n, const uint32_t 
     }
 }
 
-__device__ __forceinline__ uint32_t lower_bound_u64(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v)
-{
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_rank_txn_sorted(uint32_t n, uint32_t nb, const uint64_t *__restrict__ tkey,
                                                            const uint64_t *__restrict__ sb, const uint32_t *__restrict__ bflag,
                                                            uint32_t *__restrict__ rank, uint32_t *__restrict__ txn_of_rank,
@@ -321,7 +312,7 @@ __global__ __launch_bounds__(BLOCK) void k_rank_txn_sorted(uint32_t n, uint32_t 
     uint32_t t = blockIdx.x * BLOCK + threadIdx.x;
     uint64_t tie = 0;
     if (t < n) {
-        uint32_t lb = lower_bound_u64(sb, 0, nb, tkey[t]);
+        uint32_t lb = lower_bound(sb, 0, nb, tkey[t]);
         if (lb < nb && sb[lb] == tkey[t]) tie = 1;
         uint32_t r = t + lb;
         rank[t] = r;
@@ -342,7 +333,7 @@ __global__ __launch_bounds__(BLOCK) void k_rank_b_sorted(uint32_t n, uint32_t nb
     if (k < nb) {
         if (k > 0 && sb[k] == sb[k - 1]) tie = 1;
         uint32_t t = bsrc[sperm[k]];
-        rank[n + t] = k + lower_bound_u64(tkey, 0, n, sb[k]);
+        rank[n + t] = k + lower_bound(tkey, 0, n, sb[k]);
     }
     uint64_t v[1] = { tie };
     block_or_n<1>(v, g + 6);

@@ -33,6 +33,7 @@
 // Fragments are in ascending slot order. The receiver checks what a header alone can tell (magic, flags, G, the slot
 // and count section sizes against nfrag, the sizes against the message length) on the host before it launches anything.
 #include "prims.hpp"
+#include "search.hpp"
 
 #include <vector>
 
@@ -192,8 +193,8 @@ __global__ __launch_bounds__(BLOCK) void k_fe_write(uint64_t first, uint64_t F, 
         const uint64_t kbyte = m.kbm + (kbo[f] - m.kb0);
         const uint32_t no = (uint32_t)(oo[f + 1] - oo[f]);
         for (uint32_t j = nk + lane; j < no; j += 64) {
-            uint32_t lo = 0, hi = nk;   // key of entry position j: first k with end[k] > j
-            while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint32_t)a[mid] > j) hi = mid; else lo = mid + 1; }
+            // key of entry position j: first k with end[k] > j
+            const uint32_t lo = partition_point(0u, nk, [&](uint32_t k) { return (uint32_t)a[k] <= j; });
             put_bit(mb, kbyte, (uint64_t)lo * nv + (uint32_t)a[j]);
         }
     }

@@ -496,8 +496,7 @@ __global__ __launch_bounds__(BLOCK) void k_bcx_expand(uint32_t nb, uint32_t n, c
     __syncthreads();
     const uint64_t hi = min((uint64_t)so[cnt], nout);
     for (uint64_t j = (uint64_t)so[0] + tid; j < hi; j += BLOCK) {
-        uint32_t lo = 0, up = cnt;   // last i with so[i] <= j
-        while (up - lo > 1) { const uint32_t m = (lo + up) >> 1; if (so[m] <= j) lo = m; else up = m; }
+        const uint32_t lo = seg_of(so, cnt, (uint32_t)j);   // last i with so[i] <= j (j < so[cnt])
         const uint32_t t = st[lo];
         const uint64_t kc = pext_runs(key_code[key_off[t] + (uint32_t)(j - so[lo])], rk);
         const uint64_t w = ((uint32_t)(tl[t] >> 1) & 7u) == 1u ? 1u : 0u;
@@ -640,7 +639,7 @@ __device__ __forceinline__ V2Query v2_query(const V2View &v, uint32_t p)
         q.bstart = q.bend;   // no bumped committed entry before posM in this segment (b1 == b0)
         return q;
     }
-    q.pos = q.bq ? lower_bound_u32(v.s_rank, p + 1, s1, S) : p;
+    q.pos = q.bq ? lower_bound(v.s_rank, p + 1, s1, S) : p;
     q.rp = q.bq ? ld_row(v, q.pos) : rpp;
     // M from the last unbumped committed Write before pos
     const uint32_t lu = q.rp.c[RW_LUCW];
@@ -650,7 +649,7 @@ __device__ __forceinline__ V2Query v2_query(const V2View &v, uint32_t p)
     bool has_mb = false;
     uint32_t mb = 0;
     if (b1 > b0) {
-        uint32_t i = lower_bound_u32(v.bcs_exec, b0, b1, S);
+        uint32_t i = lower_bound(v.bcs_exec, b0, b1, S);
         if (i > b0) {
             uint32_t w = (uint32_t)v.bcs_lastw[i - 1];
             if (w > b0) { has_mb = true; mb = v.bcs_exec[w - 1]; }
@@ -660,10 +659,11 @@ __device__ __forceinline__ V2Query v2_query(const V2View &v, uint32_t p)
     q.m = (has_mb && (!has_mu || mb > mu)) ? mb : mu;
     if (!q.has_m) q.posm = q.s0;
     else if (has_mu && q.m == mu) q.posm = lu - 1;
-    else q.posm = lower_bound_u32(v.s_rank, q.s0, q.pos, q.m);
+    else q.posm = lower_bound(v.s_rank, q.s0, q.pos, q.m);
     q.rm = q.posm == q.s0 ? q.r0 : (spec && q.posm == lu0 - 1) ? rms : ld_row(v, q.posm);
     q.bend = q.rm.c[RW_CBC];
-    q.bstart = q.has_m ? lower_bound_lo32(v.bc_pm, b0, q.bend, q.m + 1) : q.bend;
+    // first bumped committed entry whose prefix max (the low words, ascending over one segment) reaches M + 1
+    q.bstart = q.has_m ? partition_point(b0, q.bend, [&](uint32_t i) { return (uint32_t)v.bc_pm[i] < q.m + 1; }) : q.bend;
     return q;
 }
 
@@ -1042,9 +1042,7 @@ template <int MAXK>
 __device__ __forceinline__ bool fetch_elem(const RunsT<MAXK> &R, const V2View &v, const TxnCtx &c, uint32_t e,
                                            uint32_t &x, uint32_t &k)
 {
-    uint32_t lo = 0, hi = c.nk;
-    while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (R.kbase[mid] <= e) lo = mid; else hi = mid; }
-    k = lo;
+    k = seg_of(R.kbase, c.nk, e);
     uint32_t off = e - R.kbase[k];
     if (R.m[k] == INLINE_M) {   // inline record: the entry itself (filters applied by the count pass)
         x = inl_entry(v.irec32, v.rec, 16 * R.start[k][0] + off);
@@ -1181,9 +1179,7 @@ template <int MAXK>
 __device__ __forceinline__ void locate_elem(const RunsT<MAXK> &R, uint32_t nk, uint32_t e, uint32_t &idx, uint32_t &k, bool &r3,
                                             bool &inl)
 {
-    uint32_t lo = 0, hi = nk;
-    while (hi - lo > 1) { uint32_t mid = (lo + hi) >> 1; if (R.kbase[mid] <= e) lo = mid; else hi = mid; }
-    k = lo;
+    k = seg_of(R.kbase, nk, e);
     uint32_t off = e - R.kbase[k];
     inl = R.m[k] == INLINE_M;
     if (inl) { idx = 16 * R.start[k][0] + off; r3 = false; return; }
@@ -1813,12 +1809,7 @@ __global__ __launch_bounds__(BLOCK) void k_v2_write_win(const uint32_t *__restri
                 for (uint32_t oq = 0; oq < (uint32_t)WAVES; ++oq) {
                     if (oq == own) continue;
                     const uint32_t s0 = min(oq * Q, n_out);
-                    uint32_t lo = s0, hi = min(s0 + Q, n_out);
-                    while (lo < hi) {
-                        const uint32_t mid = (lo + hi) >> 1;
-                        if (L.out[mid] < x) lo = mid + 1; else hi = mid;
-                    }
-                    pos += lo - s0;
+                    pos += lower_bound(L.out, s0, min(s0 + Q, n_out), x) - s0;
                 }
                 L.out2[pos] = x;
             }
@@ -2651,13 +2642,6 @@ __global__ __launch_bounds__(BLOCK) void k_v3_nelist(uint32_t n, const uint32_t 
 // chunk in windows of BLOCK txns (u_off / source bases in LDS, each output's txn by binary search there).
 constexpr uint32_t UC_CHUNK = 4096;
 
-__device__ __forceinline__ uint32_t last_le(const uint64_t *a, uint32_t n, uint64_t x)   // largest i < n with a[i] <= x
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (a[m] <= x) lo = m; else hi = m; }
-    return lo;
-}
-
 // tmap (optional): the txns are tmap[0, *n_dev) with offsets u_off[0, *n_dev] (the non-empty txns of a sparse batch,
 // k_v3_nelist), else 0..n-1 over the batch's u_off.
 __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_t *__restrict__ u_off,
@@ -2681,7 +2665,7 @@ __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_
     const uint64_t c0 = (uint64_t)blockIdx.x * UC_CHUNK;
     if (c0 >= total) return;
     const uint64_t c1 = min(total, c0 + UC_CHUNK);
-    if (tid == 0) { s_t[0] = last_le(u_off, n, c0); s_t[1] = last_le(u_off, n, c1 - 1); }
+    if (tid == 0) { s_t[0] = seg_of(u_off, n, c0); s_t[1] = seg_of(u_off, n, c1 - 1); }
     __syncthreads();
     const uint32_t tlo = s_t[0], thi = s_t[1];
     auto source = [&](uint32_t j) {
@@ -2692,8 +2676,7 @@ __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_
         // sparse chunk (long runs of txns without TxnIds, e.g. the range txns of a mixed batch): every output finds its
         // txn by a binary search of u_off over the chunk's txn span
         for (uint64_t i = c0 + tid; i < c1; i += BLOCK) {
-            uint32_t lo = tlo, hi = thi + 1;
-            while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (u_off[m] <= i) lo = m; else hi = m; }
+            const uint32_t lo = tlo + seg_of(u_off + tlo, thi + 1 - tlo, i);
             const uint64_t sb = source(lo), off = i - u_off[lo];
             dep_txn[i] = (sb >> 63) ? dep_big[(sb & ~(1ull << 63)) + off] : dep_scr[sb + off];
         }
@@ -2719,7 +2702,7 @@ __global__ __launch_bounds__(BLOCK) void k_v3_ucompact(uint32_t n, const uint64_
                 const uint64_t i = i0 + (uint64_t)u * BLOCK;
                 x[u] = 0; big[u] = false;
                 if (i < hi) {
-                    const uint32_t a = last_le(uo, nt, i);
+                    const uint32_t a = seg_of(uo, nt, i);
                     const uint64_t sb = src[a], off = i - uo[a];
                     big[u] = (sb >> 63) != 0;
                     x[u] = big[u] ? dep_big[(sb & ~(1ull << 63)) + off] : dep_scr[sb + off];

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -28,25 +29,6 @@ struct V2Cols {
     uint64_t *bc_key;     // (seg << rbits) | exec, for the (seg, executeAt) sort; null when the build made that order
                           // from the txn side (CfkBuild::bc_side)
 };
-
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// first i in [lo, hi) with (uint32_t)a[i] >= v, the low words ascending over the range (one segment's prefix maxima)
-__device__ __forceinline__ uint32_t lower_bound_lo32(const uint64_t *a, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if ((uint32_t)a[m] < v) lo = m + 1; else hi = m;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ uint64_t shfl_xor64(uint64_t v, int m)
 {
@@ -111,7 +93,7 @@ __device__ __forceinline__ Query make_query_ts(const CfkView &v, uint32_t t, uin
     q.wk = witnesses((uint32_t)(v.tl[t] >> 1) & 7u);
     q.s0 = s0;
     // insertPos(0, startedBefore): first txn with TxnId >= S (CommandsForKey.java:1698-1703)
-    q.pos = lower_bound_u32(v.s_rank, s0, s1, S);
+    q.pos = lower_bound(v.s_rank, s0, s1, S);
     // maxCommittedBefore (CommandsForKey.java:618-625): FAST bisection of S over committed[] by executeAt
     uint32_t c0 = v.cl_start[seg], c1 = v.cl_start[seg + 1];
     uint32_t from = c0, to = c1;
@@ -132,7 +114,7 @@ __device__ __forceinline__ Query make_query_ts(const CfkView &v, uint32_t t, uin
         if (w != 0 && w - 1 >= c0) { q.has_m = true; q.m = v.cl_exec[w - 1]; }
     }
     // Committed entries below scanStart all have executeAt < M (prefix max < M): pruned
-    q.scan_start = q.has_m ? lower_bound_u32(v.pmax, s0, q.pos, q.m + 1) : s0;
+    q.scan_start = q.has_m ? lower_bound(v.pmax, s0, q.pos, q.m + 1) : s0;
     q.ub = v.cum_u[s0];
     q.ue = v.cum_u[q.scan_start];
     return q;

@@ -43,9 +43,7 @@ __device__ __forceinline__ uint32_t mx_bound(const uint64_t *seg_key, const uint
     if (x < k0) return 0;
     uint64_t b = (x - k0) >> sh;
     if (b >= (1ull << tbits)) return nseg;
-    uint32_t lo = bstart[b], hi = bstart[b + 1];
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (upper ? seg_key[m] <= x : seg_key[m] < x) lo = m + 1; else hi = m; }
-    return lo;
+    return partition_point(bstart[b], bstart[b + 1], [&](uint32_t m) { return upper ? seg_key[m] <= x : seg_key[m] < x; });
 }
 
 // validation (TxnId.domain(), Range start < end, Ranges.ofSortedAndDeoverlapped) and, per range, its run of covered

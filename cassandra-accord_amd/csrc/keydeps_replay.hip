@@ -131,15 +131,6 @@ __device__ __forceinline__ bool contains_u32(const uint32_t *a, uint64_t lo, uin
     return false;
 }
 
-__device__ __forceinline__ uint64_t lower_bound_u32_64(const uint32_t *a, uint64_t lo, uint64_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        uint64_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // first[e] = dep is not in an earlier key's list of the same txn (the union keeps one copy).
 __global__ __launch_bounds__(BLOCK) void k_first(uint64_t E, const uint32_t *__restrict__ deps, const uint32_t *__restrict__ list_of,
                                                  const uint32_t *__restrict__ owner, const uint32_t *__restrict__ key_off,
@@ -197,7 +188,7 @@ __global__ __launch_bounds__(BLOCK) void k_write_entries(uint64_t E, const uint3
     for (uint32_t jj = j0; jj < j1; ++jj) {
         uint64_t a = dep_off[jj], b = dep_off[jj + 1];
         if (a == b) continue;
-        uint64_t lb = jj == j ? e : lower_bound_u32_64(deps, a, b, d);
+        uint64_t lb = jj == j ? e : lower_bound(deps, a, b, d);
         idx += cumf[lb] - cumf[a];
     }
     uint32_t kd = cnz[j1] - cnz[j0];

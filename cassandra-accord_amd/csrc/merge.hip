@@ -15,6 +15,7 @@
 #include <cstdio>
 
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -170,12 +171,6 @@ __global__ __launch_bounds__(BLOCK) void k_m_write_keys(uint64_t n, const uint64
     out_key[idx[i]] = key_code[src[i]];
 }
 
-__device__ __forceinline__ uint64_t lb_u64(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t v)
-{
-    while (lo < hi) { uint64_t mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // Entry part of keysToTxnIds: the index of the value in its group's txnIds. Header part: the record that
 // closes a (group, key) run (duplicates included) writes that key's end offset and marks the key.
 __global__ __launch_bounds__(BLOCK) void k_m_write_k2v(uint64_t n, const uint64_t *__restrict__ s, MergePlan plan,
@@ -196,13 +191,12 @@ __global__ __launch_bounds__(BLOCK) void k_m_write_k2v(uint64_t n, const uint64_
     const uint64_t obase = kv_gstart[g] + k0;      // entries + headers of earlier groups
     if (flag[i]) {
         const uint32_t v = txn_rank[val_of_slot[src[i]]];
-        uint64_t lo = v_gstart[g], hi = v_gstart[g + 1];
-        while (lo < hi) { uint64_t mid = (lo + hi) >> 1; if (out_val[mid] < v) lo = mid + 1; else hi = mid; }
+        const uint64_t lo = lower_bound(out_val, v_gstart[g], v_gstart[g + 1], v);
         out_k2v[obase + nk + (idx[i] - kv_gstart[g])] = (int32_t)(lo - v_gstart[g]);
     }
     const bool last = i + 1 == n || s[i + 1] == plan.pad_kv || (s[i + 1] >> plan.vshift_kv) != (x >> plan.vshift_kv);
     if (last) {
-        uint64_t a = lb_u64(out_key, k0, k0 + nk, key_code[key_of_slot[src[i]]]);
+        uint64_t a = lower_bound(out_key,k0, k0 + nk, key_code[key_of_slot[src[i]]]);
         out_k2v[obase + (a - k0)] = (int32_t)(nk + (idx[i] + flag[i] - kv_gstart[g]));
         has[a] = 1;
     }
@@ -377,13 +371,6 @@ __device__ __forceinline__ uint32_t lds_unique(T *s, uint32_t np, T pad, uint32_
         if ((uint32_t)q < per && ((f >> q) & 1u)) s[o++] = x[q];
     __syncthreads();
     return total;
-}
-
-__device__ __forceinline__ uint32_t lds_ub(const uint32_t *a, uint32_t n, uint32_t v)   // first index with a[i] > v
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { uint32_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
 }
 
 struct MlOut {
@@ -571,9 +558,7 @@ __global__ __launch_bounds__(ML_NT) void k_m_lds(uint64_t first, uint32_t ng, co
         Ug = lds_unique<uint32_t, ML_VC / ML_NT>(vs, lds_pad_block(vs, NV, PAD32), PAD32, scan_lds);
         for (uint32_t i = tid; i < NV; i += ML_NT) {
             const uint32_t v = rawv[i];
-            uint32_t a = 0, b = Ug;
-            while (a < b) { uint32_t m = (a + b) >> 1; if (vs[m] < v) a = m + 1; else b = m; }
-            rawv[i] = a;   // each thread rewrites only its own slots
+            rawv[i] = lower_bound(vs, 0, Ug, v);   // each thread rewrites only its own slots
         }
         for (uint32_t u = tid; u < Ug; u += ML_NT) o.s_val[VA + u] = vs[u];
         __syncthreads();

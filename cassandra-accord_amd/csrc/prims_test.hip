@@ -1,10 +1,12 @@
-// prims_test.hip — a test shim over prims.hpp (libaccord_prims_test.so): NOT part of the product ABI, nothing here is
+// prims_test.hip — a test shim over prims.hpp and search.hpp (libaccord_prims_test.so): NOT part of the product ABI, nothing here is
 // declared in include/accord_amd.h. Each entry point runs one primitive on an acc_ctx made by the main library's
 // acc_create (acc_ctx is header-only; both libraries are built with the same flags, so the layout is the same), takes
-// HOST arrays in and out, and returns after a sync: the Python side (tests/test_prims_gpu.py) needs numpy and ctypes only.
+// HOST arrays in and out, and returns after a sync: the Python side (tests/test_prims_gpu.py, tests/test_search_gpu.py)
+// needs numpy and ctypes only.
 // Every device output buffer is filled with FILL bytes before the primitive runs and copied back whole, one guard
 // element included, so a store the primitive should not have made shows in the result.
 #include "prims.hpp"
+#include "search.hpp"
 
 #include <map>
 
@@ -162,6 +164,55 @@ __global__ __launch_bounds__(BLOCK) void k_t_pext_runs(size_t n, const uint64_t 
 {
     const size_t i = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i < n) out[i] = pext_runs(w[i], r);
+}
+
+// ---------------------------------------------------------------- search.hpp, one kernel per helper, a thread per query
+
+template <class T, class I, bool UPPER>
+__global__ __launch_bounds__(BLOCK) void k_t_bound(const T *__restrict__ a, const uint64_t *__restrict__ lo,
+                                                   const uint64_t *__restrict__ hi, const uint64_t *__restrict__ v, uint32_t nq,
+                                                   uint64_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= nq) return;
+    out[q] = UPPER ? upper_bound(a, (I)lo[q], (I)hi[q], (T)v[q]) : lower_bound(a, (I)lo[q], (I)hi[q], (T)v[q]);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_t_seg_of(const uint32_t *__restrict__ off, uint32_t n, const uint32_t *__restrict__ v,
+                                                    uint32_t nq, uint32_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q < nq) out[q] = seg_of(off, n, v[q]);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_t_find_sorted(const uint64_t *__restrict__ a, uint32_t n, const uint64_t *__restrict__ v,
+                                                         uint32_t nq, uint32_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q < nq) out[q] = find_sorted(a, n, v[q]);
+}
+
+struct TsCols {
+    const uint64_t *m, *l;
+    const int32_t *n;
+};
+template <bool UPPER>
+__global__ __launch_bounds__(BLOCK) void k_t_ts_bound(TsCols a, const uint32_t *__restrict__ lo, const uint32_t *__restrict__ hi, TsCols v,
+                                                      uint32_t nq, uint32_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
+    if (q >= nq) return;
+    const Ts t = ts_at(v.m, v.l, v.n, q);
+    out[q] = UPPER ? upper_bound_ts(a.m, a.l, a.n, lo[q], hi[q], t) : lower_bound_ts(a.m, a.l, a.n, lo[q], hi[q], t);
+}
+
+// a wave per query; every lane reports the (wave-uniform) result: out[64 q + lane]
+__global__ __launch_bounds__(BLOCK) void k_t_wave_search(const uint64_t *__restrict__ a, const uint32_t *__restrict__ lo,
+                                                         const uint32_t *__restrict__ hi, const uint64_t *__restrict__ v, int upper,
+                                                         uint32_t nq, uint32_t *__restrict__ out)
+{
+    const uint32_t q = blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (q < nq) out[(size_t)q * 64 + lane_id()] = wave_search(a, lo[q], hi[q], v[q], upper != 0);
 }
 
 }  // namespace
@@ -358,6 +409,90 @@ int acct_pext_runs(acc_ctx *ctx, uint64_t mask, const uint64_t *w, uint64_t n, u
         uint64_t *o = filled<uint64_t>(ctx, "pt_out0", (size_t)n);
         launch(ctx, "t_pext_runs", k_t_pext_runs, dim3(grid_for((size_t)n, BLOCK)), dim3(BLOCK), 0, (size_t)n, d, r, o);
         download(ctx, out, o, (size_t)n);
+        ctx->sync();
+    });
+}
+
+// lower_bound (upper == 0) / upper_bound over a[0, n) of u32 (elem64 == 0) or u64 elements, with a u32 (idx64 == 0) or u64
+// index type: query q searches the window [lo[q], hi[q]) for v[q]. out holds nq + 1 values (a guard element).
+int acct_search_bound(acc_ctx *ctx, int elem64, int idx64, int upper, const void *a, uint64_t n, const uint64_t *lo,
+                      const uint64_t *hi, const uint64_t *v, uint32_t nq, uint64_t *out)
+{
+    return acc_guard(ctx, [&] {
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lo[q] > hi[q] || hi[q] > n) fail(ACC_E_ARG, "prims_test: search window outside the array");
+        const uint64_t *dlo = upload(ctx, "pt_lo", lo, nq), *dhi = upload(ctx, "pt_hi", hi, nq), *dv = upload(ctx, "pt_v", v, nq);
+        uint64_t *o = filled<uint64_t>(ctx, "pt_out0", (size_t)nq + 1);
+        auto run = [&](auto tv, auto iv) {
+            using T = decltype(tv);
+            using I = decltype(iv);
+            const T *d = upload(ctx, "pt_in0", static_cast<const T *>(a), (size_t)n);
+            if (!nq) return;
+            if (upper) launch(ctx, "t_bound", k_t_bound<T, I, true>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, d, dlo, dhi, dv, nq, o);
+            else launch(ctx, "t_bound", k_t_bound<T, I, false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, d, dlo, dhi, dv, nq, o);
+        };
+        if (elem64) { if (idx64) run(uint64_t(), uint64_t()); else run(uint64_t(), uint32_t()); }
+        else { if (idx64) run(uint32_t(), uint64_t()); else run(uint32_t(), uint32_t()); }
+        download(ctx, out, o, (size_t)nq + 1);
+        ctx->sync();
+    });
+}
+
+// out[q] = seg_of(off, n, v[q]) over the n offsets off[0, n); out holds nq + 1 values
+int acct_seg_of(acc_ctx *ctx, const uint32_t *off, uint32_t n, const uint32_t *v, uint32_t nq, uint32_t *out)
+{
+    return acc_guard(ctx, [&] {
+        const uint32_t *d = upload(ctx, "pt_in0", off, n), *dv = upload(ctx, "pt_v", v, nq);
+        uint32_t *o = filled<uint32_t>(ctx, "pt_out0", (size_t)nq + 1);
+        if (nq) launch(ctx, "t_seg_of", k_t_seg_of, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, d, n, dv, nq, o);
+        download(ctx, out, o, (size_t)nq + 1);
+        ctx->sync();
+    });
+}
+
+// out[q] = find_sorted(a, n, v[q]); out holds nq + 1 values
+int acct_find_sorted(acc_ctx *ctx, const uint64_t *a, uint32_t n, const uint64_t *v, uint32_t nq, uint32_t *out)
+{
+    return acc_guard(ctx, [&] {
+        const uint64_t *d = upload(ctx, "pt_in0", a, n), *dv = upload(ctx, "pt_v", v, nq);
+        uint32_t *o = filled<uint32_t>(ctx, "pt_out0", (size_t)nq + 1);
+        if (nq) launch(ctx, "t_find_sorted", k_t_find_sorted, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, d, n, dv, nq, o);
+        download(ctx, out, o, (size_t)nq + 1);
+        ctx->sync();
+    });
+}
+
+// lower_bound_ts (upper == 0) / upper_bound_ts over the column triple (m, l, nd)[0, n): query q searches [lo[q], hi[q]) for
+// (qm, ql, qn)[q]; out holds nq + 1 values
+int acct_ts_bound(acc_ctx *ctx, int upper, const uint64_t *m, const uint64_t *l, const int32_t *nd, uint32_t n, const uint32_t *lo,
+                  const uint32_t *hi, const uint64_t *qm, const uint64_t *ql, const int32_t *qn, uint32_t nq, uint32_t *out)
+{
+    return acc_guard(ctx, [&] {
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lo[q] > hi[q] || hi[q] > n) fail(ACC_E_ARG, "prims_test: search window outside the array");
+        const TsCols a{ upload(ctx, "pt_am", m, n), upload(ctx, "pt_al", l, n), upload(ctx, "pt_an", nd, n) };
+        const TsCols v{ upload(ctx, "pt_qm", qm, nq), upload(ctx, "pt_ql", ql, nq), upload(ctx, "pt_qn", qn, nq) };
+        const uint32_t *dlo = upload(ctx, "pt_lo", lo, nq), *dhi = upload(ctx, "pt_hi", hi, nq);
+        uint32_t *o = filled<uint32_t>(ctx, "pt_out0", (size_t)nq + 1);
+        if (nq && upper) launch(ctx, "t_ts_bound", k_t_ts_bound<true>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, a, dlo, dhi, v, nq, o);
+        else if (nq) launch(ctx, "t_ts_bound", k_t_ts_bound<false>, dim3(grid_for(nq, BLOCK)), dim3(BLOCK), 0, a, dlo, dhi, v, nq, o);
+        download(ctx, out, o, (size_t)nq + 1);
+        ctx->sync();
+    });
+}
+
+// wave_search over a[0, n), one wave per query window [lo[q], hi[q]); out holds 64 * nq + 1 values: every lane's result
+int acct_wave_search(acc_ctx *ctx, const uint64_t *a, uint32_t n, const uint32_t *lo, const uint32_t *hi, const uint64_t *v,
+                     int upper, uint32_t nq, uint32_t *out)
+{
+    return acc_guard(ctx, [&] {
+        for (uint32_t q = 0; q < nq; ++q)
+            if (lo[q] > hi[q] || hi[q] > n) fail(ACC_E_ARG, "prims_test: search window outside the array");
+        const uint64_t *d = upload(ctx, "pt_in0", a, n), *dv = upload(ctx, "pt_v", v, nq);
+        const uint32_t *dlo = upload(ctx, "pt_lo32", lo, nq), *dhi = upload(ctx, "pt_hi32", hi, nq);
+        uint32_t *o = filled<uint32_t>(ctx, "pt_out0", (size_t)nq * 64 + 1);
+        if (nq) launch(ctx, "t_wave_search", k_t_wave_search, dim3((nq + WAVES - 1) / WAVES), dim3(BLOCK), 0, d, dlo, dhi, dv, upper, nq, o);
+        download(ctx, out, o, (size_t)nq * 64 + 1);
         ctx->sync();
     });
 }

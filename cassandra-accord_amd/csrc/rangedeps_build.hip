@@ -3,6 +3,7 @@
 // compacted into the Java-layout CSR.
 
 #include "rangedeps.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -303,8 +304,7 @@ __device__ void build_block(const Out &o, uint32_t t, uint64_t *A, uint64_t *B, 
                 const uint32_t k = k0 + (uint32_t)u * BLOCK;
                 x[u] = 0;
                 if (k < m) {
-                    uint32_t lo = 0, hi = nq;   // last query starting at or before k
-                    while (hi - lo > 1) { const uint32_t md = (lo + hi) >> 1; if (qs[md] <= k) lo = md; else hi = md; }
+                    const uint32_t lo = seg_of(qs, nq, k);   // last query starting at or before k
                     x[u] = o.ent[qo[lo] + (k - qs[lo])];
                 }
             }

@@ -3,6 +3,7 @@
 // View::ent.
 
 #include "rangedeps.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -53,12 +54,8 @@ __global__ void k_rd_qgroups(const uint64_t *__restrict__ keys, uint32_t P, uint
     if (g > 4) return;
     uint32_t b = g == 0 ? P : Q;
     if (groups && g >= 1 && g <= 3) {
-        uint32_t lo = P, hi = Q;   // first sorted position whose group field is >= 4 | g
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo) >> 1);
-            if ((keys[mid] >> top_shift) < (4u | g)) lo = mid + 1; else hi = mid;
-        }
-        b = lo;
+        // first sorted position whose group field is >= 4 | g
+        b = partition_point(P, Q, [&](uint32_t m) { return (keys[m] >> top_shift) < (4u | g); });
     }
     bnd[g] = b;
 }
@@ -118,52 +115,6 @@ __global__ __launch_bounds__(BLOCK) void k_rd_qsort(uint32_t Qp, uint32_t P, uin
 }
 
 // ---------------------------------------------------------------- stabbing
-
-__device__ __forceinline__ uint32_t lower_bound_s(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v)
-{
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t *a, uint32_t lo, uint32_t hi, uint32_t v)
-{
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ uint32_t upper_bound_s(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v)
-{
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
-// 64-ary search by one wave: first index in [lo, hi) whose value is >= v (upper = false) or > v (upper = true).
-// Each round is one parallel probe of 64 positions, so a 1M-entry class takes 4 dependent loads, not 20.
-__device__ __forceinline__ uint32_t wave_search(const uint64_t *a, uint32_t lo, uint32_t hi, uint64_t v, bool upper)
-{
-    const uint32_t lane = lane_id();
-    while (hi - lo > 64) {
-        const uint32_t step = (hi - lo + 63) / 64;
-        const uint32_t p = lo + lane * step;
-        const bool below = p < hi && (upper ? a[p] <= v : a[p] < v);
-        const uint32_t c = (uint32_t)__popcll(__ballot(below));
-        if (c == 0) return lo;
-        const uint32_t base = lo + (c - 1) * step;   // a[base] is below v, the answer is in (base, base + step]
-        lo = base + 1;
-        hi = min(base + step + 1, hi);
-    }
-    const uint32_t p = lo + lane;
-    const bool below = p < hi && (upper ? a[p] <= v : a[p] < v);
-    return lo + (uint32_t)__popcll(__ballot(below));
-}
 
 struct StabTile {
     uint64_t s[TILE], e[TILE];
@@ -252,8 +203,8 @@ __device__ __forceinline__ uint32_t stab_pass(const View &v, StabTile &T, bool v
             const uint64_t W = class_width(c);
             // this query's own window inside the tile: starts in [lo - W, hi]
             uint32_t k;
-            if (REL) k = lower_bound_u32(T.s32, 0, len, (uint64_t)qlo > W ? qlo - (uint32_t)W : 0u);
-            else k = lower_bound_s(T.s, 0, len, r.lo > W ? r.lo - W : 0);
+            if (REL) k = lower_bound(T.s32, 0, len, (uint64_t)qlo > W ? qlo - (uint32_t)W : 0u);
+            else k = lower_bound(T.s, 0, len, r.lo > W ? r.lo - W : 0);
             for (; k < len; ++k) {
                 bool hit;
                 if (REL) {
@@ -301,8 +252,8 @@ __global__ __launch_bounds__(BLOCK) void k_rd_stab_win(uint32_t nsb, const uint6
     uint32_t b0 = a0, b1 = a0;
     if (a1 > a0) {
         const uint64_t lo = blo[blk], hi = bhi[blk], W = class_width(c);
-        b0 = lower_bound_s(v.cs_s, a0, a1, lo > W ? lo - W : 0);
-        b1 = upper_bound_s(v.cs_s, b0, a1, hi);
+        b0 = lower_bound(v.cs_s, a0, a1, lo > W ? lo - W : 0);
+        b1 = upper_bound(v.cs_s, b0, a1, hi);
     }
     win[(size_t)blk * 2 * NCLS + c] = b0;
     win[(size_t)blk * 2 * NCLS + NCLS + c] = b1;
@@ -328,7 +279,7 @@ __device__ __forceinline__ uint32_t stab_flat_rel(const View &v, StabTile &T, bo
         if (p0 == p1) continue;
         const uint64_t W = class_width(c);
         const uint32_t qwlo = (uint64_t)qlo > W ? qlo - (uint32_t)W : 0u;
-        for (uint32_t k = lower_bound_u32(T.s32, p0, p1, qwlo); k < p1; ++k) {
+        for (uint32_t k = lower_bound(T.s32, p0, p1, qwlo); k < p1; ++k) {
             const uint32_t s = T.s32[k];
             if (s > qhi) break;
             const uint32_t e = T.e32[k];
@@ -370,7 +321,7 @@ __device__ __forceinline__ uint32_t stab_flat(const View &v, StabTile &T, bool v
         if (p0 == p1) continue;
         const uint64_t W = class_width(c);
         const uint64_t qwlo = r.lo > W ? r.lo - W : 0;
-        for (uint32_t k = lower_bound_s(T.s, p0, p1, qwlo); k < p1; ++k) {
+        for (uint32_t k = lower_bound(T.s, p0, p1, qwlo); k < p1; ++k) {
             const uint64_t s = T.s[k];
             if (s > r.hi) break;
             const uint64_t e = T.e[k];
@@ -449,8 +400,7 @@ __global__ __launch_bounds__(BLOCK) void k_rd_stab(View v)
     uint64_t hv[STAB_RH];
     if (flat) {
         for (uint32_t k = tid; k < wtot; k += BLOCK) {
-            uint32_t lo = 0, hi = NCLS;   // the class holding flat position k: last c with pre[c] <= k
-            while (hi - lo > 1) { const uint32_t md = (lo + hi) >> 1; if (T.pre[md] <= k) lo = md; else hi = md; }
+            const uint32_t lo = seg_of(T.pre, NCLS, k);   // the class holding flat position k: last c with pre[c] <= k
             const uint32_t src = T.b0[lo] + (k - T.pre[lo]);
             const uint64_t cs = v.cs_s[src], ce = v.cs_e[src];
             T.s[k] = cs; T.e[k] = ce; T.info[k] = v.cs_info[src]; T.kind[k] = v.cs_kind[src];

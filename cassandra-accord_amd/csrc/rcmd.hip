@@ -216,11 +216,7 @@ __global__ __launch_bounds__(BLOCK) void k_rc_locate(uint32_t G, Delta d, Table 
     const uint64_t xm = d.tm[i0], xl = d.tl[i0];
     const int32_t xn = d.tn[i0];
     if (!(xl & 1u)) { pos[r] = NONE; isnew[r] = 0; bound[r] = 0; return; }
-    uint32_t lo = 0, hi = s.n;
-    while (lo < hi) {
-        const uint32_t m = (lo + hi) >> 1;
-        if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m;
-    }
+    const uint32_t lo = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, Ts{ xm, xl, xn });
     const bool found = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], xm, xl, xn) == 0;
     uint64_t b = found ? (uint64_t)(s.rng_off[lo + 1] - s.rng_off[lo]) : 0ull;
     for (uint32_t p = gstart[r]; p < gstart[r + 1]; ++p) {
@@ -418,13 +414,7 @@ __global__ __launch_bounds__(BLOCK) void k_rp_lim(uint32_t m, const uint64_t *__
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
     uint32_t lo = 0;
     if (j < m) {
-        const uint64_t xm = bm[j], xl = bl[j];
-        const int32_t xn = bn[j];
-        uint32_t hi = s.n;
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (ts_cmp(s.tm[mid], s.tl[mid], s.tn[mid], xm, xl, xn) < 0) lo = mid + 1; else hi = mid;
-        }
+        lo = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, ts_at(bm, bl, bn, j));
         lim[j] = lo;
     }
 #pragma unroll
@@ -442,9 +432,7 @@ __global__ __launch_bounds__(BLOCK) void k_rp_rowner(uint32_t n, const uint32_t 
 // the first input range that ends above a (the input is sorted and disjoint: its ends ascend)
 __device__ __forceinline__ uint32_t first_above(const uint64_t *__restrict__ re, uint32_t m, uint64_t a)
 {
-    uint32_t lo = 0, hi = m;
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (re[mid] <= a) lo = mid + 1; else hi = mid; }
-    return lo;
+    return upper_bound(re, 0, m, a);
 }
 
 // What the prune's second pass writes per kept row and per new range.
@@ -600,7 +588,7 @@ __global__ __launch_bounds__(BLOCK) void k_rt_trim(Delta d, const uint32_t *__re
             uint64_t cur = a;
             bool open = true;
             // the first interval whose end lies above a: en > a (EndInclusive), en + 1 > a
-            uint64_t i = mp.ei ? mc::lower64(mp.en, mp.nv, a + 1) : mc::lower64(mp.en, mp.nv, a);
+            uint64_t i = mp.ei ? lower_bound(mp.en, 0, mp.nv, a + 1) : lower_bound(mp.en, 0, mp.nv, a);
             for (; i < mp.nv; ++i) {
                 const uint64_t st = mp.st[i], en = mp.en[i];
                 const uint64_t is = mp.ei ? st - 1 : st;
@@ -688,40 +676,17 @@ __global__ __launch_bounds__(BLOCK) void k_rc_qprep(Queries Q, Table s, int test
             }
         if (e) atomicOr((unsigned long long *)&g[0], (unsigned long long)e);
         if constexpr (RECOVERY) {
-            const uint64_t xm = Q.tm[q];
-            const int32_t xn = Q.tn[q];
-            uint32_t lo = 0, hi = s.n;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, l, xn) < 0) lo = m + 1; else hi = m;
-            }
-            const uint32_t lower = lo;
-            hi = s.n;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], xm, l, xn) <= 0) lo = m + 1; else hi = m;
-            }
-            const uint32_t upper = lo;
+            const Ts x{ Q.tm[q], l, Q.tn[q] };
+            const uint32_t lower = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, x);
+            const uint32_t upper = upper_bound_ts(s.tm, s.tl, s.tn, lower, s.n, x);
             const uint32_t lim = started_at == ACC_STARTED_BEFORE ? lower : started_at == ACC_STARTED_AFTER ? s.n - upper : s.n;
             tinfo[q] = make_uint4(lim, NONE, mask, range ? 1u : 0u);
         } else {
             // lim: first stored TxnId >= S; tpos: first stored TxnId >= the query's own, when equal
-            const uint64_t sm = Q.xm[q], sl = Q.xl[q];
-            const int32_t sn = Q.xn[q];
-            uint32_t lo = 0, hi = s.n;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], sm, sl, sn) < 0) lo = m + 1; else hi = m;
-            }
-            const uint32_t lim = lo;
-            const uint64_t qm = Q.tm[q];
-            const int32_t qn = Q.tn[q];
-            lo = 0; hi = s.n;
-            while (lo < hi) {
-                const uint32_t m = (lo + hi) >> 1;
-                if (ts_cmp(s.tm[m], s.tl[m], s.tn[m], qm, l, qn) < 0) lo = m + 1; else hi = m;
-            }
-            const uint32_t tpos = lo < s.n && ts_cmp(s.tm[lo], s.tl[lo], s.tn[lo], qm, l, qn) == 0 ? lo : NONE;
+            const uint32_t lim = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, ts_at(Q.xm, Q.xl, Q.xn, q));
+            const Ts id{ Q.tm[q], l, Q.tn[q] };
+            const uint32_t lo = lower_bound_ts(s.tm, s.tl, s.tn, 0, s.n, id);
+            const uint32_t tpos = lo < s.n && cmp(ts_at(s.tm, s.tl, s.tn, lo), id) == 0 ? lo : NONE;
             tinfo[q] = make_uint4(lim, tpos, mask, range ? 1u : 0u);
         }
     }

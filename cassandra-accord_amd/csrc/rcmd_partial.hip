@@ -53,19 +53,6 @@ __device__ __forceinline__ uint64_t iv_end(const MapCols &m, uint32_t i)
     return m.ei ? en : (en == ~0ull ? en : en + 1);
 }
 
-__device__ __forceinline__ uint32_t lower32(const uint64_t *__restrict__ a, uint32_t n, uint64_t v)   // first a[i] >= v
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-__device__ __forceinline__ uint32_t upper32(const uint32_t *__restrict__ a, uint32_t n, uint32_t v)   // first a[i] > v
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 // ---------------------------------------------------------------- the union index
 
 // per interval: the compare words of its bound (k_rc_validate's), live = bound > TxnId.NONE; g[0] counts the live ones
@@ -96,11 +83,7 @@ __global__ __launch_bounds__(BLOCK) void k_pu_gloc(uint32_t G, MapCols m, const 
     const uint32_t i0 = first[r];
     const uint64_t xm = m.vm[i0], xl = m.vl[i0];
     const int32_t xn = m.vn[i0];
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t md = (lo + hi) >> 1;
-        if (ts_cmp(tm[md], tl[md], tn[md], xm, xl, xn) < 0) lo = md + 1; else hi = md;
-    }
+    const uint32_t lo = lower_bound_ts(tm, tl, tn, 0, n, Ts{ xm, xl, xn });
     const bool found = lo < n && ts_cmp(tm[lo], tl[lo], tn[lo], xm, xl, xn) == 0;
     gpos[r] = lo;
     gfound[r] = found ? 1u : 0u;
@@ -116,11 +99,7 @@ __global__ __launch_bounds__(BLOCK) void k_pu_iloc(MapCols m, const uint32_t *__
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= m.nv) return;
     const uint64_t s = iv_start(m, i), e = iv_end(m, i);
-    uint32_t lo = 0, hi = nd;
-    while (lo < hi) {
-        const uint32_t md = (lo + hi) >> 1;
-        if (ds[md] < s || (ds[md] == s && de[md] < e)) lo = md + 1; else hi = md;
-    }
+    const uint32_t lo = partition_point(0u, nd, [&](uint32_t md) { return ds[md] < s || (ds[md] == s && de[md] < e); });
     const bool found = lo < nd && ds[lo] == s && de[lo] == e;
     idp[i] = lo;
     iabs[i] = live[i] && !found ? 1u : 0u;
@@ -136,7 +115,7 @@ __global__ __launch_bounds__(BLOCK) void k_pu_rows(uint32_t n, uint32_t G, const
 {
     const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
     if (j > n) return;
-    const uint32_t u = j + gax[upper32(gpos, G, j)];
+    const uint32_t u = j + gax[upper_bound(gpos, 0, G, j)];
     rowpos[j] = u;
     if (j == n) return;
     im[u] = tm[j]; il[u] = tl[j]; in[u] = tn[j];
@@ -163,7 +142,7 @@ __global__ __launch_bounds__(BLOCK) void k_pu_dict(uint32_t nd, uint32_t nv, con
 {
     const uint32_t d = blockIdx.x * BLOCK + threadIdx.x;
     if (d >= nd) return;
-    const uint32_t u = d + iax[upper32(idp, nv, d)];
+    const uint32_t u = d + iax[upper_bound(idp, 0, nv, d)];
     dmap[d] = u;
     us[u] = ds[d]; ue[u] = de[d];
 }
@@ -192,7 +171,7 @@ __global__ __launch_bounds__(BLOCK) void k_pu_iwrite(MapCols m, const uint32_t *
     uint32_t sh = 0;
     if (gfound[r] && !(flags[row] & ACC_RCMD_ERASED)) {
         const uint32_t a = rng_off[row], b = rng_off[row + 1];
-        const uint32_t k = a + lower32(rs + a, b - a, s);   // a command's ranges are sorted and disjoint
+        const uint32_t k = lower_bound(rs, a, b, s);   // a command's ranges are sorted and disjoint
         sh = k < b && rs[k] == s && re[k] == e ? 1u : 0u;
     }
     ishare[i] = sh;
@@ -233,11 +212,11 @@ __device__ __forceinline__ void touched(const MapCols &m, const Parts &p, uint32
     prev = NONE;
     if (w < p.P) {
         const uint64_t k = p.key[w];
-        i0 = lower32(m.en, m.nv, k);
+        i0 = lower_bound(m.en, 0, m.nv, k);
         i1 = i0 < m.nv && m.st[i0] <= k ? i0 + 1 : i0;
         if (w > p.key_off[p.owner[w]]) {
             const uint64_t kp = p.key[w - 1];
-            const uint32_t j = lower32(m.en, m.nv, kp);
+            const uint32_t j = lower_bound(m.en, 0, m.nv, kp);
             if (j < m.nv && m.st[j] <= kp) prev = j;
         }
         return;
@@ -246,8 +225,8 @@ __device__ __forceinline__ void touched(const MapCols &m, const Parts &p, uint32
     // the intervals (is, ie) with ie > a and is < b: two ranges of one bound type intersect as sets of keys, touching
     // ends do not. ie > a: en > a (EndInclusive), en + 1 > a; is < b: st - 1 < b, st < b
     auto run = [&](uint64_t a, uint64_t b, uint32_t &f, uint32_t &l) {
-        f = m.ei ? (a == ~0ull ? m.nv : lower32(m.en, m.nv, a + 1)) : lower32(m.en, m.nv, a);
-        l = m.ei ? (b == ~0ull ? m.nv : lower32(m.st, m.nv, b + 1)) : lower32(m.st, m.nv, b);
+        f = m.ei ? (a == ~0ull ? m.nv : lower_bound(m.en, 0, m.nv, a + 1)) : lower_bound(m.en, 0, m.nv, a);
+        l = m.ei ? (b == ~0ull ? m.nv : lower_bound(m.st, 0, m.nv, b + 1)) : lower_bound(m.st, 0, m.nv, b);
         if (l < f) l = f;
     };
     run(p.rs[r], p.re[r], i0, i1);

@@ -29,21 +29,6 @@ enum : uint64_t {
     RC_ERR_MISS_IDX = 16, RC_ERR_MISS_SORT = 32, RC_ERR_MISS_OFF = 64,
 };
 
-template <class T>
-__device__ __forceinline__ uint32_t rc_lower(const T *a, uint32_t lo, uint32_t hi, T v)
-{
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] < v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
-// first index in [0, n) with a[idx] > v
-__device__ __forceinline__ uint32_t rc_upper64(const uint64_t *a, uint32_t n, uint64_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 __global__ __launch_bounds__(BLOCK) void k_rc_src_of_rank(size_t m, const uint32_t *__restrict__ rank,
                                                           uint32_t *__restrict__ src_of_rank, uint32_t *__restrict__ nranks)
 {
@@ -96,13 +81,12 @@ __global__ __launch_bounds__(BLOCK) void k_rc_query(uint32_t nq, const uint64_t 
     const uint64_t xm = qm[q], xl = ql[q];
     const int32_t xn = qn[q];
     const uint32_t nr = s.nranks ? *s.nranks : 0u;
-    uint32_t lo = 0, hi = nr;
     auto cmp_rank = [&](uint32_t r) {
         const uint32_t src = s.src_of_rank[r];
         return src < s.n ? ts_cmp(s.tm[src], s.tl[src], s.tn[src], xm, xl, xn)
                          : ts_cmp(s.em[src - s.n], s.el[src - s.n], s.en[src - s.n], xm, xl, xn);
     };
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (cmp_rank(m) < 0) lo = m + 1; else hi = m; }
+    const uint32_t lo = partition_point(0u, nr, [&](uint32_t m) { return cmp_rank(m) < 0; });
     qlo[q] = lo;
     qeq[q] = lo < nr && cmp_rank(lo) == 0;
     const uint32_t kind = (uint32_t)(xl >> 1) & 7u;
@@ -137,18 +121,16 @@ __global__ __launch_bounds__(BLOCK) void k_rc_items(uint32_t Qp, uint32_t nq, co
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= Qp) return;
-    uint32_t lo = 0, hi = nq + 1;   // q = (first index with qoff > i) - 1
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (qoff[m] <= i) lo = m + 1; else hi = m; }
-    const uint32_t q = lo - 1;
+    const uint32_t q = upper_bound(qoff, 0, nq + 1, i) - 1;   // (first index with qoff > i) - 1
     item_q[i] = q;
     uint32_t a = 0, w = 0;
     const uint64_t k = qkey[i];
-    const uint32_t s = c.nseg ? rc_lower<uint64_t>(c.seg_key, 0, c.nseg, k) : 0;
+    const uint32_t s = c.nseg ? lower_bound(c.seg_key, 0, c.nseg, k) : 0;
     if (s < c.nseg && c.seg_key[s] == k) {
         const uint32_t sb = c.seg_start[s], se = s + 1 < c.nseg ? c.seg_start[s + 1] : c.P;
         const uint32_t x = qlo[q];
         // Arrays.binarySearch(txns, testTxnId): found <=> X is a member; insertPos = its index or the insert point
-        const uint32_t pos = rc_lower<uint32_t>(c.s_rank, sb, se, x);
+        const uint32_t pos = lower_bound(c.s_rank, sb, se, x);
         const bool known = qeq[q] && pos < se && c.s_rank[pos] == x;
         if (known || p.test_dep != ACC_DEP_WITH) {
             const uint32_t start = p.started_at == ACC_STARTED_AFTER ? pos : sb;
@@ -201,7 +183,7 @@ __global__ __launch_bounds__(BLOCK) void k_rc_scan(uint64_t first, uint64_t nchu
 {
     const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
-    const uint32_t item = rc_upper64(ch.chunk_off, ch.Qp + 1, cw) - 1;
+    const uint32_t item = upper_bound(ch.chunk_off, 0, ch.Qp + 1, cw) - 1;
     const uint32_t q = ch.item_q[item];
     const uint32_t base = ch.item_a[item] + (uint32_t)(cw - ch.chunk_off[item]) * RC_CH;
     const uint32_t end = ch.item_a[item] + ch.item_w[item];
@@ -577,12 +559,8 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
             if (Q.ps[j - 1] >= Q.ps[j]) { e |= RR_ERR_PARTS; break; }
     }
     // lower = #entries with TxnId < X, upper = #entries with TxnId <= X
-    uint32_t lo = 0, hi = c.n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
-    const uint32_t lower = lo;
-    hi = c.n;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.tm[m], c.tl[m], c.tn[m], xm, xl, xn) <= 0) lo = m + 1; else hi = m; }
-    const uint32_t upper = lo;
+    const uint32_t lower = lower_bound_ts(c.tm, c.tl, c.tn, 0, c.n, Ts{ xm, xl, xn });
+    const uint32_t upper = upper_bound_ts(c.tm, c.tl, c.tn, lower, c.n, Ts{ xm, xl, xn });
     uint32_t a = 0, w = c.n;
     if (started_at == ACC_STARTED_BEFORE) w = lower;                                // txnId < X (:897-898)
     else if (started_at == ACC_STARTED_AFTER) { a = upper; w = c.n - upper; }       // txnId > X (:894-896)
@@ -595,6 +573,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_query(RrQueries Q, RrCmds c, int t
 // does range (s, e) of a command intersect the query's participants (Routables.foldl over rangeCommand.ranges, sliced)
 __device__ __forceinline__ bool rr_hits_query(const RrQueries &Q, uint32_t q, uint64_t s, uint64_t e, bool ei)
 {
+    // (hand loops, as in rr_deps_intersect: through search.hpp k_rr_scan takes two more SGPRs and loses a wave per SIMD)
     uint32_t a = Q.poff[q], b = Q.poff[q + 1];
     const uint32_t end = b;
     if (Q.isr[q]) {
@@ -620,7 +599,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_scan(uint64_t first, uint64_t nchu
 {
     const uint64_t cw = first + (uint64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
     if (cw >= nchunks) return;
-    const uint32_t q = rc_upper64(ch.chunk_off, ch.nq + 1, cw) - 1;
+    const uint32_t q = upper_bound(ch.chunk_off, 0, ch.nq + 1, cw) - 1;
     const uint32_t i = ch.qa[q] + (uint32_t)(cw - ch.chunk_off[q]) * 64u + lane_id();
     const uint64_t xm = Q.qm[q], xl = Q.ql[q];
     const int32_t xn = Q.qn[q];
@@ -669,8 +648,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_qoff(uint32_t nq, uint64_t U, cons
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     if (q > nq) return;
-    uint64_t lo = 0, hi = U;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if ((uk[m] >> qshift) < q) lo = m + 1; else hi = m; }
+    const uint64_t lo = partition_point((uint64_t)0, U, [&](uint64_t m) { return (uk[m] >> qshift) < q; });
     eoff[q] = lo;
     rd_off[q] = gexcl[lo];
     arena_off[q] = gexcl[lo] + lo;
@@ -706,8 +684,7 @@ __global__ __launch_bounds__(BLOCK) void k_rr_uoff(uint32_t nq, uint64_t U, cons
 {
     const uint32_t q = blockIdx.x * BLOCK + threadIdx.x;
     if (q > nq) return;
-    uint64_t lo = 0, hi = U;
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if ((tk[m] >> tb) < q) lo = m + 1; else hi = m; }
+    const uint64_t lo = partition_point((uint64_t)0, U, [&](uint64_t m) { return (tk[m] >> tb) < q; });
     u_off[q] = uexcl[lo];
 }
 

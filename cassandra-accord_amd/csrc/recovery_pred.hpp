@@ -14,7 +14,7 @@
 
 #include "../../include/accord_amd.h"
 #include "ctx.hpp"
-#include "ts.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -62,10 +62,11 @@ __device__ __forceinline__ bool rr_contains(uint64_t s, uint64_t e, uint64_t k, 
 template <class C>
 __device__ bool rr_deps_intersect(const C &c, uint32_t i, uint64_t xm, uint64_t xl, int32_t xn)
 {
-    uint32_t lo = c.doff[i], hi = c.doff[i + 1];
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ts_cmp(c.dm[m], c.dl[m], c.dn[m], xm, xl, xn) < 0) lo = m + 1; else hi = m; }
+    const uint32_t lo = lower_bound_ts(c.dm, c.dl, c.dn, c.doff[i], c.doff[i + 1], Ts{ xm, xl, xn });
     const uint32_t r0 = c.roff[i], r1 = c.roff[i + 1];
     const bool ei = c.end_incl != 0;
+    // (the two range searches below stay hand loops: through search.hpp the scan kernels that inline this take two more
+    // SGPRs, and recovery.hip's k_rr_scan loses a wave per SIMD)
     for (uint32_t j = lo; j < c.doff[i + 1] && ts_cmp(c.dm[j], c.dl[j], c.dn[j], xm, xl, xn) == 0; ++j) {
         const uint64_t s = c.ds[j];
         if (c.dk[j]) {

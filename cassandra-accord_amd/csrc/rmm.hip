@@ -10,23 +10,16 @@
 // A batch holds one deps object per group in the SerializerSupport layout; results are per group (per query for stab)
 // CSRs, device-resident in the context. Integer work only (HBM-bound sorts, scans and binary searches).
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
 namespace {
 
-__device__ __forceinline__ uint64_t ub64(const uint64_t *a, uint64_t lo, uint64_t hi, uint64_t v)   // first a[i] > v
-{
-    while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (a[m] <= v) lo = m + 1; else hi = m; }
-    return lo;
-}
-
 // header slot of entry position `local` (>= nk) of a keysToValues int[]: the key whose end offset first exceeds it
 __device__ __forceinline__ uint32_t key_of_entry(const int32_t *h, uint32_t nk, uint32_t local)
 {
-    uint32_t lo = 0, hi = nk;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if ((uint32_t)h[m] <= local) lo = m + 1; else hi = m; }
-    return lo;
+    return partition_point(0u, nk, [&](uint32_t m) { return (uint32_t)h[m] <= local; });
 }
 
 struct Batch {
@@ -50,7 +43,7 @@ __global__ __launch_bounds__(BLOCK) void k_b_validate(Batch b, uint64_t *__restr
     }
     if (q < b.NO && !(e & 1)) {
         // entry position q of the flattened ints
-        const uint64_t g = ub64(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
+        const uint64_t g = upper_bound(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
         const uint64_t nk = b.key_off[g + 1] - b.key_off[g], no = b.k2v_off[g + 1] - b.k2v_off[g], nv = b.val_off[g + 1] - b.val_off[g];
         const uint64_t local = q - b.k2v_off[g];
         const int32_t x = b.k2v[q];
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(BLOCK) void k_inv_expand(Batch b, uint64_t *__restr
 {
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= b.NO) return;
-    const uint64_t g = ub64(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
+    const uint64_t g = upper_bound(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
     const uint32_t nk = (uint32_t)(b.key_off[g + 1] - b.key_off[g]);
     const uint32_t local = (uint32_t)(q - b.k2v_off[g]);
     if (local < nk) { slot[q] = b.NV; key[q] = 0; return; }
@@ -85,7 +78,7 @@ __global__ __launch_bounds__(BLOCK) void k_inv_header(Batch b, const uint32_t *_
 {
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= b.NV) return;
-    const uint64_t g = ub64(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
     const uint64_t v0 = b.val_off[g], nv = b.val_off[g + 1] - v0;
     const uint64_t ebefore = b.k2v_off[g] - b.key_off[g];   // entries of earlier groups (their slots sort first)
     const uint64_t base = v0 + ebefore;                     // the group's output offset
@@ -99,7 +92,7 @@ __global__ __launch_bounds__(BLOCK) void k_inv_entries(Batch b, uint64_t nent, c
     const uint64_t p = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (p >= nent) return;
     const uint64_t s = sslot[p];
-    const uint64_t g = ub64(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
     const uint64_t v0 = b.val_off[g], nv = b.val_off[g + 1] - v0;
     const uint64_t ebefore = b.k2v_off[g] - b.key_off[g];
     out[v0 + ebefore + nv + (p - ebefore)] = (int32_t)skey[p];
@@ -125,15 +118,14 @@ __global__ __launch_bounds__(BLOCK) void k_sl_select(Batch b, Sel sel, uint32_t 
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= b.NK) return;
-    const uint64_t g = ub64(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
+    const uint64_t g = upper_bound(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
     const uint64_t a0 = sel.off[g], a1 = sel.off[g + 1];
     bool hit = false;
     if (a1 > a0) {
         if (!sel.is_range) {
             const uint64_t c = b.key_a[i];
             // last select range starting below c (EndInclusive: s < c) / at or below c (StartInclusive: s <= c)
-            uint64_t lo = a0, hi = a1;
-            while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (sel.end_inclusive ? sel.s[m] < c : sel.s[m] <= c) lo = m + 1; else hi = m; }
+            const uint64_t lo = partition_point(a0, a1, [&](uint64_t m) { return sel.end_inclusive ? sel.s[m] < c : sel.s[m] <= c; });
             if (lo > a0) {
                 const uint64_t e = sel.e[lo - 1];
                 hit = sel.end_inclusive ? c <= e : c < e;
@@ -141,8 +133,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_select(Batch b, Sel sel, uint32_t 
         } else {
             const uint64_t s = b.key_a[i], e = b.key_b[i];
             // first select range ending after s (ends ascend: deoverlapped); it intersects iff it starts before e
-            uint64_t lo = a0, hi = a1;
-            while (lo < hi) { const uint64_t m = (lo + hi) >> 1; if (sel.e[m] <= s) lo = m + 1; else hi = m; }
+            const uint64_t lo = upper_bound(sel.e, a0, a1, s);
             hit = lo < a1 && sel.s[lo] < e;
         }
     }
@@ -185,7 +176,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_used_all(Batch b, const uint32_t *
 {
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= b.NV) return;
-    const uint64_t g = ub64(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
     const uint32_t m = mode[g];
     used[s] = (m == SL_EMPTY_IN || m == SL_ALL) ? 1u : 0u;
 }
@@ -195,7 +186,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_used_entries(Batch b, const uint32
 {
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= b.NO) return;
-    const uint64_t g = ub64(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
+    const uint64_t g = upper_bound(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
     if (mode[g] != SL_SLICE) return;
     const uint32_t nk = (uint32_t)(b.key_off[g + 1] - b.key_off[g]);
     const uint32_t local = (uint32_t)(q - b.k2v_off[g]);
@@ -217,7 +208,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_write_keys(Batch b, SlOut o)
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= b.NK) return;
-    const uint64_t g = ub64(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
+    const uint64_t g = upper_bound(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
     const uint32_t m = o.mode[g];
     const uint64_t k0 = b.key_off[g], k = i - k0, nk = b.key_off[g + 1] - k0;
     const int32_t *h = b.k2v + b.k2v_off[g];
@@ -238,7 +229,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_write_vals(Batch b, SlOut o)
 {
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= b.NV) return;
-    const uint64_t g = ub64(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(b.val_off, 0, (uint64_t)b.ng + 1, s) - 1;
     if (o.used_excl[s + 1] == o.used_excl[s]) return;
     o.val_idx[o.val_out[g] + (o.used_excl[s] - o.used_excl[b.val_off[g]])] = (uint32_t)(s - b.val_off[g]);
 }
@@ -247,7 +238,7 @@ __global__ __launch_bounds__(BLOCK) void k_sl_write_entries(Batch b, SlOut o)
 {
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= b.NO) return;
-    const uint64_t g = ub64(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
+    const uint64_t g = upper_bound(b.k2v_off, 0, (uint64_t)b.ng + 1, q) - 1;
     const uint32_t m = o.mode[g];
     const uint32_t nk = (uint32_t)(b.key_off[g + 1] - b.key_off[g]);
     const uint32_t local = (uint32_t)(q - b.k2v_off[g]);
@@ -285,16 +276,12 @@ __device__ __forceinline__ void stab_window(const Batch &b, const Stab &s, uint3
     const bool key = s.qe == nullptr;
     const uint64_t y = key ? x : s.qe[q];
     // hi: ranges with start < y (EndInclusive key: start < k; StartInclusive key: start <= k; range query: start < end)
-    uint64_t l = a0, h = a1;
     const bool incl = key && !s.end_inclusive;
-    while (l < h) { const uint64_t m = (l + h) >> 1; if (incl ? b.key_a[m] <= y : b.key_a[m] < y) l = m + 1; else h = m; }
-    hi = l;
+    hi = partition_point(a0, a1, [&](uint64_t m) { return incl ? b.key_a[m] <= y : b.key_a[m] < y; });
     // lo: first range whose prefix-max end reaches x (EndInclusive key: end >= k; StartInclusive key: end > k;
     // range query: end > start)
     const bool ge = key && s.end_inclusive;
-    l = a0; h = hi;
-    while (l < h) { const uint64_t m = (l + h) >> 1; if (ge ? s.pmax[m] < x : s.pmax[m] <= x) l = m + 1; else h = m; }
-    lo = l;
+    lo = partition_point(a0, hi, [&](uint64_t m) { return ge ? s.pmax[m] < x : s.pmax[m] <= x; });
 }
 
 __device__ __forceinline__ bool stab_hit(const Batch &b, const Stab &s, uint32_t q, uint64_t i)
@@ -366,7 +353,7 @@ __global__ __launch_bounds__(BLOCK) void k_stab_pm_in(Batch b, const uint32_t *_
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= b.NK) return;
-    const uint64_t g = ub64(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
+    const uint64_t g = upper_bound(b.key_off, 0, (uint64_t)b.ng + 1, i) - 1;
     pm[i] = (g << 32) | ((uint64_t)erank[i] + 1);
 }
 
@@ -638,7 +625,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_set_check(uint32_t ng, WoSet s, ui
     bool bad = false;
     if (q < ng && s.off[q + 1] < s.off[q]) bad = true;
     if (q < ns) {
-        const uint64_t g = ub64(s.off, 0, (uint64_t)ng + 1, q) - 1;
+        const uint64_t g = upper_bound(s.off, 0, (uint64_t)ng + 1, q) - 1;
         if (q > s.off[g] && ts_cmp(s.m[q - 1], s.l[q - 1], s.n[q - 1], s.m[q], s.l[q], s.n[q]) >= 0) bad = true;
     }
     if (__ballot(bad) && bad) atomicOr((unsigned long long *)err, 4ull);
@@ -650,7 +637,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_keep(Wo w)
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s > w.NV) return;
     if (s == w.NV) { w.keep[s] = 0; return; }
-    const uint64_t g = ub64(w.val_off, 0, (uint64_t)w.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(w.val_off, 0, (uint64_t)w.ng + 1, s) - 1;
     const uint64_t m = w.tm[s], l = w.tl[s];
     const int32_t n = w.tn[s];
     w.keep[s] = (wo_contains(w.a, g, m, l, n) || wo_contains(w.b, g, m, l, n)) ? 0u : 1u;
@@ -662,7 +649,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_ekeep(Wo w)
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q > w.NO) return;
     if (q == w.NO) { w.ekeep[q] = 0; return; }
-    const uint64_t g = ub64(w.k2v_off, 0, (uint64_t)w.ng + 1, q) - 1;
+    const uint64_t g = upper_bound(w.k2v_off, 0, (uint64_t)w.ng + 1, q) - 1;
     const uint64_t nk = w.key_off[g + 1] - w.key_off[g], local = q - w.k2v_off[g];
     w.ekeep[q] = local >= nk ? w.keep[w.val_off[g] + (uint32_t)w.k2v[q]] : 0u;
 }
@@ -694,7 +681,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_keys(Wo w)
 {
     const uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i >= w.NK) return;
-    const uint64_t g = ub64(w.key_off, 0, (uint64_t)w.ng + 1, i) - 1;
+    const uint64_t g = upper_bound(w.key_off, 0, (uint64_t)w.ng + 1, i) - 1;
     if (w.kind[g] != ACC_WITHOUT_NONE) w.key_idx[w.key_out[g] + (i - w.key_off[g])] = (uint32_t)(i - w.key_off[g]);
 }
 
@@ -702,7 +689,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_vals(Wo w)
 {
     const uint64_t s = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (s >= w.NV) return;
-    const uint64_t g = ub64(w.val_off, 0, (uint64_t)w.ng + 1, s) - 1;
+    const uint64_t g = upper_bound(w.val_off, 0, (uint64_t)w.ng + 1, s) - 1;
     const uint32_t local = (uint32_t)(s - w.val_off[g]);
     const uint8_t kd = w.kind[g];
     if (kd == ACC_WITHOUT_FROM) w.val_idx[w.val_out[g] + local] = local;
@@ -714,7 +701,7 @@ __global__ __launch_bounds__(BLOCK) void k_wo_ints(Wo w)
 {
     const uint64_t q = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (q >= w.NO) return;
-    const uint64_t g = ub64(w.k2v_off, 0, (uint64_t)w.ng + 1, q) - 1;
+    const uint64_t g = upper_bound(w.k2v_off, 0, (uint64_t)w.ng + 1, q) - 1;
     const uint8_t kd = w.kind[g];
     if (kd == ACC_WITHOUT_NONE) return;
     const uint64_t o0 = w.k2v_off[g], local = q - o0, base = w.k2v_out[g];

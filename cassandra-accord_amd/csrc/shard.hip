@@ -11,6 +11,7 @@
 //            lays them out as acc_merge_in replies and runs the batched KeyDeps.merge (merge.hip), which is
 //            PartialDeps.with folded over the shards (KeyDeps.with = linearUnion, primitives/KeyDeps.java:238-253).
 #include "prims.hpp"
+#include "search.hpp"
 
 #include <vector>
 
@@ -154,16 +155,6 @@ struct Fuse {
     uint32_t *scratch;
 };
 
-__device__ __forceinline__ uint32_t lb_u32(const uint32_t *a, uint32_t n, uint32_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // copy keys + re-index keysToTxnIds of group g given its union u[0..U) (LDS or global); `tid`/`nth` = this thread's
 // index among the cooperating threads (a wave or a workgroup)
 __device__ __forceinline__ void fuse_emit(const Fuse &f, uint32_t g, const uint32_t *u, uint32_t U, uint32_t tid, uint32_t nth)
@@ -179,7 +170,7 @@ __device__ __forceinline__ void fuse_emit(const Fuse &f, uint32_t g, const uint3
         const uint32_t *vals = f.vals + f.rv[r];
         for (uint64_t j = tid; j < nk; j += nth) f.m_k2v[oo + kb + j] = (int32_t)(NK + eb + ((uint64_t)src[j] - nk));
         for (uint64_t i = tid; i < no - nk; i += nth)
-            f.m_k2v[oo + NK + eb + i] = (int32_t)lb_u32(u, U, vals[src[nk + i]]);
+            f.m_k2v[oo + NK + eb + i] = (int32_t)lower_bound(u, 0, U, vals[src[nk + i]]);
     }
 }
 

@@ -1,9 +1,11 @@
-// ts.hpp — the one definition of Timestamp order and of Kind.witnesses() on the device, shared by every path that
-// compares TxnIds / executeAts or filters by kind (keydeps, rangedeps, cfk, cfkdeps, conflicts, recovery, rmm).
+// ts.hpp — the one definition of Timestamp order, of the Timestamp value type Ts that carries it, and of
+// Kind.witnesses() on the device, shared by every path that compares TxnIds / executeAts or filters by kind (keydeps,
+// rangedeps, cfk, cfkdeps, conflicts, recovery, rmm, the resident stores). search.hpp has the searches in this order.
 // latest.hip's Ballot compare and wire.hip's Big::cmp are other orders and keep their own code.
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace acc {
@@ -25,6 +27,17 @@ __device__ __forceinline__ int ts_cmp(uint64_t am, uint64_t al, int32_t an, uint
     if (an != bn) return an < bn ? -1 : 1;
     return 0;
 }
+
+// A Timestamp (TxnId, executeAt, bound) by value: msb, lsb, node. Stored as such in cfkdeps.hip's device buffers.
+struct Ts {
+    uint64_t m, l;
+    int32_t n;
+};
+static_assert(sizeof(Ts) == 24 && offsetof(Ts, n) == 16, "Ts is stored in device buffers: 24 B, node at 16");
+__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
+__device__ __forceinline__ bool is_null(const Ts &a) { return a.m == 0 && a.l == 0 && a.n == 0; }   // Timestamp.NONE / absent
+// element i of a column triple
+__device__ __forceinline__ Ts ts_at(const uint64_t *m, const uint64_t *l, const int32_t *n, uint32_t i) { return Ts{ m[i], l[i], n[i] }; }
 
 // Kind.witnesses() as a bitmask over Kind ordinals (primitives/Txn.java:221-236); 0 = throws.
 __device__ __forceinline__ uint32_t witnesses(uint32_t kind)

@@ -26,7 +26,7 @@
 #include "dict.hpp"
 #include "prims.hpp"
 #include "rcmd_partial.hpp"
-#include "ts.hpp"
+#include "search.hpp"
 
 #include <chrono>
 
@@ -51,9 +51,6 @@ __host__ __device__ __forceinline__ uint32_t tier_of(uint32_t n_dep, uint32_t fo
     return forced ? forced : n_dep <= WT_LANE_MAX ? T_LANE : T_WAVE;
 }
 
-struct Ts { uint64_t m, l; int32_t n; };
-__device__ __forceinline__ int cmp(const Ts &a, const Ts &b) { return ts_cmp(a.m, a.l, a.n, b.m, b.l, b.n); }
-__device__ __forceinline__ bool is_null(const Ts &a) { return a.m == 0 && a.l == 0 && a.n == 0; }
 
 // the table as the kernels see it
 struct Tab {
@@ -83,28 +80,12 @@ struct Rc {
 __device__ __forceinline__ Ts txn_of(const Tab &t, uint32_t r) { return Ts{ t.tm[r], t.tl[r], t.tn[r] }; }
 __device__ __forceinline__ Ts x_of(const Tab &t, uint32_t r) { return Ts{ t.xm[r], t.xl[r], t.xn[r] }; }
 __device__ __forceinline__ Ts dep_of(const Tab &t, uint32_t s) { return Ts{ t.dm[s], t.dl[s], t.dn[s] }; }
-__device__ __forceinline__ Ts ts_at(const uint64_t *m, const uint64_t *l, const int32_t *n, uint32_t i) { return Ts{ m[i], l[i], n[i] }; }
 __device__ __forceinline__ uint32_t clr_of(uint32_t flags) { return flags & ACC_WT_RANGE_DOMAIN ? ACC_WT_APPLIED_OR_INVALIDATED : ACC_WT_NOT_WAITING; }
-
-// last index i of off[0, n) with off[i] <= v (the one non-empty segment that holds element v)
-__device__ __forceinline__ uint32_t seg_of(const uint32_t *off, uint32_t n, uint32_t v)
-{
-    uint32_t lo = 0, hi = n;
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (off[m] <= v) lo = m; else hi = m; }
-    return lo;
-}
-
-// first element of [lo, hi) of the columns that is >= t
-__device__ __forceinline__ uint32_t lower_ts(const uint64_t *m, const uint64_t *l, const int32_t *n, uint32_t lo, uint32_t hi, const Ts &t)
-{
-    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cmp(ts_at(m, l, n, mid), t) < 0) lo = mid + 1; else hi = mid; }
-    return lo;
-}
 
 // the element of [lo, hi) that equals t, or NONE
 __device__ __forceinline__ uint32_t find_ts(const uint64_t *m, const uint64_t *l, const int32_t *n, uint32_t lo, uint32_t hi, const Ts &t)
 {
-    const uint32_t p = lower_ts(m, l, n, lo, hi, t);
+    const uint32_t p = lower_bound_ts(m, l, n, lo, hi, t);
     return p < hi && cmp(ts_at(m, l, n, p), t) == 0 ? p : NONE;
 }
 
@@ -291,7 +272,7 @@ __global__ __launch_bounds__(BLOCK) void k_wt_reg_waiters(In d, Tab S, Rc rc, ui
     w0[i] = id.m;
     w1[i] = ts_w1(id.l);
     w2[i] = ts_w2(id.n);
-    const uint32_t p = lower_ts(S.tm, S.tl, S.tn, 0, S.nr, id);
+    const uint32_t p = lower_bound_ts(S.tm, S.tl, S.tn, 0, S.nr, id);
     if (p < S.nr && cmp(txn_of(S, p), id) == 0) e |= E_DUP;
     lb[i] = p;
     const uint32_t row = find_ts(rc.tm, rc.tl, rc.tn, 0, rc.n, id);
@@ -336,11 +317,7 @@ __global__ __launch_bounds__(BLOCK) void k_wt_place(In d, Tab S, const uint32_t 
     if (i >= S.nr + d.nw) return;
     if (i < S.nr) {
         const Ts id = txn_of(S, i);
-        uint32_t lo = 0, hi = d.nw;
-        while (lo < hi) {
-            const uint32_t m = (lo + hi) >> 1, w = perm ? perm[m] : m;
-            if (cmp(ts_at(d.tm, d.tl, d.tn, w), id) < 0) lo = m + 1; else hi = m;
-        }
+        const uint32_t lo = partition_point(0u, d.nw, [&](uint32_t m) { return cmp(ts_at(d.tm, d.tl, d.tn, perm ? perm[m] : m), id) < 0; });
         const uint32_t q = i + lo;
         o.srco[q] = i; o.srcw[q] = NONE;
         o.kc[q] = S.key_off[i + 1] - S.key_off[i];
@@ -471,13 +448,9 @@ __global__ __launch_bounds__(BLOCK) void k_wt_ranges(Ids c, Tab S, uint32_t *__r
     if (i >= c.n) return;
     const Ts id = ts_at(c.m, c.l, c.nn, i);
     if (i > 0 && cmp(ts_at(c.m, c.l, c.nn, i - 1), id) >= 0) err(errs, E_CHANGED);
-    uint32_t lo = 0, hi = S.nd;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (cmp(dep_of(S, S.idx[m]), id) < 0) lo = m + 1; else hi = m; }
-    const uint32_t first = lo;
-    hi = S.nd;
-    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (cmp(dep_of(S, S.idx[m]), id) <= 0) lo = m + 1; else hi = m; }
+    const uint32_t first = partition_point(0u, S.nd, [&](uint32_t m) { return cmp(dep_of(S, S.idx[m]), id) < 0; });
     clo[i] = first;
-    ccnt[i] = lo - first;
+    ccnt[i] = partition_point(first, S.nd, [&](uint32_t m) { return cmp(dep_of(S, S.idx[m]), id) <= 0; }) - first;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_wt_expand(uint32_t n, uint32_t nc, const uint32_t *__restrict__ coff, const uint32_t *__restrict__ clo,
@@ -548,8 +521,7 @@ __global__ __launch_bounds__(BLOCK) void k_wt_rel_apply(Rel q, const uint64_t *_
         const uint32_t i = src[p2];
         if (q.flags[i] & ACC_WT_REL_KEY) {
             const uint64_t c = q.key[i];
-            uint32_t lo = k0, hi = k1;
-            while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (W.key[m] < c) lo = m + 1; else hi = m; }
+            const uint32_t lo = lower_bound(W.key, k0, k1, c);
             if (lo < k1 && W.key[lo] == c && W.kw[lo]) { W.kw[lo] = 0; ++released; }
             else ++ignored;
         }

@@ -20,6 +20,7 @@
 // with more nonzero digits are rejected. DOUBLE egress is Double.toString: the shortest decimal that rounds back to
 // the value, closest on ties (JDK >= 19; JDK-4511638 changed a few outputs of older JDKs), with Java's layout rules.
 #include "dict.hpp"
+#include "search.hpp"
 
 namespace acc {
 
@@ -536,8 +537,7 @@ __global__ __launch_bounds__(BLOCK) void k_json_reply_offs(uint64_t R, Sing s, u
     const uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (r > R) return;
     if (r == R) { koff[r] = s.kb[s.nd]; roff[r] = s.rb[s.nd]; return; }
-    uint32_t lo = 0, hi = s.nd;   // document d: rep_off[d] <= r < rep_off[d + 1]
-    while (hi - lo > 1) { const uint32_t m = (lo + hi) >> 1; if (s.rep_off[m] <= r) lo = m; else hi = m; }
+    const uint32_t lo = seg_of(s.rep_off, s.nd, r);   // document d: rep_off[d] <= r < rep_off[d + 1]
     const uint64_t q = r - s.rep_off[lo];
     koff[r] = s.kb[lo] + min(q, s.nk[lo]);
     roff[r] = s.rb[lo] + min(q, s.nr[lo]);

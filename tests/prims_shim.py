@@ -1,4 +1,4 @@
-"""ctypes binding of the test shim over csrc/prims.hpp (accord_amd/libaccord_prims_test.so, csrc/prims_test.hip): numpy
+"""ctypes binding of the test shim over csrc/prims.hpp and csrc/search.hpp (accord_amd/libaccord_prims_test.so, csrc/prims_test.hip): numpy
 arrays in, numpy arrays out, on a context of the main library. A missing library or symbol raises: nothing here skips.
 
 ACC_PRIMS_TEST_LIB names another build of the shim (a deliberately mutated prims.hpp, to see which test notices)."""
@@ -40,6 +40,12 @@ _SIGS = {
     "acct_block_bitonic": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p],
     "acct_chunk_owners": [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p],
     "acct_pext_runs": [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)],
+    "acct_search_bound": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_uint32, C.c_void_p],
+    "acct_seg_of": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "acct_find_sorted": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p],
+    "acct_ts_bound": [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 5 + [C.c_uint32, C.c_void_p],
+    "acct_wave_search": [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p],
 }
 
 
@@ -161,3 +167,45 @@ class Shim:
         out, bits, nruns = np.zeros(len(w), np.uint64), C.c_int(-1), C.c_int(-1)
         self.ctx.check(self.lib.acct_pext_runs(self.h, mask, _p(w), len(w), _p(out), C.byref(bits), C.byref(nruns)))
         return out, bits.value, nruns.value
+
+    # ---- csrc/search.hpp: every method returns (results, the guard element behind them)
+
+    def search_bound(self, a, lo, hi, v, upper, idx64):
+        """lower_bound / upper_bound over a (u32 or u64), query q over the window [lo[q], hi[q]) for v[q]"""
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.uint32, np.uint64)
+        lo, hi, v = (np.ascontiguousarray(x, dtype=np.uint64) for x in (lo, hi, v))
+        out = np.zeros(len(v) + 1, np.uint64)
+        self.ctx.check(self.lib.acct_search_bound(self.h, int(a.dtype == np.uint64), int(idx64), int(upper), _p(a), len(a),
+                                                  _p(lo), _p(hi), _p(v), len(v), _p(out)))
+        return out[:-1], out[-1]
+
+    def seg_of(self, off, v):
+        off, v = np.ascontiguousarray(off, dtype=np.uint32), np.ascontiguousarray(v, dtype=np.uint32)
+        out = np.zeros(len(v) + 1, np.uint32)
+        self.ctx.check(self.lib.acct_seg_of(self.h, _p(off), len(off), _p(v), len(v), _p(out)))
+        return out[:-1], out[-1]
+
+    def find_sorted(self, a, v):
+        a, v = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(v, dtype=np.uint64)
+        out = np.zeros(len(v) + 1, np.uint32)
+        self.ctx.check(self.lib.acct_find_sorted(self.h, _p(a), len(a), _p(v), len(v), _p(out)))
+        return out[:-1], out[-1]
+
+    def ts_bound(self, cols, lo, hi, qcols, upper):
+        """cols / qcols: (msb u64, lsb u64, node i32) column triples"""
+        m, l, n = (np.ascontiguousarray(x, dtype=t) for x, t in zip(cols, (np.uint64, np.uint64, np.int32)))
+        qm, ql, qn = (np.ascontiguousarray(x, dtype=t) for x, t in zip(qcols, (np.uint64, np.uint64, np.int32)))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint32), np.ascontiguousarray(hi, dtype=np.uint32)
+        out = np.zeros(len(qm) + 1, np.uint32)
+        self.ctx.check(self.lib.acct_ts_bound(self.h, int(upper), _p(m), _p(l), _p(n), len(m), _p(lo), _p(hi), _p(qm), _p(ql),
+                                              _p(qn), len(qm), _p(out)))
+        return out[:-1], out[-1]
+
+    def wave_search(self, a, lo, hi, v, upper):
+        """-> (results[nq, 64]: every lane's, the guard element)"""
+        a, v = np.ascontiguousarray(a, dtype=np.uint64), np.ascontiguousarray(v, dtype=np.uint64)
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint32), np.ascontiguousarray(hi, dtype=np.uint32)
+        out = np.zeros(len(v) * 64 + 1, np.uint32)
+        self.ctx.check(self.lib.acct_wave_search(self.h, _p(a), len(a), _p(lo), _p(hi), _p(v), int(upper), len(v), _p(out)))
+        return out[:-1].reshape(len(v), 64), out[-1]
